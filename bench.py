@@ -14,8 +14,10 @@ scaling); the bar that straddles a shard boundary is stitched by a single neighb
 bar's raw ticks per step: ncclSend/ncclRecv of librccl behind the C ABI (fmk_comm_*, csrc/fmk_comm.hip), on its own
 stream, ordered against the compute stream by events -- no host synchronisation inside a step (finmlkit_amd/dist.py).
 
-Prints ONE JSON line on rank 0 (see the contract in the task statement); `roofline` describes the
-dominant kernel (k_bar_ohlcv: 12 algorithmic B/tick), `cpu_baseline` the scalar C oracle on this host.
+Prints ONE JSON line on rank 0: `value` in ticks/s, `ms_per_step` per timed step; `roofline` describes the dominant kernel
+(k_bar_ohlcv: 12 algorithmic B/tick, HIP events of the timed steps).  A plain run does only that; `--full` adds what takes runs of
+its own: `cpu_baseline` (the scalar C oracle on this host), `other_configs` and `roofline.placed`.  `--dump-outputs DIR` writes what
+the last timed step computed as DIR/<name>.npy.
 """
 from __future__ import annotations
 
@@ -110,9 +112,15 @@ def parse():
     ap.add_argument("--ticks", type=int, default=1_000_000_000, help="ticks per GPU")
     ap.add_argument("--interval", type=float, default=60.0)
     ap.add_argument("--no-median", action="store_true", help="skip the median trade size (not the reference path)")
-    ap.add_argument("--cpu-sample", type=int, default=200_000_000, help="ticks of the CPU-baseline sample (0: skip)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline (1 GPU): the CPU baseline, the informational cfg 3 / cfg 4 / next-row timings and the placed "
+                         "probe -- off by default, a plain run times the steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps: the arrays the last step computed (bar clock, close indices, OHLCV fields) as "
+                         "DIR/<name>.npy in float64 (float32 where computed so), at most 64 MB in all (1 process only)")
+    ap.add_argument("--cpu-sample", type=int, default=200_000_000, help="with --full: ticks of the CPU-baseline sample (0: skip)")
     ap.add_argument("--seed", type=int, default=42)
-    ap.add_argument("--no-extras", action="store_true", help="skip the informational cfg 3 / cfg 4 timings")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the informational cfg 3 / cfg 4 timings")
     ap.add_argument("--force-dist", action="store_true",
                     help="run the sharded step with 1 rank: RCCL communicator of size 1, the rank is its own neighbour "
                          "(ncclSend/ncclRecv to self), plus the boundary-bar launches -- the per-step overhead of the "
@@ -123,12 +131,38 @@ def parse():
                          "DeviceTrades.place() (finmlkit_amd/engine.py: K positions, one every 16 GiB of ONE allocation, probed with the step) "
                          "BEFORE the timed region and the headline is measured on the chosen position -- a diagnostic, roofline.placement says so")
     ap.add_argument("--placed-probe", type=int, default=7,
-                    help="after the timed region (1 GPU): the same step on columns placed by the library's opt-in DeviceTrades.place() with this many "
+                    help="with --full, after the timed region (1 GPU): the same step on columns placed by the library's opt-in DeviceTrades.place() with this many "
                          "positions -> roofline.placed (0: skip); never part of `value` / `frac`")
     ap.add_argument("--separate-index", action="store_true",
                     help="the step as two library calls (time-bar indexer kernels, then OHLCV + median) instead of the one-launch "
                          "fmk_time_bars_ohlcv_dev -- for A/B timing")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.dump_outputs and (args.gpus > 1 or int(os.environ.get("WORLD_SIZE", "1")) > 1):
+        ap.error("--dump-outputs writes the outputs of one process: use it with --gpus 1")
+    return args
+
+
+DUMP_BUDGET = 64_000_000     # bytes --dump-outputs may write in all
+
+
+def dump_outputs(d, arrays, seed):
+    """--dump-outputs: `arrays` (name -> DeviceArray, what the last timed step handed its caller) as d/<name>.npy, float64 (float32
+    where the step computed float32).  If they do not fit DUMP_BUDGET, the same fixed, seeded sample of rows of every array (row numbers
+    in d/rows.npy), so that two builds on the same arguments can be compared file for file."""
+    import numpy as np
+    host = {k: v.to_host() for k, v in arrays.items()}
+    host = {k: a if a.dtype == np.float32 else a.astype(np.float64) for k, a in host.items()}
+    rows = min(len(a) for a in host.values())
+    per_row = sum(a.itemsize for a in host.values())
+    header = 128 * (len(host) + 1)                                    # one .npy header per file
+    if sum(a.nbytes for a in host.values()) + header > DUMP_BUDGET:
+        k = (DUMP_BUDGET - header) // (per_row + 8)
+        pick = np.sort(np.random.default_rng(seed).choice(rows, size=k, replace=False))
+        host = {name: a[pick] for name, a in host.items()}
+        host["rows"] = pick.astype(np.float64)
+    os.makedirs(d, exist_ok=True)
+    for name, a in host.items():
+        np.save(os.path.join(d, name + ".npy"), a)
 
 
 def cpu_baseline(args):
@@ -734,6 +768,14 @@ def run(args):
     total_launches = c_i64()
     ctx.call("fmk_profile_count", C.byref(total_launches))
     ctx.call("fmk_profile_enable", C.c_int(0))
+    if args.dump_outputs:
+        if use_dist:
+            clock, idx, out = shard.clock, shard.idx, shard.out
+        else:
+            ne = state["n_bars"] + 1
+            clock, idx = state["clock"].view(0, ne), state["idx"].view(0, ne)
+            out = {k: v.view(0, ne - 1) for k, v in state["out"].items()}
+        dump_outputs(args.dump_outputs, {"clock": clock, "close_idx": idx, **out}, args.seed)
 
     k_ms = [kms[i] for i in range(kn.value)]
     # the pipelined time-bar step launches the dominant kernel TWICE per step (the first eighth of the bars, then the rest): the
@@ -837,7 +879,7 @@ def run(args):
         if transport_note:
             line["config"]["transport_note"] = transport_note
             line["valid"] = False
-        if world == 1 and not use_dist and not placement and args.placed_probe > 1:
+        if args.full and world == 1 and not use_dist and not placement and args.placed_probe > 1:
             # AUXILIARY, after the timed region and outside `value` / `frac`: the same step on columns placed by the library's opt-in
             # DeviceTrades.place() -- what a caller who asks for it gets (the headline above is the default: columns as allocated)
             try:
@@ -862,7 +904,7 @@ def run(args):
                 del placed, fnp
             except Exception as e:                                   # noqa: BLE001 -- auxiliary
                 line["roofline"]["placed"] = {"error": f"{type(e).__name__}: {e}"}
-        if world == 1:
+        if args.full and world == 1:
             line["cpu_baseline"] = cpu_baseline(args)
             if not args.no_extras:
                 line["other_configs"] = other_configs(trades, ctx, args)

@@ -5,6 +5,7 @@ Every record cites the reference test that made the call and holds its arguments
 exception it raised).  `replay(target)` runs each record through a table of callables -- the oracle's (CPU tests) or the
 package's (GPU tests) -- and compares under the numerical contract of DESIGN.md 5.  Records of functions a target has no
 counterpart for must be listed in that target's `skip` table with a reason: nothing is dropped silently."""
+import hashlib
 import json
 import os
 
@@ -22,8 +23,30 @@ def load(path=PATH):
     return json.loads(bytes(d["__manifest__"]).decode()), d
 
 
+def digest(a):
+    """SHA-256 of an array's values as np.testing.assert_array_equal sees them: integers and booleans as int64, floats as float64 with
+    -0.0 folded into 0.0 and every NaN made the same, plus the shape and which of the two kinds it is"""
+    a = np.asarray(a)
+    whole = a.dtype.kind in "biu"
+    c = a.astype(np.int64) if whole else a.astype(np.float64) + 0.0
+    if not whole:
+        c[np.isnan(c)] = np.nan
+    return hashlib.sha256(repr((whole, c.shape)).encode() + np.ascontiguousarray(c).tobytes()).hexdigest()[:32]
+
+
+class Digest:
+    """a recorded answer kept as its digest only (the oracle matched it bit for bit when it was recorded)"""
+    def __init__(self, h):
+        self.h = h
+
+    def matches(self, a):
+        return isinstance(a, np.ndarray) and a.dtype != object and digest(a) == self.h
+
+
 def dec(e, d):
     t = e["t"]
+    if t == "digest":
+        return Digest(e["h"])
     if t == "py":
         return e["v"]
     if t == "int":
