@@ -76,9 +76,9 @@ int fmk_ctx_create(int device, fmk_ctx **out)
     CK(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
     CK(hipEventCreate(&c->ev0));
     CK(hipEventCreate(&c->ev1));
-    CK(hipHostMalloc((void **)&c->h_mail, 64 * sizeof(int64_t), hipHostMallocDefault));
-    memset(c->h_mail, 0, 64 * sizeof(int64_t));
-    CK(hipMalloc((void **)&c->d_mail, 64 * sizeof(int64_t)));
+    CK(hipHostMalloc((void **)&c->h_mail, sizeof(fmk_mail), hipHostMallocDefault));
+    memset(c->h_mail, 0, sizeof(fmk_mail));
+    CK(hipMalloc((void **)&c->d_mail, sizeof(fmk_mail)));
 #undef CK
     *out = c;
     return FMK_OK;
@@ -127,12 +127,12 @@ int fmk_ctx_trim(fmk_ctx *ctx)
 }
 
 // Kernels that wait for other workgroups inside a launch (the one-pass scans) bound their spins and, instead of hanging,
-// raise h_mail[40] (pinned host memory the device writes directly); it is looked at whenever the host waits for the stream.
+// raise fmk_mail::device_error (pinned host memory the device writes directly); it is looked at whenever the host waits for the stream.
 static int fmk_check_device_error(fmk_ctx *ctx)
 {
-    if (ctx->h_mail[40] != 0) {
-        const long long code = (long long)ctx->h_mail[40];
-        ctx->h_mail[40] = 0;
+    if (ctx->h_mail->device_error != 0) {
+        const long long code = (long long)ctx->h_mail->device_error;
+        ctx->h_mail->device_error = 0;
         return fmk_set_error(ctx, FMK_E_HIP, "a one-pass scan kernel gave up waiting for another workgroup (code %lld); "
                              "its output is not valid", code);
     }
@@ -147,6 +147,26 @@ int fmk_ctx_sync(fmk_ctx *ctx)
 }
 
 void *fmk_ctx_stream(fmk_ctx *ctx) { return (void *)ctx->stream; }
+
+}  // extern "C"
+
+int fmk_wait(fmk_ctx *ctx, hipError_t queued)
+{
+    const hipError_t w = hipStreamSynchronize(ctx->stream);
+    const hipError_t e = queued != hipSuccess ? queued : w;
+    if (e != hipSuccess) return fmk_set_error(ctx, FMK_E_HIP, "read-back from the device failed: %s", hipGetErrorString(e));
+    return FMK_OK;
+}
+
+int fmk_read_back(fmk_ctx *ctx, void *dst, const void *d_src, size_t bytes)
+{
+    if (bytes > sizeof ctx->h_mail->staging) return fmk_set_error(ctx, FMK_E_ARG, "read-back of %zu bytes: too large", bytes);
+    FMK_TRY(fmk_wait(ctx, hipMemcpyAsync(ctx->h_mail->staging, d_src, bytes, hipMemcpyDeviceToHost, ctx->stream)));
+    memcpy(dst, ctx->h_mail->staging, bytes);
+    return FMK_OK;
+}
+
+extern "C" {
 
 // ---------------------------------------------------------------------------------------
 // Caching allocator.  Everything the library enqueues runs on the context's ONE stream, so a block that is freed

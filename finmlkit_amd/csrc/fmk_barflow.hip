@@ -1128,6 +1128,7 @@ static void bf_redo_launch(fmk_ctx *ctx, unsigned rblocks, const double *d_price
 //   k_bs_scatter: perm[offset[class][block] + rank inside (block, class)] = bar
 // ---------------------------------------------------------------------------------------
 #define BS_CLASSES 128
+static_assert(BS_CLASSES * sizeof(int64_t) <= sizeof(fmk_mail::staging), "the class totals come back through fmk_read_back");
 #define BS_BLOCK 1024
 __device__ __forceinline__ int bs_class(int64_t len)            // 0: the longest ... 127: empty / negative
 {
@@ -1191,10 +1192,9 @@ static int bf_bar_census(fmk_ctx *ctx, const int64_t *d_ci, int64_t nb, int64_t 
     k_bs_hist<<<(unsigned)nblk, 256, 0, ctx->stream>>>(d_ci, nb, nblk, hist);
     k_bs_totals<<<BS_CLASSES, 256, 0, ctx->stream>>>(hist, nblk, tot);
     int64_t h[BS_CLASSES];
-    hipError_t e = hipGetLastError();
-    if (e == hipSuccess) e = hipMemcpyAsync(h, tot, sizeof(h), hipMemcpyDeviceToHost, ctx->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    if (e != hipSuccess) { (void)fmk_free(ctx, p_hist); return fmk_set_error(ctx, FMK_E_HIP, "bar census: %s", hipGetErrorString(e)); }
+    const hipError_t e = hipGetLastError();
+    const int rc = e != hipSuccess ? fmk_set_error(ctx, FMK_E_HIP, "bar census: %s", hipGetErrorString(e)) : fmk_read_back(ctx, h, tot, sizeof h);
+    if (rc != FMK_OK) { (void)fmk_free(ctx, p_hist); return rc; }
     int64_t best = 0, run = 0;
     for (int c = 0; c < BS_CLASSES - 1; ++c) {                       // (class 127: empty bars -- they cost nothing anywhere)
         run += h[c];
@@ -1700,13 +1700,14 @@ static int bars_flow_fused_ok(fmk_ctx *ctx, const void *d_amount, int amount_is_
     // 12.6 / 8.9).  Without the histogram (sizes that do not certify) it only pays where the two-pass form starts to hand bars to its
     // long-bar classes: 7.05 / 7.33 at 1 260, 7.32 / 7.88 at 1 340, 7.45 / 8.56 at 1 400, but 9.3 / 8.2 at 600 and 14.6 / 11.9 at 300.
     if (mean < 256 || mean > 1400 || nb < (int64_t)ctx->n_cu * 8) return FMK_OK;
-    int *d = (int *)(ctx->d_mail + 44);
+    int *d = ctx->d_mail->bf.fu_census;
     const int init[3] = {FP_Q_UNKNOWN, -1000, 0};
+    static_assert(sizeof init == sizeof ctx->d_mail->bf.fu_census, "k_fu_census: three ints");
     FMK_HIP(ctx, hipMemcpyAsync(d, init, sizeof init, hipMemcpyHostToDevice, ctx->stream));
     k_fu_census<<<16, 256, 0, ctx->stream>>>((const float *)d_amount, n, d);
     FMK_LAUNCH_CHECK(ctx);
-    int got[3];
-    FMK_HIP(ctx, hipMemcpyAsync(got, d, sizeof got, hipMemcpyDeviceToHost, ctx->stream));
+    const int *got = ctx->h_mail->bf.fu_census;                      // (pinned: the copy may outlive an early return)
+    FMK_HIP(ctx, hipMemcpyAsync(ctx->h_mail->bf.fu_census, d, sizeof init, hipMemcpyDeviceToHost, ctx->stream));
     // ... and the bars are of about equal length (the census of bf_bar_census: 80 % of them within a factor 2.4).  On a tape of
     // lognormal lengths most TICKS lie in bars of several tiles, whose medians the long-bar kernels take in a pass of their own --
     // measured at sigma = 1, full-mantissa sizes: 14.2 ms against 11.9 for the sorted-lane schedule below.  One wait for both answers.
@@ -1717,11 +1718,10 @@ static int bars_flow_fused_ok(fmk_ctx *ctx, const void *d_amount, int amount_is_
     k_bs_hist<<<(unsigned)nblk, 256, 0, ctx->stream>>>(d_ci, nb, nblk, hist);
     k_bs_totals<<<BS_CLASSES, 256, 0, ctx->stream>>>(hist, nblk, tot);
     int64_t h[BS_CLASSES];
-    hipError_t ce = hipGetLastError();
-    if (ce == hipSuccess) ce = hipMemcpyAsync(h, tot, sizeof(h), hipMemcpyDeviceToHost, ctx->stream);
-    if (ce == hipSuccess) ce = hipStreamSynchronize(ctx->stream);
+    const hipError_t ce = hipGetLastError();
+    const int crc = ce != hipSuccess ? fmk_set_error(ctx, FMK_E_HIP, "bar census: %s", hipGetErrorString(ce)) : fmk_read_back(ctx, h, tot, sizeof h);
     (void)fmk_free(ctx, p_hist);
-    if (ce != hipSuccess) return fmk_set_error(ctx, FMK_E_HIP, "bar census: %s", hipGetErrorString(ce));
+    FMK_TRY(crc);
     {
         int64_t best = 0, run = 0;
         for (int c = 0; c < BS_CLASSES - 1; ++c) {
@@ -1779,7 +1779,7 @@ static int bars_flow_fused(fmk_ctx *ctx, const double *d_price, const float *d_a
     rc = fmk_scratch(ctx, (size_t)(nb + 32) * 24, (void **)&redo);
     if (rc != FMK_OK) { fmk_fused_release(ctx); return rc; }
     unsigned long long *dir_list = redo + nb + 32, *redo_fu = redo + 2 * (nb + 32);
-    int *saw_long = (int *)(ctx->d_mail + 18);
+    int *saw_long = ctx->d_mail->bf.fu_long;
     FuLists li{redo_fu, redo, dir_list, st->fp_list, saw_long, saw_long + 1};
     auto fail = [&](int code) { fmk_fused_release(ctx); return code; };
 #define FU_HIP(expr) do { const hipError_t e__ = (expr); if (e__ != hipSuccess) return fail(fmk_set_error(ctx, FMK_E_HIP, "%s failed: %s", #expr, hipGetErrorString(e__))); } while (0)
@@ -1848,13 +1848,14 @@ static int bars_flow_fused(fmk_ctx *ctx, const double *d_price, const float *d_a
     FU_HIP(hipGetLastError());
     k_bar_dir_redo<false><<<(unsigned)dblocks, 256, 0, ctx->stream>>>(d_price, d_amount, d_side, d_close_idx, n, o, redo_fu);
     FU_HIP(hipGetLastError());
-    FU_HIP(hipMemcpyAsync(&ctx->h_mail[14], st->fp_list, 8, hipMemcpyDeviceToHost, ctx->stream));
-    FU_HIP(hipMemcpyAsync(&ctx->h_mail[15], dir_list, 8, hipMemcpyDeviceToHost, ctx->stream));
-    FU_HIP(hipMemcpyAsync(&ctx->h_mail[16], redo_fu, 8, hipMemcpyDeviceToHost, ctx->stream));
+    auto &last = ctx->h_mail->fused_last;
+    FU_HIP(hipMemcpyAsync(&last.n_fp, st->fp_list, 8, hipMemcpyDeviceToHost, ctx->stream));
+    FU_HIP(hipMemcpyAsync(&last.n_dir, dir_list, 8, hipMemcpyDeviceToHost, ctx->stream));
+    FU_HIP(hipMemcpyAsync(&last.n_redo, redo_fu, 8, hipMemcpyDeviceToHost, ctx->stream));
 #undef FU_HIP
     rc = fmk_comp_bar_footprints_size_dev(ctx, d_low, d_high, nb, price_tick_size, d_level_offsets, total_levels, max_levels);
     if (rc != FMK_OK) return fail(rc);
-    st->n_fp = ctx->h_mail[14];                                      // (the sizing call has waited for the stream)
+    st->n_fp = last.n_fp;                                            // (the sizing call has waited for the stream)
     if (!units) fmk_fused_release(ctx);                              // nothing staged: the fill call is the ordinary one
     return FMK_OK;
 }
@@ -1902,9 +1903,9 @@ extern "C" int fmk_diag_fused_phases(fmk_ctx *ctx, int64_t *out4)
 // (bar, columns) entries of the tick-order redo
 extern "C" int fmk_diag_fused_last(fmk_ctx *ctx, int64_t *n_fp_list, int64_t *n_dir_list, int64_t *n_redo)
 {
-    *n_fp_list = ctx->h_mail[14];
-    *n_dir_list = ctx->h_mail[15];
-    *n_redo = ctx->h_mail[16];
+    *n_fp_list = ctx->h_mail->fused_last.n_fp;
+    *n_dir_list = ctx->h_mail->fused_last.n_dir;
+    *n_redo = ctx->h_mail->fused_last.n_redo;
     return FMK_OK;
 }
 
@@ -2126,7 +2127,7 @@ static int bars_flow_size(fmk_ctx *ctx, const double *d_price, const void *d_amo
         unsigned long long *redo;
         FMK_TRY(fmk_scratch(ctx, (size_t)(nb + 32) * 16, (void **)&redo));
         unsigned long long *long_list = redo + nb + 32;
-        int *any_long = (int *)(ctx->d_mail + 20);
+        int *any_long = &ctx->d_mail->bf.any_long;
         FMK_HIP(ctx, hipMemsetAsync(redo, 0, 8, ctx->stream));
         FMK_HIP(ctx, hipMemsetAsync(long_list, 0, 8, ctx->stream));
         FMK_HIP(ctx, hipMemsetAsync(any_long, 0, sizeof(int), ctx->stream));
@@ -2205,8 +2206,8 @@ static int bars_flow_size(fmk_ctx *ctx, const double *d_price, const void *d_amo
         // carry most of the ticks are then better served by comp_bar_ohlcv's own size classes (one pass, median included) than by
         // the generic leftover kernel plus the stand-alone median kernels -- measured at sigma 1: 20.0 ms for this call against
         // 14.3 ms for the three functions apart (tools/realcfg4.py).  One 8-byte read-back; the call waits for its sizing pass anyway.
-        FMK_HIP(ctx, hipMemcpyAsync(&ctx->h_mail[13], long_list, 8, hipMemcpyDeviceToHost, ctx->stream));
-        FMK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        int64_t n_long;
+        FMK_TRY(fmk_read_back(ctx, &n_long, long_list, 8));
         if (sort_mode && d_median) {
             // bars in order of length: the lanes have served every bar up to 8 192 ticks; the longer ones (listed) got their order flow from
             // k_bar_dir above; medians (and open .. trades of the bars beyond 1 344 ticks) by comp_bar_ohlcv's size classes
@@ -2216,7 +2217,7 @@ static int bars_flow_size(fmk_ctx *ctx, const double *d_price, const void *d_amo
                                                     max_levels);
         }
         if (side_median) FMK_HIP(ctx, hipStreamWaitEvent(ctx->stream, ctx->aev[1], 0));    // the medians of the auxiliary stream
-        if (ctx->h_mail[13] > nb / 50) {
+        if (n_long > nb / 50) {
             FMK_TRY(fmk_comp_bar_ohlcv_dev(ctx, d_price, d_amount, 0, n, d_close_idx, n_idx, d_open, d_high, d_low, d_close, d_volume,
                                            d_vwap, d_trades, d_median));
             return fmk_comp_bar_footprints_size_dev(ctx, d_low, d_high, n_idx - 1, price_tick_size, d_level_offsets, total_levels,
@@ -2245,7 +2246,7 @@ static int bars_flow_size(fmk_ctx *ctx, const double *d_price, const void *d_amo
         unsigned long long *redo;
         FMK_TRY(fmk_scratch(ctx, (size_t)(nb + 32) * 8, (void **)&redo));
         FMK_HIP(ctx, hipMemsetAsync(redo, 0, 8, ctx->stream));
-        int *saw_long = (int *)(ctx->d_mail + 16);
+        int *saw_long = &ctx->d_mail->bf.saw_long;
         FMK_HIP(ctx, hipMemsetAsync(saw_long, 0, sizeof(int), ctx->stream));
         if (d_median)
             k_bar_ohlcv_dir<true><<<(unsigned)blocks, 256, 0, ctx->stream>>>(d_price, (const float *)d_amount, d_side, d_close_idx,

@@ -12,6 +12,66 @@
 #define FMK_WAVE 64
 #define FMK_PROFILE_SLOTS 256              // launches fmk_profile_* can time between enable and read
 
+// The context's mailbox: small flags / counters the kernels leave for the host.  One device copy (fmk_ctx::d_mail, hipMalloc) and
+// one pinned host copy (fmk_ctx::h_mail, hipHostMalloc) of the same layout; every use has a field of its own, grouped by the file
+// that owns it.  A sub-struct is what one memset or one read-back covers.
+struct fmk_mail {
+    // ---- fields that outlive the call that writes them
+    // set by the device through the pinned host copy when a one-pass scan gives up waiting for another workgroup
+    // (k_ew_onepass_d, fmk_ticklevel.hip); read and cleared by fmk_check_device_error (fmk_api.hip) on every fmk_ctx_sync
+    int64_t device_error;
+    // status of the volume prefix pass (k_vc_prefix in vol_chase, fmk_volume.hip); read again by the table tiers of a later
+    // vol_chase(..., have_prefix = true) call on the same prefix (d_pstat)
+    int vol_prefix_status;
+    // [0] a bar beyond the in-sweep median's reach was met (flag of the call), [1] bars that took the generic selection (atomicAdd
+    // by k_bar_footprints<MED>, fmk_footprint.hip); [1] is read by fmk_diag_fp_median_fallbacks after the call
+    int fp_median[2];
+    // host copy only: the list sizes of the last one-pass cfg 4 sizing call (fmk_barflow.hip, queued without a wait: the sizing
+    // call waits later); read by fmk_diag_fused_last and by the fill call (n_fp)
+    struct { int64_t n_fp, n_dir, n_redo; } fused_last;
+
+    // ---- per-call fields
+    uint8_t staging[1024];                 // host copy: fmk_read_back's landing area
+    struct Vol {                           // fmk_volume.hip / fmk_volume_exact.h: the level tables
+        struct Levels { int status; uint32_t root; int root_tie; } lv;                          // k_vol_level0 / k_vol_level_up4
+        struct Table { uint32_t root; uint32_t maxlen; int status; unsigned long long nfrag; } tb;      // k_vg_* (vg_run)
+        struct Closes { uint32_t count; int status; } closes;                                   // host copy: vg_run's last batch
+        struct Chase { int64_t res; int prefix_status; } chase;                                 // host copy: vol_chase's batch
+        int64_t chase_res;                 // k_vc_chase: closes (or the total, total_only)
+        int mismatch;                      // k_vol_verify
+    } vol;
+    struct Dl {                            // fmk_dollar.hip
+        struct Pass1 { int bad; unsigned long long dmax; double whale; double total[2] /* hi, lo; not cleared */; } p1;
+        struct Emit { unsigned long long frag; int64_t res; unsigned long long area; } emit;       // res also: k_dl_scan_min
+        struct One { int64_t last; unsigned long long frag; int flags; } one;                     // k_dl1
+        double sample_sum;                 // k_dl1_sample
+    } dl;
+    struct { double total; int64_t res[2] /* count, uncertified */; } th;                      // fmk_threshold.hip
+    struct Cusum {                         // fmk_cusum.hip
+        struct Fill { unsigned long long first; long long nan_count; } ff;                      // k_ff_tile / k_ff_count
+        struct Round { unsigned long long changed, pending, nan; } round;                       // k_cs1_fix / k_cusum_chunks
+    } cusum;
+    struct Fp {                            // fmk_footprint.hip
+        unsigned long long max_levels;     // k_fp_level_counts
+        struct Sizes { int64_t total; unsigned long long max; } sizes;                          // host copy
+        int lds_probe;                     // k_fp_lds_order_probe
+    } fp;
+    struct { unsigned long long max; unsigned status; } vp;                                    // fmk_volprofile.hip
+    struct Ohlcv {                         // fmk_ohlcv.hip
+        int saw_long;                      // a bar longer than the small kernels take (also the pipelined step's host copy)
+        int64_t span[3];                   // k_list_span: listed bars, first tick, last tick
+    } ohlcv;
+    struct Bf {                            // fmk_barflow.hip
+        int fu_census[3];                  // k_fu_census: min low bit, max exponent, bad
+        int fu_long[2];                    // FuLists::saw_long, FuLists::saw_huge
+        int any_long;                      // k_bar_dir_lanes
+        int saw_long;                      // k_bar_ohlcv_dir
+    } bf;
+    struct { unsigned long long sink; long long hops[2]; } diag;                               // fmk_diag.hip
+};
+static_assert(sizeof(fmk_mail::fp_median) == 2 * sizeof(int), "k_bar_footprints adds to saw_long + 1");
+static_assert(alignof(fmk_mail) == 8, "the 64-bit atomics of the kernels need 8-byte fields");
+
 struct fmk_ctx {
     int device;
     hipStream_t stream;
@@ -20,9 +80,9 @@ struct fmk_ctx {
     // grow-on-demand device scratch (scan partials, flags)
     void *scratch;
     size_t scratch_bytes;
-    // small pinned host mailbox for flags / counters read back from the device
-    int64_t *h_mail;   // 64 x int64
-    int64_t *d_mail;   // 64 x int64
+    // the mailbox (fmk_mail): pinned host copy, device copy
+    fmk_mail *h_mail;
+    fmk_mail *d_mail;
     int n_cu;
     // per-launch timing of the dominant kernel (fmk_profile_enable)
     int profile_on, profile_n;
@@ -64,6 +124,11 @@ int fmk_time_bar_index_stage(fmk_ctx *ctx, hipStream_t st, const int64_t *d_ts, 
                              int *saw_long, int64_t long_min, int64_t max_blocks /* 0: one workgroup per 256 edges */);
 
 int fmk_set_error(fmk_ctx *ctx, int code, const char *fmt, ...);
+// Waits for the context's stream after copies to the host were queued (`queued`: the first failure among them, or hipSuccess): also
+// on failure, so that no copy is left in flight.  -> FMK_OK or FMK_E_HIP.
+int fmk_wait(fmk_ctx *ctx, hipError_t queued);
+// d_src -> dst (host memory of any kind, <= sizeof(fmk_mail::staging) bytes) through the pinned mailbox, then fmk_wait.
+int fmk_read_back(fmk_ctx *ctx, void *dst, const void *d_src, size_t bytes);
 int fmk_scratch(fmk_ctx *ctx, size_t bytes, void **out);
 // per-context result / work caches of the threshold indexers (released by fmk_ctx_trim and fmk_ctx_destroy)
 void fmk_volume_trim(fmk_ctx *ctx);

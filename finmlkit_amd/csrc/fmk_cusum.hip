@@ -528,10 +528,9 @@ static int cs1_run(fmk_ctx *ctx, const int64_t *d_ts, const double *d_price, con
     Cs1Fix *fix = (Cs1Fix *)(base + 5 * st_bytes + cnt_bytes + c0_bytes);
     unsigned short *staged = (unsigned short *)(base + 5 * st_bytes + cnt_bytes + c0_bytes + fix_bytes);
     unsigned short *patch = (unsigned short *)(base + 5 * st_bytes + cnt_bytes + c0_bytes + fix_bytes + row_bytes);
-    unsigned long long *d_changed = (unsigned long long *)(ctx->d_mail + 1), *d_pending = (unsigned long long *)(ctx->d_mail + 3);
-    unsigned long long *d_nan = (unsigned long long *)(ctx->d_mail + 5);
+    fmk_mail::Cusum::Round *d_round = &ctx->d_mail->cusum.round, r;
+    unsigned long long *d_changed = &d_round->changed, *d_pending = &d_round->pending, *d_nan = &d_round->nan;
     if (check_nan) FMK_HIP(ctx, hipMemsetAsync(d_nan, 0, 8, ctx->stream));
-    ctx->h_mail[5] = 0;
     FMK_HIP(ctx, hipMemsetAsync(fix, 0, fix_bytes, ctx->stream));
     {
         const unsigned g = (unsigned)fmk_ceil_div(chunks, (int64_t)CS1_TK);
@@ -545,9 +544,8 @@ static int cs1_run(fmk_ctx *ctx, const int64_t *d_ts, const double *d_price, con
     int limit = CS1_FIRST_LIMIT;
     int64_t launches = 0;
     if (check_nan && chunks <= 1) {
-        FMK_HIP(ctx, hipMemcpyAsync(&ctx->h_mail[5], d_nan, 8, hipMemcpyDeviceToHost, ctx->stream));
-        FMK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        if (ctx->h_mail[5] != 0) { *redo = true; return FMK_OK; }
+        FMK_TRY(fmk_read_back(ctx, &r.nan, d_nan, 8));
+        if (r.nan != 0) { *redo = true; return FMK_OK; }
     }
     while (chunks > 1) {
         FMK_HIP(ctx, hipMemcpyAsync(S_read, S, (size_t)chunks * sizeof(CsState), hipMemcpyDeviceToDevice, ctx->stream));
@@ -558,12 +556,9 @@ static int cs1_run(fmk_ctx *ctx, const int64_t *d_ts, const double *d_price, con
             d_changed, d_pending);
         FMK_LAUNCH_CHECK(ctx);
         ++launches; ++*rounds;
-        FMK_HIP(ctx, hipMemcpyAsync(&ctx->h_mail[1], d_changed, 8, hipMemcpyDeviceToHost, ctx->stream));
-        FMK_HIP(ctx, hipMemcpyAsync(&ctx->h_mail[3], d_pending, 8, hipMemcpyDeviceToHost, ctx->stream));
-        if (check_nan) FMK_HIP(ctx, hipMemcpyAsync(&ctx->h_mail[5], d_nan, 8, hipMemcpyDeviceToHost, ctx->stream));
-        FMK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        if (check_nan && ctx->h_mail[5] != 0) { *redo = true; return FMK_OK; }
-        const int64_t changed = ctx->h_mail[1], pending = ctx->h_mail[3];
+        FMK_TRY(fmk_read_back(ctx, &r, d_round, sizeof r));
+        if (check_nan && r.nan != 0) { *redo = true; return FMK_OK; }
+        const int64_t changed = (int64_t)r.changed, pending = (int64_t)r.pending;
         g_cs1_last[1] = launches;
         if (launches == 1) {
             g_cs1_last[2] = pending;
@@ -576,9 +571,7 @@ static int cs1_run(fmk_ctx *ctx, const int64_t *d_ts, const double *d_price, con
     k_cs1_counts<<<(unsigned)fmk_ceil_div(chunks, (int64_t)256), 256, 0, ctx->stream>>>(C0, fix, chunks, counts);
     FMK_LAUNCH_CHECK(ctx);
     FMK_TRY(fmk_exclusive_scan_i64(ctx, counts, counts, chunks, true));
-    FMK_HIP(ctx, hipMemcpyAsync(&ctx->h_mail[2], counts + chunks, 8, hipMemcpyDeviceToHost, ctx->stream));
-    FMK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    *total = ctx->h_mail[2];
+    FMK_TRY(fmk_read_back(ctx, total, counts + chunks, 8));
     if (d_out) {
         if (capacity < *total + 1)
             return fmk_set_error(ctx, FMK_E_CAPACITY, "cusum: %lld close indices, capacity %lld", (long long)(*total + 1),
@@ -618,8 +611,9 @@ extern "C" int fmk_cusum_bar_indexer_dev(fmk_ctx *ctx, const int64_t *d_ts, cons
     FMK_TRY(fmk_scratch(ctx, ff_bytes + (size_t)tiles * 4 + 256, &scr));
     double *tile_last = (double *)scr;
     int *tile_nan = (int *)((char *)scr + ff_bytes);
-    unsigned long long *d_first = (unsigned long long *)ctx->d_mail;
-    unsigned long long *d_changed = d_first + 1;
+    fmk_mail::Cusum::Fill *d_fill = &ctx->d_mail->cusum.ff;
+    unsigned long long *d_first = &d_fill->first;
+    unsigned long long *d_changed = &ctx->d_mail->cusum.round.changed;
     // ---- forward fill of sigma (in place) + first non-NaN index
     const unsigned long long big = ~0ULL;
     int64_t first = 0;
@@ -631,14 +625,13 @@ extern "C" int fmk_cusum_bar_indexer_dev(fmk_ctx *ctx, const int64_t *d_ts, cons
         FMK_HIP(ctx, hipMemcpyAsync(d_first, &big, 8, hipMemcpyHostToDevice, ctx->stream));
         k_ff_tile<<<(unsigned)tiles, FF_THREADS, 0, ctx->stream>>>(d_sigma, n, tile_last, d_first, tile_nan);
         FMK_LAUNCH_CHECK(ctx);
-        k_ff_count<<<1, 1024, 0, ctx->stream>>>(tile_nan, tiles, (long long *)(ctx->d_mail + 2));
+        k_ff_count<<<1, 1024, 0, ctx->stream>>>(tile_nan, tiles, &d_fill->nan_count);
         FMK_LAUNCH_CHECK(ctx);
-        FMK_HIP(ctx, hipMemcpyAsync(&ctx->h_mail[0], d_first, 8, hipMemcpyDeviceToHost, ctx->stream));
-        FMK_HIP(ctx, hipMemcpyAsync(&ctx->h_mail[2], ctx->d_mail + 2, 8, hipMemcpyDeviceToHost, ctx->stream));
-        FMK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        first = ctx->h_mail[0];
-        all_nan = (unsigned long long)first == big;
-        if (!all_nan && ctx->h_mail[2] != first) {                // NaNs after the first valid entry: fill them (logic.py:187-189)
+        fmk_mail::Cusum::Fill f;
+        FMK_TRY(fmk_read_back(ctx, &f, d_fill, sizeof f));
+        first = (int64_t)f.first;
+        all_nan = f.first == big;
+        if (!all_nan && f.nan_count != first) {                // NaNs after the first valid entry: fill them (logic.py:187-189)
             k_ff_scan_tiles<<<1, 1024, 0, ctx->stream>>>(tile_last, tiles);
             FMK_LAUNCH_CHECK(ctx);
             k_ff_apply<<<(unsigned)tiles, FF_THREADS, 0, ctx->stream>>>(d_sigma, n, tile_last);
@@ -656,9 +649,9 @@ extern "C" int fmk_cusum_bar_indexer_dev(fmk_ctx *ctx, const int64_t *d_ts, cons
             FMK_HIP(ctx, hipMemcpyAsync(d_first, &big, 8, hipMemcpyHostToDevice, ctx->stream));
             k_ff_head<<<16, 1024, 0, ctx->stream>>>(d_sigma, n_head, d_first);
             FMK_LAUNCH_CHECK(ctx);
-            FMK_HIP(ctx, hipMemcpyAsync(&ctx->h_mail[0], d_first, 8, hipMemcpyDeviceToHost, ctx->stream));
-            FMK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-            if ((unsigned long long)ctx->h_mail[0] != big) { first = ctx->h_mail[0]; head_ok = true; }
+            unsigned long long f = big;
+            FMK_TRY(fmk_read_back(ctx, &f, d_first, 8));
+            if (f != big) { first = (int64_t)f; head_ok = true; }
         }
         if (!head_ok) FMK_TRY(full_fill());
     }
@@ -698,9 +691,9 @@ extern "C" int fmk_cusum_bar_indexer_dev(fmk_ctx *ctx, const int64_t *d_ts, cons
                 if (one_done) break;
             }
         }
-        unsigned long long *d_nan = (unsigned long long *)(ctx->d_mail + 5);
+        fmk_mail::Cusum::Round *d_round = &ctx->d_mail->cusum.round, r;
+        unsigned long long *d_nan = &d_round->nan;
         if (check_nan) FMK_HIP(ctx, hipMemsetAsync(d_nan, 0, 8, ctx->stream));
-        ctx->h_mail[5] = 0;
         rounds = 0;
         FMK_TRY(fmk_scratch(ctx, scan_bytes + 3 * st_bytes + cnt_bytes + 2 * tr_bytes + act_bytes + list_bytes, &scr));
         char *base = (char *)scr + scan_bytes;
@@ -727,11 +720,9 @@ extern "C" int fmk_cusum_bar_indexer_dev(fmk_ctx *ctx, const int64_t *d_ts, cons
                                                                   counts, d_changed, nullptr, nullptr);
             FMK_LAUNCH_CHECK(ctx);
             ++rounds;
-            FMK_HIP(ctx, hipMemcpyAsync(&ctx->h_mail[1], d_changed, 8, hipMemcpyDeviceToHost, ctx->stream));
-            if (check_nan) FMK_HIP(ctx, hipMemcpyAsync(&ctx->h_mail[5], d_nan, 8, hipMemcpyDeviceToHost, ctx->stream));
-            FMK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-            if (check_nan && ctx->h_mail[5] != 0) { redo = true; break; }
-            if (ctx->h_mail[1] == 0) break;                       // fixed point: every chunk started from the truth
+            FMK_TRY(fmk_read_back(ctx, &r, d_round, sizeof r));
+            if (check_nan && r.nan != 0) { redo = true; break; }
+            if (r.changed == 0) break;                            // fixed point: every chunk started from the truth
             if (rounds > chunks + 2) return fmk_set_error(ctx, FMK_E_HIP, "cusum: fixed point did not converge");
             if (rounds >= 2) {
                 // how many dependency chains are left?  (heads: inconsistent chunks with a consistent predecessor)
@@ -739,9 +730,8 @@ extern "C" int fmk_cusum_bar_indexer_dev(fmk_ctx *ctx, const int64_t *d_ts, cons
                 k_cusum_mark<<<(unsigned)fmk_ceil_div(chunks, 256), 256, 0, ctx->stream>>>(cur, last_in, chunks, active, list,
                                                                                            d_changed);
                 FMK_LAUNCH_CHECK(ctx);
-                FMK_HIP(ctx, hipMemcpyAsync(&ctx->h_mail[1], d_changed, 8, hipMemcpyDeviceToHost, ctx->stream));
-                FMK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-                int64_t n_list = ctx->h_mail[1];
+                int64_t n_list;
+                FMK_TRY(fmk_read_back(ctx, &n_list, d_changed, 8));
                 // chunks a wave follows per launch: many walks start from inputs that are not final yet and are redone,
                 // so short legs waste little; measured at N = 1e9 in the slow regime: 4..16 within 3 %, 64: +30 %, 512: 3x
                 const int walk_steps = 8;
@@ -756,9 +746,7 @@ extern "C" int fmk_cusum_bar_indexer_dev(fmk_ctx *ctx, const int64_t *d_ts, cons
                     k_cusum_mark<<<(unsigned)fmk_ceil_div(chunks, 256), 256, 0, ctx->stream>>>(cur, last_in, chunks, active,
                                                                                                list, d_changed);
                     FMK_LAUNCH_CHECK(ctx);
-                    FMK_HIP(ctx, hipMemcpyAsync(&ctx->h_mail[1], d_changed, 8, hipMemcpyDeviceToHost, ctx->stream));
-                    FMK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-                    n_list = ctx->h_mail[1];
+                    FMK_TRY(fmk_read_back(ctx, &n_list, d_changed, 8));
                 }
                 break;
             }
@@ -766,9 +754,7 @@ extern "C" int fmk_cusum_bar_indexer_dev(fmk_ctx *ctx, const int64_t *d_ts, cons
         if (redo) { FMK_TRY(full_fill()); continue; }
         // counts -> offsets (+1 for the opening entry), total
         FMK_TRY(fmk_exclusive_scan_i64(ctx, counts, counts, chunks, true));
-        FMK_HIP(ctx, hipMemcpyAsync(&ctx->h_mail[2], counts + chunks, 8, hipMemcpyDeviceToHost, ctx->stream));
-        FMK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        total = ctx->h_mail[2];
+        FMK_TRY(fmk_read_back(ctx, &total, counts + chunks, 8));
         if (d_out) {
             if (capacity < total + 1)
                 return fmk_set_error(ctx, FMK_E_CAPACITY, "cusum: %lld close indices, capacity %lld", (long long)(total + 1),

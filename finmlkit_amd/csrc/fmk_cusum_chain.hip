@@ -791,10 +791,9 @@ int fmk_cusum_chain_tier(fmk_ctx *ctx, const int64_t *d_ts, const double *d_pric
     CcHost hh;
     memset(&hh, 0, sizeof(hh));
     auto fetch = [&]() -> int {
-        FMK_HIP(ctx, hipMemcpyAsync(&hh.st[0], st, 2 * sizeof(CcState), hipMemcpyDeviceToHost, ctx->stream));
-        FMK_HIP(ctx, hipMemcpyAsync(&hh.st[2], st + JOINT, sizeof(CcState), hipMemcpyDeviceToHost, ctx->stream));
-        FMK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        return FMK_OK;
+        hipError_t e = hipMemcpyAsync(&hh.st[0], st, 2 * sizeof(CcState), hipMemcpyDeviceToHost, ctx->stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(&hh.st[2], st + JOINT, sizeof(CcState), hipMemcpyDeviceToHost, ctx->stream);
+        return fmk_wait(ctx, e);
     };
     auto walk = [&](int joint, int64_t hi, int64_t budget) -> int {
         k_cc_walk<<<joint ? 1 : 2, 64 * CC_WALK_WAVES, 0, ctx->stream>>>(d_ts, d_price, d_sigma, n, first, m, hi, chunks, sigma_floor,
@@ -819,9 +818,9 @@ int fmk_cusum_chain_tier(fmk_ctx *ctx, const int64_t *d_ts, const double *d_pric
                                                                             margin_scale, lists, d_out, d_out ? capacity : 0);
         FMK_LAUNCH_CHECK(ctx);
         hseg.resize((size_t)(2 * K));
-        FMK_HIP(ctx, hipMemcpyAsync(hseg.data(), st, sizeof(CcState) * 2 * K, hipMemcpyDeviceToHost, ctx->stream));
-        FMK_HIP(ctx, hipMemcpyAsync(&active, d_active, 8, hipMemcpyDeviceToHost, ctx->stream));
-        FMK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        hipError_t e = hipMemcpyAsync(hseg.data(), st, sizeof(CcState) * 2 * K, hipMemcpyDeviceToHost, ctx->stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(&active, d_active, 8, hipMemcpyDeviceToHost, ctx->stream);
+        FMK_TRY(fmk_wait(ctx, e));
         // fold the segments into the two sides' records: counts add up, the worst status and the largest visit count stand
         for (int side = 0; side < 2; ++side) {
             CcState &h = hh.st[side];
@@ -860,8 +859,7 @@ int fmk_cusum_chain_tier(fmk_ctx *ctx, const int64_t *d_ts, const double *d_pric
         FMK_HIP(ctx, hipMemsetAsync(d_starts, 0, 8, ctx->stream));
         k_cc_rate<<<(unsigned)fmk_ceil_div(4 * lead, 256), 256, 0, ctx->stream>>>(subs, 4 * chunks, 4 * lead, (unsigned long long *)d_starts);
         FMK_LAUNCH_CHECK(ctx);
-        FMK_HIP(ctx, hipMemcpyAsync(&cnt, d_starts, 8, hipMemcpyDeviceToHost, ctx->stream));
-        FMK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        FMK_TRY(fmk_read_back(ctx, &cnt, d_starts, 8));
         g_cc_rate = (double)cnt / (2.0 * (double)lead);
         if (g_cc_rate > max_certain) { g_cc_last[2] = CC_ST_BUDGET; return FMK_OK; }     // thresholds reached often: the fixed point
     }
@@ -888,8 +886,7 @@ int fmk_cusum_chain_tier(fmk_ctx *ctx, const int64_t *d_ts, const double *d_pric
             k_cc_merge<<<(unsigned)fmk_ceil_div(np + nn, 256), 256, 0, ctx->stream>>>(lists, np, lists + list_cap, nn, d_out,
                                                                                     d_out ? capacity : 0, d_coincide);
             FMK_LAUNCH_CHECK(ctx);
-            FMK_HIP(ctx, hipMemcpyAsync(&hh.coincide, d_coincide, 8, hipMemcpyDeviceToHost, ctx->stream));
-            FMK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+            FMK_TRY(fmk_read_back(ctx, &hh.coincide, d_coincide, 8));
             if (hh.coincide) {                                        // a positive and a negative close on one tick: `elif`
                 FMK_TRY(walk(1, chunks, budget));
                 h = hh.st[2];

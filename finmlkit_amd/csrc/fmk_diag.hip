@@ -74,7 +74,7 @@ extern "C" int fmk_diag_read_bandwidth(fmk_ctx *ctx, const void *d_buf, size_t b
     FMK_HIP(ctx, hipSetDevice(ctx->device));
     const int64_t n16 = (int64_t)(bytes / 16);
     const unsigned blocks = (unsigned)(ctx->n_cu * (blocks_per_cu > 0 ? blocks_per_cu : 8));
-    unsigned long long *sink = (unsigned long long *)(ctx->d_mail + 60);
+    unsigned long long *sink = &ctx->d_mail->diag.sink;
     FMK_HIP(ctx, hipEventRecord(ctx->ev0, ctx->stream));
     if (variant == 0) k_diag_read<0><<<blocks, 256, 0, ctx->stream>>>((const uint4 *)d_buf, n16, sink);
     else if (variant == 1) k_diag_read<1><<<blocks, 256, 0, ctx->stream>>>((const uint4 *)d_buf, n16, sink);
@@ -152,7 +152,7 @@ extern "C" int fmk_diag_read_two_streams(fmk_ctx *ctx, const void *d_a8, const v
     if (n <= 0 || seg <= 0 || pattern < 0 || pattern > 3) return fmk_set_error(ctx, FMK_E_ARG, "diag: bad arguments");
     FMK_HIP(ctx, hipSetDevice(ctx->device));
     const unsigned blocks = (unsigned)(ctx->n_cu * (blocks_per_cu > 0 ? blocks_per_cu : 8));
-    unsigned long long *sink = (unsigned long long *)(ctx->d_mail + 60);
+    unsigned long long *sink = &ctx->d_mail->diag.sink;
     FMK_HIP(ctx, hipEventRecord(ctx->ev0, ctx->stream));
     if (pattern == 0) k_diag_read2<0><<<blocks, 256, 0, ctx->stream>>>((const uint2 *)d_a8, (const unsigned *)d_b4, n, seg, sink);
     else if (pattern == 1) k_diag_read2<1><<<blocks, 256, 0, ctx->stream>>>((const uint2 *)d_a8, (const unsigned *)d_b4, n, seg, sink);
@@ -195,16 +195,16 @@ extern "C" int fmk_diag_hop_latency(fmk_ctx *ctx, const void *d_buf, int64_t n, 
 {
     if (n <= 0 || stride <= 0 || loads < 1 || loads > 16 || hops < 1) return fmk_set_error(ctx, FMK_E_ARG, "diag: bad arguments");
     FMK_HIP(ctx, hipSetDevice(ctx->device));
-    long long *d_out = (long long *)(ctx->d_mail + 56);
+    long long *d_out = ctx->d_mail->diag.hops;
     FMK_HIP(ctx, hipEventRecord(ctx->ev0, ctx->stream));
     k_diag_hops<<<1, 64, 0, ctx->stream>>>((const double *)d_buf, n, stride, loads, hops, d_out);
     FMK_LAUNCH_CHECK(ctx);
     FMK_HIP(ctx, hipEventRecord(ctx->ev1, ctx->stream));
-    FMK_HIP(ctx, hipMemcpyAsync(&ctx->h_mail[8], d_out, 16, hipMemcpyDeviceToHost, ctx->stream));
-    FMK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    long long out[2];
+    FMK_TRY(fmk_read_back(ctx, out, d_out, sizeof out));
     float ms = 0.f;
     FMK_HIP(ctx, hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1));
-    *cycles_per_hop = (double)ctx->h_mail[8] / hops;
+    *cycles_per_hop = (double)out[0] / hops;
     *elapsed_ms = (double)ms;
     return FMK_OK;
 }
@@ -305,7 +305,7 @@ extern "C" int fmk_diag_read_owned(fmk_ctx *ctx, const double *d_price, const fl
     if (n <= 0 || seg < 16 || (r != 1 && r != 2 && r != 4 && r != 8)) return fmk_set_error(ctx, FMK_E_ARG, "diag: bad arguments");
     FMK_HIP(ctx, hipSetDevice(ctx->device));
     const unsigned blocks = (unsigned)(ctx->n_cu * (blocks_per_cu > 0 ? blocks_per_cu : 4));
-    unsigned long long *sink = (unsigned long long *)(ctx->d_mail + 60);
+    unsigned long long *sink = &ctx->d_mail->diag.sink;
     FMK_HIP(ctx, hipEventRecord(ctx->ev0, ctx->stream));
     if (r == 1) k_diag_read_owned<1><<<blocks, 256, 0, ctx->stream>>>(d_price, d_amount, d_side, n, seg, sink);
     else if (r == 2) k_diag_read_owned<2><<<blocks, 256, 0, ctx->stream>>>(d_price, d_amount, d_side, n, seg, sink);

@@ -529,32 +529,29 @@ static int dl_run(fmk_ctx *ctx, const double *p, const void *a, int64_t n, doubl
     int64_t *tmin = (int64_t *)(segb + gdd);
     int64_t *segm = tmin + tiles;
     double *wpart = (double *)(segm + gmn + 1);                        // per-tile sums of the increments >= thr
-    int64_t *d_res = ctx->d_mail + 24;
-    int *d_bad = (int *)(ctx->d_mail + 26);
-    unsigned long long *d_dmax = (unsigned long long *)(ctx->d_mail + 27);
-    double *d_whale = (double *)(ctx->d_mail + 28);
-    FMK_HIP(ctx, hipMemsetAsync(d_bad, 0, 24, ctx->stream));
-    k_dl_tile_sums<AF64><<<(unsigned)tiles, DL_THREADS, 0, ctx->stream>>>(p, a, n, tsum, d_bad, d_dmax, thr, wpart);
-    k_dl_whale_total<<<(unsigned)(tiles < 512 * 256 ? fmk_ceil_div(tiles, 256) : 512), 256, 0, ctx->stream>>>(wpart, tiles, thr, d_whale);
+    int64_t *d_res = &ctx->d_mail->dl.emit.res;
+    fmk_mail::Dl::Pass1 *d_p1 = &ctx->d_mail->dl.p1, p1;
+    FMK_HIP(ctx, hipMemsetAsync(d_p1, 0, offsetof(fmk_mail::Dl::Pass1, total), ctx->stream));
+    k_dl_tile_sums<AF64><<<(unsigned)tiles, DL_THREADS, 0, ctx->stream>>>(p, a, n, tsum, &d_p1->bad, &d_p1->dmax, thr, wpart);
+    k_dl_whale_total<<<(unsigned)(tiles < 512 * 256 ? fmk_ceil_div(tiles, 256) : 512), 256, 0, ctx->stream>>>(wpart, tiles, thr,
+                                                                                                                &d_p1->whale);
     FMK_LAUNCH_CHECK(ctx);
     k_dl_scan_dd<<<(unsigned)gdd, DL_THREADS, 0, ctx->stream>>>(tsum, tiles, (int64_t)1 << DL_SEG_SHIFT, segb);
-    DD *d_total = (DD *)(ctx->d_mail + 44);                            // sum of all increments (double-double)
+    static_assert(sizeof(DD) == sizeof d_p1->total, "a double-double");
+    DD *d_total = (DD *)d_p1->total;                                   // sum of all increments (double-double)
     k_dl_scan_dd<<<1, DL_THREADS, 0, ctx->stream>>>(segb, gdd, gdd, d_total);
     FMK_LAUNCH_CHECK(ctx);
     // what pass 1 learned: negative / NaN increments (-> serial walk), the largest increment, the total
-    FMK_HIP(ctx, hipMemcpyAsync(ctx->h_mail + 1, d_bad, 24, hipMemcpyDeviceToHost, ctx->stream));
-    FMK_HIP(ctx, hipMemcpyAsync(ctx->h_mail + 4, d_total, 16, hipMemcpyDeviceToHost, ctx->stream));
-    FMK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    if ((int)ctx->h_mail[1] != 0) return 1;
-    memcpy(&c.dmax, &ctx->h_mail[2], 8);
+    FMK_TRY(fmk_read_back(ctx, &p1, d_p1, sizeof p1));
+    if (p1.bad != 0) return 1;
+    memcpy(&c.dmax, &p1.dmax, 8);
     // The drift bound of a decision.  Without whales every add of the reference happens below 2 thr: <= (i + 1) * 2^-52 * thr after i
     // ticks.  An increment w >= thr leaves a backlog -- cum falls from ~w to below thr by one threshold per tick -- and the adds of
     // those ~w / thr ticks round at the magnitude of cum: their errors sum to <= 2^-53 * w^2 / (2 thr) ... for ALL whales together
     // (a second one may arrive before the first is worked off) <= 2^-53 * W^2 / thr, W their sum.  In units of 2.3e-16 * thr that is
     // `extra` = (W / thr)^2 more "ticks".  (Found by tools/fuzz_volume.py seed 81003, dollar cases 792 / 1143, late in round 3: with
     // the tick count alone two closes right after a whale were certified and wrong by one tick.)
-    double whale_thr = 0.0;                                           // W / thr (k_dl_whale_total)
-    memcpy(&whale_thr, &ctx->h_mail[3], 8);
+    const double whale_thr = p1.whale;                                // W / thr (k_dl_whale_total)
     const double extra = whale_thr * whale_thr;
     c.extra = extra;
     const int simple = c.dmax < thr ? 1 : 0;
@@ -564,16 +561,14 @@ static int dl_run(fmk_ctx *ctx, const double *p, const void *a, int64_t n, doubl
         k_dl_scan_min<<<(unsigned)gmn, 1024, 0, ctx->stream>>>(tmin, tiles, (int64_t)1 << DL_SEGM_SHIFT, segm, nullptr);
         k_dl_scan_min<<<1, 1024, 0, ctx->stream>>>(segm, gmn, gmn, nullptr, d_res);
         FMK_LAUNCH_CHECK(ctx);
-        FMK_HIP(ctx, hipMemcpyAsync(ctx->h_mail, d_res, 8, hipMemcpyDeviceToHost, ctx->stream));
-        FMK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        const int64_t gmin = ctx->h_mail[0] < 0 ? ctx->h_mail[0] : 0; // G_0 = 0 is part of every prefix
+        int64_t res;
+        FMK_TRY(fmk_read_back(ctx, &res, d_res, 8));
+        const int64_t gmin = res < 0 ? res : 0;                       // G_0 = 0 is part of every prefix
         c.count = (n - 1) + gmin + 1;                                   // K_{n-1} closes + the leading 0
     } else {
         // two passes: the number of closes is M_{n-1} = floor(D_{n-1} / thr), from the double-double total (same arithmetic as
         // dd_floor_div on the device; the emit pass reports the value it used and the two are compared)
-        double hi, lo;
-        memcpy(&hi, &ctx->h_mail[4], 8);
-        memcpy(&lo, &ctx->h_mail[5], 8);
+        const double hi = p1.total[0], lo = p1.total[1];
         double q = floor(hi / thr);
         const double pq = q * thr, eq = fma(q, thr, -pq);
         double r = (hi - pq) + (lo - eq);
@@ -591,8 +586,7 @@ static int dl_run(fmk_ctx *ctx, const double *p, const void *a, int64_t n, doubl
         FMK_HIP(ctx, hipMalloc((void **)&c.dbuf, (size_t)c.cap * 8));
         FMK_HIP(ctx, hipMalloc((void **)&c.carry, (size_t)c.cap * 8));
     }
-    unsigned long long *d_frag = (unsigned long long *)(ctx->d_mail + 25);
-    unsigned long long *d_area = (unsigned long long *)(ctx->d_mail + 46);     // [d_frag + 1 would be d_bad: keep the area apart]
+    unsigned long long *d_frag = &ctx->d_mail->dl.emit.frag, *d_area = &ctx->d_mail->dl.emit.area;
     FMK_HIP(ctx, hipMemsetAsync(d_frag, 0, 8, ctx->stream));
     FMK_HIP(ctx, hipMemsetAsync(d_area, 0, 8, ctx->stream));
     int ex;
@@ -602,16 +596,14 @@ static int dl_run(fmk_ctx *ctx, const double *p, const void *a, int64_t n, doubl
                                                                      simple ? c.cap : c.count, d_frag, c.carry,
                                                                      ldexp(1.0, 53 - ex), simple, d_res, extra, d_area);
     FMK_LAUNCH_CHECK(ctx);
-    FMK_HIP(ctx, hipMemcpyAsync(ctx->h_mail, d_frag, 8, hipMemcpyDeviceToHost, ctx->stream));
-    FMK_HIP(ctx, hipMemcpyAsync(ctx->h_mail + 1, d_res, 8, hipMemcpyDeviceToHost, ctx->stream));
-    FMK_HIP(ctx, hipMemcpyAsync(ctx->h_mail + 2, d_area, 8, hipMemcpyDeviceToHost, ctx->stream));
-    FMK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    c.unc = ctx->h_mail[0];
-    c.area = (double)ctx->h_mail[2];
-    if (simple && ctx->h_mail[1] + 1 != c.count) {
+    fmk_mail::Dl::Emit em;
+    FMK_TRY(fmk_read_back(ctx, &em, &ctx->d_mail->dl.emit, sizeof em));
+    c.unc = (int64_t)em.frag;
+    c.area = (double)(int64_t)em.area;
+    if (simple && em.res + 1 != c.count) {
         // the device's D_{n-1} (segment base + tile base + in-tile prefix) and the host's total are the same sum in two
         // association orders: they can only disagree about floor(D / thr) when D is within ~2^-100 of a multiple of thr
-        const int64_t dev = ctx->h_mail[1] + 1;
+        const int64_t dev = em.res + 1;
         if (dev < 1 || dev > c.cap)
             return fmk_set_error(ctx, FMK_E_HIP, "dollar indexer: %lld closes on the device, %lld from the total",
                                  (long long)(dev - 1), (long long)(c.count - 1));
@@ -648,10 +640,8 @@ static int dl1_run(fmk_ctx *ctx, const double *p, const void *a, int64_t n, doub
     void *scr;
     FMK_TRY(fmk_scratch(ctx, desc_bytes + (size_t)tiles * 32 + 64, &scr));            // (+ the time stamps of a -DDL1_TIMING build)
     unsigned long long *desc = (unsigned long long *)scr;
-    int64_t *d_last = ctx->d_mail + 24;
-    unsigned long long *d_frag = (unsigned long long *)(ctx->d_mail + 25);
-    int *d_flags = (int *)(ctx->d_mail + 26);
-    double *d_sum = (double *)(ctx->d_mail + 27);
+    fmk_mail::Dl::One *d_one = &ctx->d_mail->dl.one, one;
+    double *d_sum = &ctx->d_mail->dl.sample_sum;
     if (!c.dbuf || c.cap <= 0) {
         // no close buffers yet: their capacity from a strided sample of the products (x 1.3 + slack).  Only a guess -- the pass
         // itself reports the true count, and a guess that was too small costs one more pass with the exact capacity.
@@ -659,10 +649,8 @@ static int dl1_run(fmk_ctx *ctx, const double *p, const void *a, int64_t n, doub
         FMK_HIP(ctx, hipMemsetAsync(d_sum, 0, 8, ctx->stream));
         k_dl1_sample<AF64><<<(unsigned)fmk_ceil_div(m, 256), 256, 0, ctx->stream>>>(p, a, n, stride, m, d_sum);
         FMK_LAUNCH_CHECK(ctx);
-        FMK_HIP(ctx, hipMemcpyAsync(ctx->h_mail, d_sum, 8, hipMemcpyDeviceToHost, ctx->stream));
-        FMK_HIP(ctx, hipStreamSynchronize(ctx->stream));
         double ssum;
-        memcpy(&ssum, &ctx->h_mail[0], 8);
+        FMK_TRY(fmk_read_back(ctx, &ssum, d_sum, 8));
         double est = ssum / (double)m * (double)n / thr;
         if (!(est >= 0.0) || est > (double)n) est = (double)n;
         c.cap = (int64_t)(est * 1.3) + 65536 + DL_EXTRA;
@@ -676,12 +664,12 @@ static int dl1_run(fmk_ctx *ctx, const double *p, const void *a, int64_t n, doub
         FMK_HIP(ctx, hipMemsetAsync(desc, 0, desc_bytes, ctx->stream));
         unsigned long long *d_ticket = (unsigned long long *)((char *)desc + desc_bytes + (size_t)tiles * 32);
         FMK_HIP(ctx, hipMemsetAsync(d_ticket, 0, 8, ctx->stream));
-        FMK_HIP(ctx, hipMemsetAsync(d_last, 0, 24, ctx->stream));
+        FMK_HIP(ctx, hipMemsetAsync(d_one, 0, sizeof *d_one, ctx->stream));
         unsigned long long *dB = desc + 2 * tiles;
-        k_dl1<AF64, 16, 512><<<(unsigned)tiles, 512, 0, ctx->stream>>>(p, a, n, P, desc, dB, c.dbuf, c.carry, c.cap, d_last, d_frag, d_flags, d_ticket);
+        k_dl1<AF64, 16, 512><<<(unsigned)tiles, 512, 0, ctx->stream>>>(p, a, n, P, desc, dB, c.dbuf, c.carry, c.cap, &d_one->last,
+                                                                       &d_one->frag, &d_one->flags, d_ticket);
         FMK_LAUNCH_CHECK(ctx);
-        FMK_HIP(ctx, hipMemcpyAsync(ctx->h_mail, d_last, 24, hipMemcpyDeviceToHost, ctx->stream));
-        FMK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        FMK_TRY(fmk_read_back(ctx, &one, d_one, sizeof one));
 #ifdef DL1_TIMING
         {
             unsigned long long *tt = (unsigned long long *)malloc((size_t)tiles * 32);
@@ -701,11 +689,11 @@ static int dl1_run(fmk_ctx *ctx, const double *p, const void *a, int64_t n, doub
             free(tt);
         }
 #endif
-        if ((int)(ctx->h_mail[2] & 0xFFFFFFFF) != 0) return 1;
-        const int64_t count = ctx->h_mail[0] + 1;                    // M_{n-1} closes + the leading 0
+        if (one.flags != 0) return 1;
+        const int64_t count = one.last + 1;                          // M_{n-1} closes + the leading 0
         if (count + DL_EXTRA <= c.cap) {
             c.count = count;
-            c.unc = ctx->h_mail[1];
+            c.unc = (int64_t)one.frag;
             c.dmax = nextafter(thr, 0.0);                             // all the callers ask is whether an increment reached thr
             c.extra = 0.0;
             c.area = 0.0;

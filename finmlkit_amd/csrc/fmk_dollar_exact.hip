@@ -739,7 +739,7 @@ int fmk_dollar_exact(fmk_ctx *ctx, const double *d_price, const void *d_amount, 
     const int64_t tu = llrint(thr * inv_u);          // thr in units of u: an integer in [2^52, 2^53)
     const double top = ldexp(1.0, ex + 1);           // thr in [2^(ex-1), 2^ex): closing sums from here on are whale closes
     int rc = FMK_OK;
-    unsigned long long *cnt;
+    unsigned long long *cnt, h[3];
     int64_t n_flag = 0;
     int rounds = 0;
     int bpl = (int)(nbar / ((int64_t)128 * 8192));
@@ -774,10 +774,9 @@ int fmk_dollar_exact(fmk_ctx *ctx, const double *d_price, const void *d_amount, 
                                                        (DlxFn *)p_fn, (int32_t *)p_fidx, (int32_t *)p_owner, (int64_t *)p_flist, cnt, bpl,
                                                        whales, extra_ticks, tu, top, (unsigned char *)p_btype, (double *)p_dlast);
     DLX_HIP(hipGetLastError());
-    DLX_HIP(hipMemcpyAsync(ctx->h_mail, cnt, 24, hipMemcpyDeviceToHost, ctx->stream));
-    DLX_HIP(hipStreamSynchronize(ctx->stream));
-    n_flag = ctx->h_mail[0];
-    if (ctx->h_mail[2] != 0) goto done;              // a backlog beyond 500 thresholds (or a bar the closed form and the states disagree about)
+    DLX_TRY(fmk_read_back(ctx, h, cnt, 24));
+    n_flag = (int64_t)h[0];
+    if (h[2] != 0) goto done;                     // a backlog beyond 500 thresholds (or a bar the closed form and the states disagree about)
     if (n_flag == 0) { *status = 0; goto done; }     // no bar needs a replay: every decision of the closed form is certain
     DLX_TRY(fmk_alloc(ctx, (size_t)n_flag * sizeof(DlxRes), &p_res));
     DLX_HIP(hipMemsetAsync(p_res, 0, (size_t)n_flag * sizeof(DlxRes), ctx->stream));
@@ -816,19 +815,16 @@ int fmk_dollar_exact(fmk_ctx *ctx, const double *d_price, const void *d_amount, 
                                                                  (int32_t *)p_owner, (DlxRes *)p_res, cnt + 1, cnt + 2,
                                                                  (const unsigned char *)p_btype, (const int64_t *)p_sval);
             DLX_HIP(hipGetLastError());
-            DLX_HIP(hipMemcpyAsync(ctx->h_mail, cnt + 1, 16, hipMemcpyDeviceToHost, ctx->stream));
-            DLX_HIP(hipStreamSynchronize(ctx->stream));
-            if (ctx->h_mail[1] != 0) goto done;      // a replay did not get back onto the closed form: serial walk
-            if (ctx->h_mail[0] == 0) break;          // a quiet round: every state is the reference's
+            DLX_TRY(fmk_read_back(ctx, h, cnt + 1, 16));
+            if (h[1] != 0) goto done;                // a replay did not get back onto the closed form: serial walk
+            if (h[0] == 0) break;                    // a quiet round: every state is the reference's
         }
         if (rounds >= 64) goto done;
         DLX_HIP(hipMemcpyAsync(cnt + 3, count, 8, hipMemcpyHostToDevice, ctx->stream));
         k_dlx_commit<<<gf, 64, 0, ctx->stream>>>((const int64_t *)p_flist, n_flag, (const int32_t *)p_owner, (const DlxRes *)p_res,
                                                  d_close_idx, *count + 16, (int64_t *)(cnt + 3));
         DLX_HIP(hipGetLastError());
-        DLX_HIP(hipMemcpyAsync(ctx->h_mail, cnt + 3, 8, hipMemcpyDeviceToHost, ctx->stream));
-        DLX_HIP(hipStreamSynchronize(ctx->stream));
-        *count = ctx->h_mail[0];
+        DLX_TRY(fmk_read_back(ctx, count, cnt + 3, 8));
         *status = 0;
     }
 done:

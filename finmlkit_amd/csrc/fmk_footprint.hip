@@ -100,17 +100,18 @@ extern "C" int fmk_comp_bar_footprints_size_dev(fmk_ctx *ctx, const double *d_ba
     if (n_bars < 0) return fmk_set_error(ctx, FMK_E_ARG, "negative dimensions are not allowed");
     if (!(price_tick_size > 0)) return fmk_set_error(ctx, FMK_E_ARG, "price_tick_size must be > 0");
     FMK_HIP(ctx, hipSetDevice(ctx->device));
-    unsigned long long *d_max = (unsigned long long *)ctx->d_mail;
+    unsigned long long *d_max = &ctx->d_mail->fp.max_levels;
     FMK_HIP(ctx, hipMemsetAsync(d_max, 0, 8, ctx->stream));
     k_fp_level_counts<<<(unsigned)fmk_ceil_div(n_bars, 256), 256, 0, ctx->stream>>>(
         d_bar_lows, d_bar_highs, n_bars, price_tick_size, d_level_offsets, d_max);
     FMK_LAUNCH_CHECK(ctx);
     FMK_TRY(fmk_exclusive_scan_i64(ctx, d_level_offsets, d_level_offsets, n_bars, true));
-    FMK_HIP(ctx, hipMemcpyAsync(&ctx->h_mail[0], d_level_offsets + n_bars, 8, hipMemcpyDeviceToHost, ctx->stream));
-    FMK_HIP(ctx, hipMemcpyAsync(&ctx->h_mail[1], d_max, 8, hipMemcpyDeviceToHost, ctx->stream));
-    FMK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    *total_levels = ctx->h_mail[0];
-    *max_levels = ctx->h_mail[1];
+    auto &h = ctx->h_mail->fp.sizes;
+    hipError_t e = hipMemcpyAsync(&h.total, d_level_offsets + n_bars, 8, hipMemcpyDeviceToHost, ctx->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(&h.max, d_max, 8, hipMemcpyDeviceToHost, ctx->stream);
+    FMK_TRY(fmk_wait(ctx, e));
+    *total_levels = h.total;
+    *max_levels = (int64_t)h.max;
     return FMK_OK;
 }
 
@@ -436,12 +437,11 @@ static int fp_lds_atomics_in_lane_order(fmk_ctx *ctx)
 {
     static int known = -1;
     if (known >= 0) return known;
-    int *d = (int *)(ctx->d_mail + 30);
+    int *d = &ctx->d_mail->fp.lds_probe;
     if (hipMemsetAsync(d, 0, 4, ctx->stream) != hipSuccess) return 0;
     k_fp_lds_order_probe<<<64, 64, 0, ctx->stream>>>(d);
     int bad = 1;
-    if (hipMemcpyAsync(&bad, d, 4, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess) return 0;
-    if (hipStreamSynchronize(ctx->stream) != hipSuccess) return 0;
+    if (fmk_read_back(ctx, &bad, d, 4) != FMK_OK) return 0;
     known = bad == 0 ? 1 : 0;
     return known;
 }
@@ -1567,7 +1567,7 @@ int fmk_footprints_fill_classes(fmk_ctx *ctx, const double *d_price, const void 
         }
     }
     int lmin = 0, rc = FMK_OK;
-    int *saw_long = (int *)(ctx->d_mail + 16);
+    int *saw_long = ctx->d_mail->fp_median;
     if (d_median && amount_is_f64) {      // float64 amounts: the in-sweep median is a float32 schedule
         if (rest) (void)fmk_free(ctx, rest);
         return fmk_set_error(ctx, FMK_E_ARG, "footprints with the median trade size: float32 amounts only");
@@ -1717,10 +1717,9 @@ extern "C" int fmk_comp_bar_footprints_fill_median_dev(fmk_ctx *ctx, const doubl
 // diagnostics: how many bars of the last fmk_comp_bar_footprints_fill_median_dev call took the generic selection (bracket miss)
 extern "C" int fmk_diag_fp_median_fallbacks(fmk_ctx *ctx, int64_t *count)
 {
-    int v[2] = {0, 0};
+    int v = 0;
     FMK_HIP(ctx, hipSetDevice(ctx->device));
-    FMK_HIP(ctx, hipMemcpyAsync(v, ctx->d_mail + 16, sizeof v, hipMemcpyDeviceToHost, ctx->stream));
-    FMK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    *count = v[1];
+    FMK_TRY(fmk_read_back(ctx, &v, &ctx->d_mail->fp_median[1], sizeof v));
+    *count = v;
     return FMK_OK;
 }

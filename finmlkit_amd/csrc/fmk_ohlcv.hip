@@ -338,11 +338,10 @@ static int oh_wide_launch(fmk_ctx *ctx, const double *p, const void *a, const in
             // here; in enqueue-only mode nothing may be waited for, so the scratch covers the whole tick axis (1.25 B/tick).
             int64_t base = 0, span = n;
             if (!ctx->enqueue_only) {
-                int64_t *d_span = ctx->d_mail + 48, *h_span = ctx->h_mail + 20;
+                int64_t *d_span = ctx->d_mail->ohlcv.span, h_span[3];
                 k_list_span<<<1, 256, 0, ctx->stream>>>(ci, list, d_span);
                 FMK_LAUNCH_CHECK(ctx);
-                FMK_HIP(ctx, hipMemcpyAsync(h_span, d_span, 24, hipMemcpyDeviceToHost, ctx->stream));
-                FMK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+                FMK_TRY(fmk_read_back(ctx, h_span, d_span, sizeof h_span));
                 if (h_span[0] == 0) {                               // no bar for the workgroup kernels
                     FMK_TRY(fmk_free(ctx, list));
                     *median_done = 1;
@@ -683,7 +682,7 @@ __global__ __launch_bounds__(256) void k_bar_median_small(const float *__restric
 int fmk_median_small_launch(fmk_ctx *ctx, const float *d_amount, const int64_t *d_close_idx, int64_t nb, double *d_median,
                             int64_t n_ticks)
 {
-    int *saw_long = (int *)(ctx->d_mail + 16);
+    int *saw_long = &ctx->d_mail->ohlcv.saw_long;
     FMK_HIP(ctx, hipMemsetAsync(saw_long, 0, sizeof(int), ctx->stream));
     int64_t blocks = fmk_ceil_div(nb, 4);
     const int64_t cap = (int64_t)ctx->n_cu * 64;
@@ -1621,7 +1620,7 @@ static int ohlcv_launch(fmk_ctx *ctx, const double *p, const void *a, const int6
             // running: the call decides about the leftover passes and returns without ever waiting for a kernel it launched.
             FMK_TRY(fmk_ctx_aux(ctx));
             const int idx_bpc = 2;         // workgroups per CU of the second index stage (0: no cap)
-            int *saw_long = (int *)(ctx->d_mail + 16);
+            int *saw_long = &ctx->d_mail->ohlcv.saw_long;
             const int64_t *coarse = nullptr;
             int64_t m = 0;
             const int64_t ne = nb + 1, long_min = 64 * FMK_SMALL_NCH;
@@ -1635,7 +1634,7 @@ static int ohlcv_launch(fmk_ctx *ctx, const double *p, const void *a, const int6
             FMK_HIP(ctx, hipEventRecord(ctx->aev[1], ctx->aux));
             // (also in enqueue-only mode: this wait ends when the index stages do, ~0.1 ms into a 2 ms launch -- the device never idles
             //  for it, and it saves the ~36 empty launches of the leftover passes, 0.25 ms per step of the sharded path)
-            int *h_saw = (int *)(ctx->h_mail + 50);
+            int *h_saw = &ctx->h_mail->ohlcv.saw_long;
             FMK_HIP(ctx, hipMemcpyAsync(h_saw, saw_long, sizeof(int), hipMemcpyDeviceToHost, ctx->aux));
             FMK_HIP(ctx, hipEventRecord(ctx->aev[2], ctx->aux));
             for (int stage = 0; stage < 2; ++stage) {
@@ -1662,7 +1661,7 @@ static int ohlcv_launch(fmk_ctx *ctx, const double *p, const void *a, const int6
     // small bars: all loads up front (+ fused median); long bars: generic kernels on the rest
     // launch bounds measured on MI355X: forcing >4 waves/SIMD on the fused-median kernel makes the compiler
     // serialise the up-front loads (2.7 ms -> 3.5..4.3 ms at N = 1e9); 4 waves/SIMD (102 VGPRs) is the optimum.
-    int *saw_long = (int *)(ctx->d_mail + 16);               // set by the small kernel iff a long bar exists
+    int *saw_long = &ctx->d_mail->ohlcv.saw_long;            // set by the small kernel iff a long bar exists
     FMK_HIP(ctx, hipMemsetAsync(saw_long, 0, sizeof(int), ctx->stream));
     // mean bar length (the tick array's length over the bars is an upper bound) picks the schedule: several whole bars per
     // LANE below FMK_PACKED_MAX_MEAN ticks per bar (k_bar_ohlcv_lanes), one bar per wave above
@@ -1739,10 +1738,9 @@ static int ohlcv_launch(fmk_ctx *ctx, const double *p, const void *a, const int6
         if (n <= long_min) return FMK_OK;                          // no bar is longer than the tick array (the sharded step's boundary bar)
         const int census_sync = 1;
         if (census_sync && !ctx->enqueue_only) {
-            int *h_saw = (int *)(ctx->h_mail + 12);
-            FMK_HIP(ctx, hipMemcpyAsync(h_saw, saw_long, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
-            FMK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-            if (*h_saw == 0) return FMK_OK;
+            int saw = 0;
+            FMK_TRY(fmk_read_back(ctx, &saw, saw_long, sizeof saw));
+            if (saw == 0) return FMK_OK;
         }
     }
     return ohlcv_leftovers<AF64>(ctx, p, a, ci, nb, n, o, saw_long, long_min, grid);
@@ -1775,7 +1773,7 @@ int fmk_median_small_ohlcv_long_launch(fmk_ctx *ctx, const double *p, const floa
                                        double *d_open, double *d_high, double *d_low, double *d_close, float *d_volume,
                                        double *d_vwap, int64_t *d_trades, double *d_median)
 {
-    int *saw_long = (int *)(ctx->d_mail + 16);
+    int *saw_long = &ctx->d_mail->ohlcv.saw_long;
     FMK_HIP(ctx, hipMemsetAsync(saw_long, 0, sizeof(int), ctx->stream));
     int64_t blocks = fmk_ceil_div(nb, 4);
     const int64_t cap = (int64_t)ctx->n_cu * 64;

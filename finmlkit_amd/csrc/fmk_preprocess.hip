@@ -129,9 +129,8 @@ extern "C" int fmk_merge_split_trades_dev(fmk_ctx *ctx, const int64_t *d_ts, con
     FMK_LAUNCH_CHECK(ctx);
     k_scan_tile_scan<<<1, 1024, 0, ctx->stream>>>(tile_off, tiles, tile_off + tiles);
     FMK_LAUNCH_CHECK(ctx);
-    FMK_HIP(ctx, hipMemcpyAsync(&ctx->h_mail[0], tile_off + tiles, 8, hipMemcpyDeviceToHost, ctx->stream));
-    FMK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    const int64_t m = ctx->h_mail[0];
+    int64_t m;
+    FMK_TRY(fmk_read_back(ctx, &m, tile_off + tiles, 8));
     if (n_merged) *n_merged = m;
     if (!d_out_ts) return FMK_OK;                                 // phase 1: count only
     if (capacity < m)

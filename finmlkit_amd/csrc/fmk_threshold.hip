@@ -267,7 +267,7 @@ static int th_run(fmk_ctx *ctx, const double *d_price, const void *d_amount, int
                      c.kind == (int)DOLLAR && c.is_f64 == is_f64 && c.dbuf && c.exact == exact;
     if (!(hit && d_close_idx)) {
         // bound the number of closes
-        double *d_acc = (double *)ctx->d_mail;
+        double *d_acc = &ctx->d_mail->th.total;
         FMK_HIP(ctx, hipMemsetAsync(d_acc, 0, 8, ctx->stream));
         const unsigned blocks = (unsigned)(fmk_ceil_div(n, 256 * 16) < ctx->n_cu * 16 ? fmk_ceil_div(n, 256 * 16)
                                                                                       : ctx->n_cu * 16);
@@ -275,8 +275,7 @@ static int th_run(fmk_ctx *ctx, const double *d_price, const void *d_amount, int
         else k_threshold_total<false, DOLLAR><<<blocks, 256, 0, ctx->stream>>>(d_price, d_amount, n, d_acc);
         FMK_LAUNCH_CHECK(ctx);
         double total = 0.0;
-        FMK_HIP(ctx, hipMemcpyAsync(&total, d_acc, 8, hipMemcpyDeviceToHost, ctx->stream));
-        FMK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        FMK_TRY(fmk_read_back(ctx, &total, d_acc, 8));
         int64_t bound = n;
         if (thr > 0 && total / thr + 2.0 < (double)n) bound = (int64_t)(total / thr) + 2;
         if (bound < 1) bound = 1;
@@ -285,7 +284,7 @@ static int th_run(fmk_ctx *ctx, const double *d_price, const void *d_amount, int
             FMK_HIP(ctx, hipMalloc((void **)&c.dbuf, (size_t)bound * 8));
             c.cap = bound;
         }
-        int64_t *d_res = ctx->d_mail + 8;
+        int64_t *d_res = ctx->d_mail->th.res;
         if (exact) {
             if (is_f64)
                 k_threshold_exact<true, DOLLAR><<<1, 64, 0, ctx->stream>>>(d_price, d_amount, n, thr, c.dbuf, c.cap, d_res);
@@ -296,11 +295,11 @@ static int th_run(fmk_ctx *ctx, const double *d_price, const void *d_amount, int
         else
             k_threshold_index<false, DOLLAR><<<1, 64, 0, ctx->stream>>>(d_price, d_amount, n, thr, c.dbuf, c.cap, d_res);
         FMK_LAUNCH_CHECK(ctx);
-        FMK_HIP(ctx, hipMemcpyAsync(ctx->h_mail, d_res, 16, hipMemcpyDeviceToHost, ctx->stream));
-        FMK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        int64_t res[2];
+        FMK_TRY(fmk_read_back(ctx, res, d_res, sizeof res));
         c.ctx = ctx; c.amount = d_amount; c.price = d_price; c.n = n; c.thr = thr; c.kind = (int)DOLLAR;
         ctx->idx_key[2][0] = d_amount; ctx->idx_key[2][1] = d_price; ctx->idx_stale[2] = 0;
-        c.is_f64 = is_f64; c.count = ctx->h_mail[0]; c.unc = ctx->h_mail[1]; c.exact = exact;
+        c.is_f64 = is_f64; c.count = res[0]; c.unc = res[1]; c.exact = exact;
         if (c.count > c.cap) return fmk_set_error(ctx, FMK_E_CAPACITY, "threshold indexer: internal bound exceeded");
     }
     *n_idx = c.count;

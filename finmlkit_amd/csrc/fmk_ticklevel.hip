@@ -827,7 +827,7 @@ static int ew_run(fmk_ctx *ctx, const int64_t *d_ts, const double *d_y, int64_t 
         D.A = D.tagP + slots; D.R = D.A + 12 * otiles; D.P = D.R + 12 * slots;
         D.groups = groups;
         D.ticket = (unsigned long long *)((char *)scr + tag_bytes + rec_bytes);
-        k_ew_onepass_d<MODE, EW_THREADS, 4><<<(unsigned)otiles, EW_THREADS, 0, ctx->stream>>>(d_ts, d_y, n, hl, sigma_floor, d_state_in, d_out, D, ctx->h_mail + 40);
+        k_ew_onepass_d<MODE, EW_THREADS, 4><<<(unsigned)otiles, EW_THREADS, 0, ctx->stream>>>(d_ts, d_y, n, hl, sigma_floor, d_state_in, d_out, D, &ctx->h_mail->device_error);
         FMK_LAUNCH_CHECK(ctx);
         return FMK_OK;
     }

@@ -240,9 +240,9 @@ extern "C" int fmk_volume_profile_rolling_dev(fmk_ctx *ctx, const int64_t *d_bar
     FMK_HIP(ctx, hipMemsetAsync(d_lva, 0, (size_t)n_bars * 4, ctx->stream));
     FMK_HIP(ctx, hipMemsetAsync(d_pct, 0, (size_t)n_bars * 4, ctx->stream));
     if (first_bar >= n_bars) return FMK_OK;
-    unsigned long long *d_max = (unsigned long long *)ctx->d_mail;
-    unsigned int *d_status = (unsigned int *)(d_max + 1);
-    FMK_HIP(ctx, hipMemsetAsync(d_max, 0, 16, ctx->stream));
+    unsigned long long *d_max = &ctx->d_mail->vp.max;
+    unsigned int *d_status = &ctx->d_mail->vp.status;
+    FMK_HIP(ctx, hipMemsetAsync(&ctx->d_mail->vp, 0, sizeof ctx->d_mail->vp, ctx->stream));
     const int64_t work = n_bars - first_bar;
     void *win_v = nullptr;
     FMK_TRY(fmk_alloc(ctx, (size_t)work * 32, &win_v));
@@ -251,9 +251,8 @@ extern "C" int fmk_volume_profile_rolling_dev(fmk_ctx *ctx, const int64_t *d_bar
     k_vp_windows<<<(unsigned)fmk_ceil_div(work, 256), 256, 0, ctx->stream>>>(d_bar_ts, d_highs, d_lows, n_bars, first_bar,
                                                                             window_ns, price_tick, d_win, d_max);
     FMK_LAUNCH_CHECK(ctx);
-    FMK_HIP(ctx, hipMemcpyAsync(&ctx->h_mail[0], d_max, 8, hipMemcpyDeviceToHost, ctx->stream));
-    FMK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    const int64_t max_levels = ctx->h_mail[0];
+    int64_t max_levels;
+    FMK_TRY(fmk_read_back(ctx, &max_levels, d_max, 8));
     if (max_levels > VP_MAX_LEVELS_GLOBAL)
         return fmk_set_error(ctx, FMK_E_CAPACITY, "volume_profile_rolling: a window spans %lld price levels; this build "
                              "supports <= %d", (long long)max_levels, VP_MAX_LEVELS_GLOBAL);
@@ -288,9 +287,8 @@ extern "C" int fmk_volume_profile_rolling_dev(fmk_ctx *ctx, const int64_t *d_bar
             d_bar_ts, d_highs, d_lows, d_level_offsets, d_price_levels, d_buy_volumes, d_sell_volumes, n_bars, first_bar,
             window_ns, n_bins, price_tick, va_pct, cap, d_poc, d_hva, d_lva, d_pct, d_status, nullptr, d_win);
     FMK_LAUNCH_CHECK(ctx);
-    FMK_HIP(ctx, hipMemcpyAsync(&ctx->h_mail[1], d_status, 4, hipMemcpyDeviceToHost, ctx->stream));
-    FMK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    const unsigned st = (unsigned)(ctx->h_mail[1] & 0xFFFFFFFF);
+    unsigned st;
+    FMK_TRY(fmk_read_back(ctx, &st, d_status, 4));
     if (st & VP_BAD_LEVEL) return fmk_set_error(ctx, FMK_E_LEVEL, "volume_profile_rolling: footprint level outside its window");
     if (st & VP_ONE_LEVEL)
         return fmk_set_error(ctx, FMK_E_LEVEL, "volume_profile_rolling: a window spans a single price level; it cannot be "

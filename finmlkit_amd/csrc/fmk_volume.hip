@@ -581,10 +581,10 @@ static int vol_run(fmk_ctx *ctx, const void *a, int64_t n, double thr, VolCache 
             ent[k] = entall + eo; off[k] = offall + eo; eo += (size_t)nblk[k];
         }
     }
-    int *d_status = (int *)(ctx->d_mail + 32);
-    uint32_t *d_root = (uint32_t *)(ctx->d_mail + 33);
-    int *d_root_tie = (int *)(ctx->d_mail + 35);
-    FMK_HIP(ctx, hipMemsetAsync(ctx->d_mail + 32, 0, 32, ctx->stream));
+    fmk_mail::Vol::Levels *d_lv = &ctx->d_mail->vol.lv, lv;
+    int *d_status = &d_lv->status, *d_root_tie = &d_lv->root_tie;
+    uint32_t *d_root = &d_lv->root;
+    FMK_HIP(ctx, hipMemsetAsync(d_lv, 0, sizeof *d_lv, ctx->stream));
     {
         constexpr size_t lds = (size_t)(2 * S + 1 + (2 * S + 1) / 8 + 1) * 8 + (size_t)S * 8 + 64;
         if (lds > 64 * 1024)
@@ -602,18 +602,16 @@ static int vol_run(fmk_ctx *ctx, const void *a, int64_t n, double thr, VolCache 
         FMK_LAUNCH_CHECK(ctx);
     }
     // root entry + total count
-    FMK_HIP(ctx, hipMemcpyAsync(ctx->h_mail, ctx->d_mail + 32, 24, hipMemcpyDeviceToHost, ctx->stream));
-    FMK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    const int status = (int)(ctx->h_mail[0] & 0xFFFFFFFF);
-    const uint32_t root = (uint32_t)(ctx->h_mail[1] & 0xFFFFFFFFu);
+    FMK_TRY(fmk_read_back(ctx, &lv, d_lv, sizeof lv));
+    const int status = lv.status;
+    const uint32_t root = lv.root;
     if (status & VOL_ST_BAD) return 2;              // negative / NaN volumes: only the serial walk reproduces those
     if (status & VOL_ST_OVERFLOW) return 1;
     int64_t closes = 0;
     if (root != VOL_END) {
         if ((int64_t)root >= S) return 1;
         uint32_t cnt = 0;
-        FMK_HIP(ctx, hipMemcpyAsync(&cnt, C[K] + root, 4, hipMemcpyDeviceToHost, ctx->stream));
-        FMK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        FMK_TRY(fmk_read_back(ctx, &cnt, C[K] + root, 4));
         closes = cnt;
     }
     c.count = closes + 1;
@@ -961,10 +959,11 @@ static int vol_chase(fmk_ctx *ctx, const void *a, int64_t n, double thr, VolCach
     VcDD *Bb = (VcDD *)((char *)c.work + lp_bytes + tot_bytes);
     double *wgt = (double *)((char *)c.work + lp_bytes + tot_bytes + bb_bytes);
     VcDD *BW = (VcDD *)((char *)c.work + lp_bytes + tot_bytes + bb_bytes + wg_bytes);
-    int64_t *d_res = ctx->d_mail + 44;
-    int *d_bad = (int *)(ctx->d_mail + 40);
+    int64_t *d_res = &ctx->d_mail->vol.chase_res;
+    int *d_bad = &ctx->d_mail->vol_prefix_status;
+    auto &h = ctx->h_mail->vol.chase;
     if (!have_prefix) {
-        FMK_HIP(ctx, hipMemsetAsync(d_bad, 0, 8, ctx->stream));
+        FMK_HIP(ctx, hipMemsetAsync(d_bad, 0, sizeof *d_bad, ctx->stream));
         k_vc_prefix<AF64><<<(unsigned)fmk_ceil_div(n, VC_WG_TICKS), 256, 0, ctx->stream>>>(a, n, Lp, totals, d_bad);
         FMK_LAUNCH_CHECK(ctx);
         // serial double-double scan over the N/2048 workgroup totals, expanded to the N/512 blocks in parallel
@@ -975,11 +974,11 @@ static int vol_chase(fmk_ctx *ctx, const void *a, int64_t n, double thr, VolCach
         FMK_LAUNCH_CHECK(ctx);
     }
     if (total_only) {
-        FMK_HIP(ctx, hipMemcpyAsync(&ctx->h_mail[6], &Bb[nblk].hi, 8, hipMemcpyDeviceToHost, ctx->stream));
-        FMK_HIP(ctx, hipMemcpyAsync(&ctx->h_mail[5], d_bad, 8, hipMemcpyDeviceToHost, ctx->stream));
-        FMK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        memcpy(total, &ctx->h_mail[6], 8);
-        if (ctx->h_mail[5] & VOL_ST_BAD) return 2;      // negative / NaN amounts: only the serial walk reproduces those
+        hipError_t e = hipMemcpyAsync(&h.res, &Bb[nblk].hi, 8, hipMemcpyDeviceToHost, ctx->stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(&h.prefix_status, d_bad, sizeof *d_bad, hipMemcpyDeviceToHost, ctx->stream);
+        FMK_TRY(fmk_wait(ctx, e));
+        memcpy(total, &h.res, 8);
+        if (h.prefix_status & VOL_ST_BAD) return 2;         // negative / NaN amounts: only the serial walk reproduces those
         return FMK_OK;
     }
     int64_t cap = c.dbuf ? c.cap : 0;
@@ -994,11 +993,11 @@ static int vol_chase(fmk_ctx *ctx, const void *a, int64_t n, double thr, VolCach
         FMK_HIP(ctx, hipMemsetAsync(c.d_list, 0, 8, ctx->stream));
         k_vc_chase<<<1, 64, 0, ctx->stream>>>(Lp, Bb, n, nblk, thr, c.dbuf, c.cap, d_res, c.d_list, d_bad);
         FMK_LAUNCH_CHECK(ctx);
-        FMK_HIP(ctx, hipMemcpyAsync(&ctx->h_mail[6], d_res, 8, hipMemcpyDeviceToHost, ctx->stream));
-        FMK_HIP(ctx, hipMemcpyAsync(&ctx->h_mail[5], d_bad, 8, hipMemcpyDeviceToHost, ctx->stream));
-        FMK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        if (ctx->h_mail[5] & VOL_ST_BAD) return 2;
-        c.count = ctx->h_mail[6];
+        hipError_t e = hipMemcpyAsync(&h.res, d_res, 8, hipMemcpyDeviceToHost, ctx->stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(&h.prefix_status, d_bad, sizeof *d_bad, hipMemcpyDeviceToHost, ctx->stream);
+        FMK_TRY(fmk_wait(ctx, e));
+        if (h.prefix_status & VOL_ST_BAD) return 2;
+        c.count = h.res;
         if (c.count <= c.cap) return vol_certify(ctx, a, AF64 ? 1 : 0, n, thr, c);
         FMK_HIP(ctx, hipFree(c.dbuf));                              // more closes than expected: exact size, once more
         c.dbuf = nullptr;
@@ -1431,20 +1430,19 @@ __global__ __launch_bounds__(64) void k_vg_replay_wave(const void *__restrict__ 
 // fast mode, or 3 (a replay disagrees / more fragile decisions than the list holds -> serial walk)
 static int vol_certify(fmk_ctx *ctx, const void *a, int is_f64, int64_t n, double thr, VolCache &c)
 {
-    int *d_mis = (int *)(ctx->d_mail + 41);
-    FMK_HIP(ctx, hipMemcpyAsync(&ctx->h_mail[3], c.d_list, 8, hipMemcpyDeviceToHost, ctx->stream));
-    FMK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    const int64_t listed = ctx->h_mail[3];
+    int *d_mis = &ctx->d_mail->vol.mismatch;
+    int64_t listed;
+    FMK_TRY(fmk_read_back(ctx, &listed, c.d_list, 8));
     c.unc = listed;
     if (listed == 0 || ctx->fast_threshold) return FMK_OK;
     if (listed > VOL_LIST_CAP) return 3;
-    FMK_HIP(ctx, hipMemsetAsync(d_mis, 0, 8, ctx->stream));
+    FMK_HIP(ctx, hipMemsetAsync(d_mis, 0, sizeof *d_mis, ctx->stream));
     if (is_f64) k_vol_verify<true><<<(unsigned)fmk_ceil_div(listed, 64), 64, 0, ctx->stream>>>(a, n, thr, c.dbuf, c.count, c.d_list, d_mis);
     else k_vol_verify<false><<<(unsigned)fmk_ceil_div(listed, 64), 64, 0, ctx->stream>>>(a, n, thr, c.dbuf, c.count, c.d_list, d_mis);
     FMK_LAUNCH_CHECK(ctx);
-    FMK_HIP(ctx, hipMemcpyAsync(&ctx->h_mail[3], d_mis, 8, hipMemcpyDeviceToHost, ctx->stream));
-    FMK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    if (ctx->h_mail[3] & 1) return 3;
+    int mis;
+    FMK_TRY(fmk_read_back(ctx, &mis, d_mis, sizeof mis));
+    if (mis & 1) return 3;
     c.unc = 0;                                                      // every fragile decision replayed and confirmed
     return FMK_OK;
 }
@@ -1478,23 +1476,21 @@ static int vol_global_tables(fmk_ctx *ctx, const void *a, int is_f64, int64_t n,
     if (!c.d_list) FMK_HIP(ctx, hipMalloc((void **)&c.d_list, ((size_t)1 + VOL_LIST_CAP) * 8));
     uint32_t *nxt = (uint32_t *)c.work2;
     unsigned char *fragile = (unsigned char *)c.work2 + nxt_bytes;
-    uint32_t *d_root = (uint32_t *)(ctx->d_mail + 36);
-    unsigned *d_maxlen = (unsigned *)(ctx->d_mail + 37);
-    int *d_status = (int *)(ctx->d_mail + 38);
-    FMK_HIP(ctx, hipMemsetAsync(ctx->d_mail + 36, 0, 24, ctx->stream));
+    fmk_mail::Vol::Table *d_tb = &ctx->d_mail->vol.tb, tb;
+    uint32_t *d_root = &d_tb->root, *d_maxlen = &d_tb->maxlen;
+    int *d_status = &d_tb->status;
+    unsigned long long *d_nfrag = &d_tb->nfrag;
+    FMK_HIP(ctx, hipMemsetAsync(d_tb, 0, sizeof *d_tb, ctx->stream));
     FMK_HIP(ctx, hipMemsetAsync(c.d_list, 0, 8, ctx->stream));
-    const int *d_pstat = (const int *)(ctx->d_mail + 40);          // status of the prefix pass (k_vc_prefix)
-    unsigned long long *d_nfrag = (unsigned long long *)(ctx->d_mail + 39);
-    FMK_HIP(ctx, hipMemsetAsync(d_nfrag, 0, 8, ctx->stream));
+    const int *d_pstat = &ctx->d_mail->vol_prefix_status;           // status of the prefix pass (k_vc_prefix)
     k_vg_nxt<<<(unsigned)fmk_ceil_div(nblk, 4), 256, 0, ctx->stream>>>(Lp, Bb, n, nblk, thr, nxt, fragile, d_maxlen, d_pstat,
                                                                        d_nfrag);
     k_vg_root<<<1, 64, 0, ctx->stream>>>(Lp, Bb, n, nblk, thr, d_root, c.d_list, d_pstat);
     FMK_LAUNCH_CHECK(ctx);
-    FMK_HIP(ctx, hipMemcpyAsync(ctx->h_mail, ctx->d_mail + 36, 32, hipMemcpyDeviceToHost, ctx->stream));
-    FMK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    FMK_TRY(fmk_read_back(ctx, &tb, d_tb, sizeof tb));
     if (!ctx->fast_threshold) {
         // exact mode: settle the fragile ticks before the tables are built -- while that is cheaper than the serial walk
-        const double est_fragile = (double)ctx->h_mail[3] * (nblk >= 64 ? 64.0 : (double)nblk);
+        const double est_fragile = (double)tb.nfrag * (nblk >= 64 ? 64.0 : (double)nblk);
         if (est_fragile * mean_len > 24000.0 * (double)n) return 3; // 7e-13 s per replayed addition against 19 ns per tick
         int64_t few = -1;                                           // live fragile ticks when they fit the wave-replay list
         if (est_fragile < (double)VG_REPLAY_LIST_CAP / 2) {
@@ -1503,9 +1499,8 @@ static int vol_global_tables(fmk_ctx *ctx, const void *a, int is_f64, int64_t n,
             k_vg_fragile_list<<<(unsigned)fmk_ceil_div(fmk_ceil_div(n, 8), 256), 256, 0, ctx->stream>>>(fragile, n, thr, d_pstat,
                                                                                                       ticks, d_nfrag);
             FMK_LAUNCH_CHECK(ctx);
-            FMK_HIP(ctx, hipMemcpyAsync(&ctx->h_mail[3], d_nfrag, 8, hipMemcpyDeviceToHost, ctx->stream));
-            FMK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-            if (ctx->h_mail[3] <= VG_REPLAY_LIST_CAP) few = ctx->h_mail[3];
+            FMK_TRY(fmk_read_back(ctx, &tb.nfrag, d_nfrag, 8));
+            if (tb.nfrag <= VG_REPLAY_LIST_CAP) few = (int64_t)tb.nfrag;
             if (few > 0) {
                 if (is_f64) k_vg_replay_wave<true><<<(unsigned)few, 64, 0, ctx->stream>>>(a, n, thr, nxt, fragile, ticks, d_maxlen);
                 else k_vg_replay_wave<false><<<(unsigned)few, 64, 0, ctx->stream>>>(a, n, thr, nxt, fragile, ticks, d_maxlen);
@@ -1519,11 +1514,10 @@ static int vol_global_tables(fmk_ctx *ctx, const void *a, int is_f64, int64_t n,
         else k_vg_replay<false><<<rblocks, 256, 0, ctx->stream>>>(a, n, thr, nxt, fragile, d_pstat, d_maxlen, d_root, c.d_list,
                                                                    only_root);
         FMK_LAUNCH_CHECK(ctx);
-        FMK_HIP(ctx, hipMemcpyAsync(ctx->h_mail, ctx->d_mail + 36, 16, hipMemcpyDeviceToHost, ctx->stream));
-        FMK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        FMK_TRY(fmk_read_back(ctx, &tb, d_tb, sizeof tb));
     }
-    const uint32_t root = (uint32_t)(ctx->h_mail[0] & 0xFFFFFFFFu);
-    const int64_t longest = (int64_t)(ctx->h_mail[1] & 0xFFFFFFFFu);
+    const uint32_t root = tb.root;
+    const int64_t longest = tb.maxlen;
     int ls = 12;
     while (((int64_t)1 << ls) < longest) ++ls;
     const int64_t S = (int64_t)1 << ls;
@@ -1563,11 +1557,12 @@ static int vol_global_tables(fmk_ctx *ctx, const void *a, int is_f64, int64_t n,
     int64_t closes = 0;
     if (root != VOL_END) {
         if ((int64_t)root >= S) return 1;
-        FMK_HIP(ctx, hipMemcpyAsync(&ctx->h_mail[0], C[K] + root, 4, hipMemcpyDeviceToHost, ctx->stream));
-        FMK_HIP(ctx, hipMemcpyAsync(&ctx->h_mail[1], d_status, 4, hipMemcpyDeviceToHost, ctx->stream));
-        FMK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        if (ctx->h_mail[1] & VOL_ST_OVERFLOW) return 1;
-        closes = (int64_t)(ctx->h_mail[0] & 0xFFFFFFFFu);
+        auto &h = ctx->h_mail->vol.closes;
+        hipError_t e = hipMemcpyAsync(&h.count, C[K] + root, 4, hipMemcpyDeviceToHost, ctx->stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(&h.status, d_status, 4, hipMemcpyDeviceToHost, ctx->stream);
+        FMK_TRY(fmk_wait(ctx, e));
+        if (h.status & VOL_ST_OVERFLOW) return 1;
+        closes = h.count;
     }
     c.count = closes + 1;
     if (c.dbuf && c.cap < c.count) { FMK_HIP(ctx, hipFree(c.dbuf)); c.dbuf = nullptr; }

@@ -424,9 +424,10 @@ static int vx_run(fmk_ctx *ctx, const void *a, int64_t n, double thr, VolCache &
             ent[k] = entall + eo; off[k] = offall + eo; eo += (size_t)nblk[k];
         }
     }
-    int *d_status = (int *)(ctx->d_mail + 32);
-    uint32_t *d_root = (uint32_t *)(ctx->d_mail + 33);
-    FMK_HIP(ctx, hipMemsetAsync(ctx->d_mail + 32, 0, 32, ctx->stream));
+    fmk_mail::Vol::Levels *d_lv = &ctx->d_mail->vol.lv, lv;
+    int *d_status = &d_lv->status;
+    uint32_t *d_root = &d_lv->root;
+    FMK_HIP(ctx, hipMemsetAsync(d_lv, 0, sizeof *d_lv, ctx->stream));
     {
         constexpr int T = S + W;
         constexpr size_t lds = (size_t)(PAD ? T + 1 + (T + 1) / 8 + 1 : T + 2 + (T + 2) / 32 + 1) * 8 + (size_t)S * 2 + (size_t)(THREADS / 64) * 24 + 64;
@@ -446,10 +447,9 @@ static int vx_run(fmk_ctx *ctx, const void *a, int64_t n, double thr, VolCache &
                 W, E[k - 1], C[k - 1], nblk[k - 1], spanq[k - 1], E[k], C[k], nblk[k], d_status, RAD);
         FMK_LAUNCH_CHECK(ctx);
     }
-    FMK_HIP(ctx, hipMemcpyAsync(ctx->h_mail, ctx->d_mail + 32, 24, hipMemcpyDeviceToHost, ctx->stream));
-    FMK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    const int status = (int)(ctx->h_mail[0] & 0xFFFFFFFF);
-    const uint32_t root = (uint32_t)(ctx->h_mail[1] & 0xFFFFFFFFu);
+    FMK_TRY(fmk_read_back(ctx, &lv, d_lv, sizeof lv));
+    const int status = lv.status;
+    const uint32_t root = lv.root;
     if (status & VOL_ST_BAD) return 2;
     if (status & VOL_ST_INEXACT) return 4;                          // no class of this tier will serve the stream
     if (status & VOL_ST_OVERFLOW) return 1;
@@ -457,8 +457,7 @@ static int vx_run(fmk_ctx *ctx, const void *a, int64_t n, double thr, VolCache &
     if (root != VOL_END) {
         if ((int64_t)root >= W) return 1;
         uint32_t cnt = 0;
-        FMK_HIP(ctx, hipMemcpyAsync(&cnt, (K == 0 ? E[0] : C[K]) + root, 4, hipMemcpyDeviceToHost, ctx->stream));
-        FMK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        FMK_TRY(fmk_read_back(ctx, &cnt, (K == 0 ? E[0] : C[K]) + root, 4));
         closes = K == 0 ? cnt >> 16 : cnt;                           // (a single block: the packed level-0 row itself)
     }
     c.count = closes + 1;
