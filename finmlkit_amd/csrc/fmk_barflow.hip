@@ -1646,7 +1646,15 @@ struct FuState {                      // what the sizing call leaves for the fil
     FuStage stg;
     unsigned long long *fp_list;
     int64_t nb, n_fp;
-    const int64_t *ci;                // the close indices the rows belong to (the fill call must name the same)
+    // the call the rows belong to: the fill call must name the same close indices, columns, tick size and level offsets (a sizing
+    // call that no fill followed must not hand its rows to a later fill on other columns that happens to share the close indices)
+    const int64_t *ci;
+    const double *price;
+    const void *amount;
+    const int8_t *side;
+    int64_t n, max_levels;
+    double tick;
+    const int64_t *level_offsets;
 };
 
 void fmk_fused_release(fmk_ctx *ctx)
@@ -1771,6 +1779,8 @@ static int bars_flow_fused(fmk_ctx *ctx, const double *d_price, const float *d_a
     FuArgs *d_args = (FuArgs *)(blk + rows * 16 + lbytes + fbytes);
     unsigned long long *d_scrap = (unsigned long long *)(blk + rows * 16 + lbytes + fbytes + ((sizeof(FuArgs) + 255) & ~(size_t)255));
     st->nb = nb; st->ci = d_close_idx; st->n_fp = -1;
+    st->price = d_price; st->amount = d_amount; st->side = d_side; st->n = n; st->tick = price_tick_size;
+    st->level_offsets = d_level_offsets;
     ctx->fused = st;
     // two redo lists: the one-pass kernel's own (bars of <= FU_MAXT ticks: one wave per bar walks them, k_bar_dir_redo) and k_bar_dir's
     // (any length: the chunk-record kernel).  On the bench tape 0.19 % of the bars are TRUE near-ties -- its prices and sizes lie on
@@ -1853,9 +1863,10 @@ static int bars_flow_fused(fmk_ctx *ctx, const double *d_price, const float *d_a
     FU_HIP(hipMemcpyAsync(&last.n_dir, dir_list, 8, hipMemcpyDeviceToHost, ctx->stream));
     FU_HIP(hipMemcpyAsync(&last.n_redo, redo_fu, 8, hipMemcpyDeviceToHost, ctx->stream));
 #undef FU_HIP
-    rc = fmk_comp_bar_footprints_size_dev(ctx, d_low, d_high, nb, price_tick_size, d_level_offsets, total_levels, max_levels);
+    rc = fmk_footprints_size(ctx, d_low, d_high, nb, price_tick_size, d_level_offsets, total_levels, max_levels);
     if (rc != FMK_OK) return fail(rc);
     st->n_fp = last.n_fp;                                            // (the sizing call has waited for the stream)
+    st->max_levels = *max_levels;
     if (!units) fmk_fused_release(ctx);                              // nothing staged: the fill call is the ordinary one
     return FMK_OK;
 }
@@ -1870,8 +1881,14 @@ int fmk_fused_fill(fmk_ctx *ctx, const double *d_price, const void *d_amount, in
     *handled = 0;
     FuState *st = (FuState *)ctx->fused;
     if (!st) return FMK_OK;
-    if (st->ci != d_close_idx || st->nb != n_idx - 1 || amount_is_f64 || st->n_fp < 0) { fmk_fused_release(ctx); return FMK_OK; }
+    if (st->ci != d_close_idx || st->nb != n_idx - 1 || amount_is_f64 || st->n_fp < 0 || st->price != d_price || st->amount != d_amount ||
+        st->side != d_side || st->n != n || st->tick != price_tick_size || st->level_offsets != d_level_offsets ||
+        st->max_levels != max_levels) {
+        fmk_fused_release(ctx);
+        return FMK_OK;
+    }
     *handled = 1;
+    ctx->h_mail->fused_last.fill_staged = 1;
     const int64_t nb = st->nb;
     FpOut o;
     memcpy(&o, d_out, sizeof(o));
@@ -1906,6 +1923,20 @@ extern "C" int fmk_diag_fused_last(fmk_ctx *ctx, int64_t *n_fp_list, int64_t *n_
     *n_fp_list = ctx->h_mail->fused_last.n_fp;
     *n_dir_list = ctx->h_mail->fused_last.n_dir;
     *n_redo = ctx->h_mail->fused_last.n_redo;
+    return FMK_OK;
+}
+// which schedule the last fmk_bars_flow_size[_defer]_dev call took (0 the two-pass schedules, 1 the one-pass kernel with the unit
+// histogram, 2 the one-pass kernel with float64 volumes), and whether the last footprint fill consumed the rows a sizing call staged
+extern "C" int fmk_diag_fused_mode(fmk_ctx *ctx, int64_t *mode, int64_t *fill_used_staged)
+{
+    *mode = ctx->h_mail->fused_last.mode;
+    *fill_used_staged = ctx->h_mail->fused_last.fill_staged;
+    return FMK_OK;
+}
+// compute units of the context's device (the one-pass gate asks for 8 bars per CU)
+extern "C" int fmk_diag_n_cu(fmk_ctx *ctx, int64_t *n_cu)
+{
+    *n_cu = ctx->n_cu;
     return FMK_OK;
 }
 
@@ -2017,6 +2048,7 @@ extern "C" int fmk_bars_flow_size_dev(fmk_ctx *ctx, const double *d_price, const
                                       int64_t *d_n_zero_div, int64_t *d_level_offsets, int64_t *total_levels,
                                       int64_t *max_levels)
 {
+    ctx->h_mail->fused_last.mode = 0;
     return bars_flow_size(ctx, d_price, d_amount, amount_is_f64, n, d_close_idx, n_idx, d_side, price_tick_size, d_open, d_high,
                           d_low, d_close, d_volume, d_vwap, d_trades, d_median, d_dir, d_n_zero_div, d_level_offsets,
                           total_levels, max_levels, nullptr);
@@ -2034,6 +2066,7 @@ extern "C" int fmk_bars_flow_size_defer_dev(fmk_ctx *ctx, const double *d_price,
                                             int64_t *d_level_offsets, int64_t *total_levels, int64_t *max_levels,
                                             int *median_deferred)
 {
+    ctx->h_mail->fused_last.mode = 0;                                   // (fmk_diag_fused_mode: set again below when the one pass runs)
     if (!median_deferred) return fmk_set_error(ctx, FMK_E_ARG, "bars_flow: median_deferred must not be NULL");
     *median_deferred = 0;
     return bars_flow_size(ctx, d_price, d_amount, amount_is_f64, n, d_close_idx, n_idx, d_side, price_tick_size, d_open, d_high,
@@ -2063,6 +2096,7 @@ static int bars_flow_size(fmk_ctx *ctx, const double *d_price, const void *d_amo
     {
         int fused_mode = 0;
         FMK_TRY(bars_flow_fused_ok(ctx, d_amount, amount_is_f64, n, d_close_idx, n_idx - 1, &fused_mode));
+        ctx->h_mail->fused_last.mode = fused_mode;
         if (fused_mode)
             return bars_flow_fused(ctx, d_price, (const float *)d_amount, n, d_close_idx, n_idx, d_side, price_tick_size, d_open, d_high,
                                    d_low, d_close, d_volume, d_vwap, d_trades, d_median, d_dir, d_n_zero_div, d_level_offsets,
@@ -2198,8 +2232,8 @@ static int bars_flow_size(fmk_ctx *ctx, const double *d_price, const void *d_amo
             FMK_TRY(rc);
             FMK_HIP(ctx, hipEventRecord(ctx->aev[1], ctx->aux));
             FMK_HIP(ctx, hipStreamWaitEvent(ctx->stream, ctx->aev[1], 0));
-            return fmk_comp_bar_footprints_size_dev(ctx, d_low, d_high, n_idx - 1, price_tick_size, d_level_offsets, total_levels,
-                                                    max_levels);
+            return fmk_footprints_size(ctx, d_low, d_high, n_idx - 1, price_tick_size, d_level_offsets, total_levels,
+                                       max_levels);
         }
         // How many bars did the lane kernel hand on?  On a stream of about equally long bars none, and their OHLC is done.  On real
         // one-minute bars (lognormal lengths) most waves keep only their short bars (k_bar_dir_lanes: the 70 % rule): the bars that
@@ -2213,15 +2247,15 @@ static int bars_flow_size(fmk_ctx *ctx, const double *d_price, const void *d_amo
             // k_bar_dir above; medians (and open .. trades of the bars beyond 1 344 ticks) by comp_bar_ohlcv's size classes
             FMK_TRY(fmk_median_small_ohlcv_long_launch(ctx, d_price, (const float *)d_amount, d_close_idx, nb, n, d_open, d_high, d_low,
                                                        d_close, d_volume, d_vwap, d_trades, d_median));
-            return fmk_comp_bar_footprints_size_dev(ctx, d_low, d_high, n_idx - 1, price_tick_size, d_level_offsets, total_levels,
-                                                    max_levels);
+            return fmk_footprints_size(ctx, d_low, d_high, n_idx - 1, price_tick_size, d_level_offsets, total_levels,
+                                       max_levels);
         }
         if (side_median) FMK_HIP(ctx, hipStreamWaitEvent(ctx->stream, ctx->aev[1], 0));    // the medians of the auxiliary stream
         if (n_long > nb / 50) {
             FMK_TRY(fmk_comp_bar_ohlcv_dev(ctx, d_price, d_amount, 0, n, d_close_idx, n_idx, d_open, d_high, d_low, d_close, d_volume,
                                            d_vwap, d_trades, d_median));
-            return fmk_comp_bar_footprints_size_dev(ctx, d_low, d_high, n_idx - 1, price_tick_size, d_level_offsets, total_levels,
-                                                    max_levels);
+            return fmk_footprints_size(ctx, d_low, d_high, n_idx - 1, price_tick_size, d_level_offsets, total_levels,
+                                       max_levels);
         }
         FMK_TRY(fmk_ohlcv_leftover_launch(ctx, d_price, d_amount, 0, d_close_idx, nb, n, 8192, any_long, d_open, d_high, d_low,
                                           d_close, d_volume, d_vwap, d_trades));
@@ -2262,8 +2296,8 @@ static int bars_flow_size(fmk_ctx *ctx, const double *d_price, const void *d_amo
         FMK_LAUNCH_CHECK(ctx);
         if (d_median) FMK_TRY(fmk_median_launch(ctx, d_amount, 0, d_close_idx, nb, (int64_t)BF_MED_TILES * 512, saw_long, d_median, n));
     }
-    return fmk_comp_bar_footprints_size_dev(ctx, d_low, d_high, n_idx - 1, price_tick_size, d_level_offsets, total_levels,
-                                            max_levels);
+    return fmk_footprints_size(ctx, d_low, d_high, n_idx - 1, price_tick_size, d_level_offsets, total_levels,
+                               max_levels);
 }
 
 // (In-kernel fusion of the order-flow and footprint halves was built and measured twice in round 1 -- one wave doing both halves on a

@@ -27,8 +27,10 @@ struct fmk_mail {
     // by k_bar_footprints<MED>, fmk_footprint.hip); [1] is read by fmk_diag_fp_median_fallbacks after the call
     int fp_median[2];
     // host copy only: the list sizes of the last one-pass cfg 4 sizing call (fmk_barflow.hip, queued without a wait: the sizing
-    // call waits later); read by fmk_diag_fused_last and by the fill call (n_fp)
-    struct { int64_t n_fp, n_dir, n_redo; } fused_last;
+    // call waits later); read by fmk_diag_fused_last and by the fill call (n_fp).  mode: the schedule the last cfg 4 sizing call
+    // took (0 two-pass, 1 / 2 one pass with / without the unit histogram), fill_staged: the last footprint fill consumed staged
+    // rows -- both read by fmk_diag_fused_mode
+    struct { int64_t n_fp, n_dir, n_redo, mode, fill_staged; } fused_last;
 
     // ---- per-call fields
     uint8_t staging[1024];                 // host copy: fmk_read_back's landing area
@@ -111,6 +113,9 @@ struct fmk_ctx {
     void *fused;
 };
 void fmk_fused_release(fmk_ctx *ctx);
+// fmk_comp_bar_footprints_size_dev without dropping staged rows: the cfg 4 sizing calls (fmk_barflow.hip)
+int fmk_footprints_size(fmk_ctx *ctx, const double *d_bar_lows, const double *d_bar_highs, int64_t n_bars, double price_tick_size,
+                        int64_t *d_level_offsets, int64_t *total_levels, int64_t *max_levels);
 int fmk_fused_fill(fmk_ctx *ctx, const double *d_price, const void *d_amount, int amount_is_f64, int64_t n, const int64_t *d_close_idx,
                    int64_t n_idx, const int8_t *d_side, double price_tick_size, const double *d_bar_lows, double imbalance_factor,
                    const int64_t *d_level_offsets, int64_t max_levels, const fmk_footprint_out *d_out, int64_t *d_n_bad_level,

@@ -85,9 +85,19 @@ __global__ __launch_bounds__(256) void k_fp_level_counts(const double *__restric
         atomicMax(max_levels, (unsigned long long)m);
 }
 
+// A sizing call of its own starts a new footprint computation: rows that an earlier one-pass cfg 4 sizing call staged (and no fill
+// consumed) belong to another call and are dropped.  The cfg 4 sizing calls themselves size through fmk_footprints_size, which
+// keeps what they have just staged.
 extern "C" int fmk_comp_bar_footprints_size_dev(fmk_ctx *ctx, const double *d_bar_lows, const double *d_bar_highs,
                                                 int64_t n_bars, double price_tick_size, int64_t *d_level_offsets,
                                                 int64_t *total_levels, int64_t *max_levels)
+{
+    fmk_fused_release(ctx);
+    return fmk_footprints_size(ctx, d_bar_lows, d_bar_highs, n_bars, price_tick_size, d_level_offsets, total_levels, max_levels);
+}
+
+int fmk_footprints_size(fmk_ctx *ctx, const double *d_bar_lows, const double *d_bar_highs, int64_t n_bars, double price_tick_size,
+                        int64_t *d_level_offsets, int64_t *total_levels, int64_t *max_levels)
 {
     if (n_bars == 0) {   // zero bars (base.py:615-752 has no length check): one offset, no levels
         FMK_HIP(ctx, hipSetDevice(ctx->device));
@@ -460,6 +470,16 @@ static int fp_lds_atomics_in_lane_order(fmk_ctx *ctx)
 // ---------------------------------------------------------------------------------------
 #define FP_SEG 256
 #define FP_SORT_BYTES (FP_SEG * 8)
+// Bytes of one wave's slice of k_bar_footprints in front of the sort table: FAST 16 B per level + the tree routine's stack, otherwise
+// 24 B per level + 64 ints (+ the median's candidate list).  The kernel and fp_launch both size the slice from here.  Rounded up to 16 B:
+// fp_accumulate_sorted reads and writes the table as int4 (ds_*_b128), which CDNA replays at about 64 cycles per wave instruction off
+// 16-byte alignment -- and the widest class takes lmax = the call's max_levels, which may be odd (24 lmax = 8 mod 16).
+__host__ __device__ constexpr size_t fp_wave_head_bytes(int lmax, bool fast, bool med_area)
+{
+    return ((fast ? (size_t)lmax * 16 + FMK_PW_PAR_STK * 4 : (size_t)lmax * 24 + 256 + (med_area ? (size_t)FP_MED_CAP * 4 : 0)) + 15) &
+           ~(size_t)15;
+}
+static_assert(FP_SORT_BYTES % 16 == 0, "the next wave's slice starts 16-byte aligned");
 // STATS: also measure the quantum a later bar could certify with (lowest set bit, magnitude); a wave whose bars keep failing that test
 // sweeps without (k_bar_footprints: re-probed every 32nd bar).
 template <bool STATS>
@@ -633,8 +653,7 @@ __global__ __launch_bounds__(256) void k_bar_footprints(const double *__restrict
     const int wpb = blockDim.x >> 6;
     // FAST: 16 B per level (no aux area) + the tree routine's tables
     constexpr size_t sort_bytes = (!AF64 && !GLOBAL) ? (size_t)FP_SORT_BYTES : 0;     // fp_accumulate_sorted's slice table + sorted amounts
-    const size_t per_wave = (FAST ? (size_t)lmax * 16 + FMK_PW_PAR_STK * 4
-                                  : (size_t)lmax * 24 + 256 + ((MED && !GLOBAL) ? (size_t)FP_MED_CAP * 4 : 0)) + sort_bytes;
+    const size_t per_wave = fp_wave_head_bytes(lmax, FAST, MED && !GLOBAL) + sort_bytes;
     // the wave's histogram: LDS for the three narrow classes (LDS-typed pointers: ds_add / ds_read), a slice of global
     // scratch for bars wider than 2048 levels (same code; a wave's own stores are visible to its later loads)
     unsigned char *mine;
@@ -1385,14 +1404,13 @@ static int fp_launch(fmk_ctx *ctx, const double *p, const void *a, const int8_t 
     // dispatcher then balances per wave
     const int wpb_in = wpb;
     const size_t sort_bytes = AF64 ? 0 : (size_t)FP_SORT_BYTES;
-    size_t smem = fast ? (size_t)wpb * ((size_t)lmax * 16 + FMK_PW_PAR_STK * 4 + sort_bytes)
-                       : (size_t)wpb * ((size_t)lmax * 24 + 256 + (med ? (size_t)FP_MED_CAP * 4 : 0) + sort_bytes);
+    size_t smem = (size_t)wpb * (fp_wave_head_bytes(lmax, fast, med) + sort_bytes);
     int64_t blocks = fmk_ceil_div(nb, wpb);
     int64_t cap = (int64_t)ctx->n_cu * 64 * (wpb_in / wpb);                        // (the same number of waves in the grid)
     unsigned char *gscratch = nullptr;
     if (lmax > (med ? FP_MAX_LEVELS : FP_MAX_LEVELS_LDS)) {
         // wide bars: one wave per workgroup, histogram in global scratch (<= 8 GB in total, >= 16 waves)
-        const size_t per_wave = (size_t)lmax * 24 + 256;
+        const size_t per_wave = fp_wave_head_bytes(lmax, false, false);      // (k_bar_footprints<.., GLOBAL>: no median area, no sort table)
         cap = (int64_t)(((size_t)8 << 30) / per_wave);
         if (cap < 16) cap = 16;
         if (cap > (int64_t)ctx->n_cu * 32) cap = (int64_t)ctx->n_cu * 32;     // (every wave slot of the chip: 65 -> 47 ms per 2e8 ticks of 6 000-level bars against n_cu * 8)
@@ -1466,6 +1484,7 @@ extern "C" int fmk_comp_bar_footprints_fill_dev(fmk_ctx *ctx, const double *d_pr
                                                 const int64_t *d_level_offsets, int64_t max_levels,
                                                 const fmk_footprint_out *d_out, int64_t *d_n_bad_level)
 {
+    ctx->h_mail->fused_last.fill_staged = 0;                        // (fmk_diag_fused_mode; fmk_fused_fill sets it when it serves the call)
     if (n_idx == 1) return FMK_OK;   // zero bars: nothing to fill
     if (n_idx < 1) return fmk_set_error(ctx, FMK_E_ARG, "negative dimensions are not allowed");
     if (n <= 0 || !d_side || !d_out) return fmk_set_error(ctx, FMK_E_ARG, "comp_bar_footprints: bad arguments");
@@ -1695,6 +1714,7 @@ extern "C" int fmk_comp_bar_footprints_fill_median_dev(fmk_ctx *ctx, const doubl
                                                        const fmk_footprint_out *d_out, int64_t *d_n_bad_level,
                                                        double *d_median)
 {
+    ctx->h_mail->fused_last.fill_staged = 0;                        // (fmk_diag_fused_mode; fmk_fused_fill sets it when it serves the call)
     if (n_idx == 1) return FMK_OK;   // zero bars: nothing to fill
     if (n_idx < 1) return fmk_set_error(ctx, FMK_E_ARG, "negative dimensions are not allowed");
     if (n <= 0 || !d_side || !d_out) return fmk_set_error(ctx, FMK_E_ARG, "comp_bar_footprints: bad arguments");

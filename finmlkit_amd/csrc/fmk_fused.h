@@ -587,6 +587,11 @@ __device__ __forceinline__ void fu_finish(const double *__restrict__ price, int6
         }
         if (fmk_near_f32_tie(mean, (1.17e-16 * (len_d + terms) + 1.2e-16) * fabs(mean))) mask |= 1u << 4;
         if (bf_force_redo != 0) mask = 0x7F;
+        // the reference starts the running extrema at +-1e9 (base.py:461-464): a bar whose signed volume or dollar sum stays beyond
+        // 1e9 from its first tick reports exactly 1e9 / -1e9.  (cum_ticks_* need no clamp: every tick of the class is +-1, so the
+        // running count of a bar of at most FU_LONGEST ticks never reaches 1e9.)
+        const float cvmin_f = (float)fmin(cvmin, 1e9), cvmax_f = (float)fmax(cvmax, -1e9);
+        const float dmin_f = (float)fmin(dmin_w, 1e9), dmax_f = (float)fmax(dmax_w, -1e9);
         if (lane == 0) {
             if (mask) {
                 // (bars of one tile: the wave-per-bar redo; longer ones: k_bar_dir's chunk-record kernel)
@@ -600,8 +605,8 @@ __device__ __forceinline__ void fu_finish(const double *__restrict__ price, int6
                 ps_[12] = (unsigned long long)__float_as_uint((float)db); ps_[13] = (unsigned long long)__float_as_uint((float)ds);
                 ps_[14] = (unsigned long long)__float_as_uint((float)mean); ps_[15] = (unsigned long long)__float_as_uint((float)mxs_w);
                 ps_[16] = (unsigned long long)(long long)tmin_w; ps_[17] = (unsigned long long)(long long)tmax_w;
-                ps_[18] = (unsigned long long)__float_as_uint((float)cvmin); ps_[19] = (unsigned long long)__float_as_uint((float)cvmax);
-                ps_[20] = (unsigned long long)__float_as_uint((float)dmin_w); ps_[21] = (unsigned long long)__float_as_uint((float)dmax_w);
+                ps_[18] = (unsigned long long)__float_as_uint(cvmin_f); ps_[19] = (unsigned long long)__float_as_uint(cvmax_f);
+                ps_[20] = (unsigned long long)__float_as_uint(dmin_f); ps_[21] = (unsigned long long)__float_as_uint(dmax_f);
             } else {
                 o.ticks_buy[b] = tb; o.ticks_sell[b] = tsell;
                 o.volume_buy[b] = (float)vb; o.volume_sell[b] = (float)vs;
@@ -609,8 +614,8 @@ __device__ __forceinline__ void fu_finish(const double *__restrict__ price, int6
                 o.max_spread[b] = (float)mxs_w;
                 o.mean_spread[b] = (float)mean;
                 o.cum_ticks_min[b] = tmin_w; o.cum_ticks_max[b] = tmax_w;
-                o.cum_volumes_min[b] = (float)cvmin; o.cum_volumes_max[b] = (float)cvmax;
-                o.cum_dollars_min[b] = (float)dmin_w; o.cum_dollars_max[b] = (float)dmax_w;
+                o.cum_volumes_min[b] = cvmin_f; o.cum_volumes_max[b] = cvmax_f;
+                o.cum_dollars_min[b] = dmin_f; o.cum_dollars_max[b] = dmax_f;
             }
         }
         pvalid |= 0x3FFF00u;

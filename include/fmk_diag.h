@@ -60,6 +60,12 @@ int fmk_diag_dir_redo(fmk_ctx *ctx, int64_t *out10);
 /* the last one-pass cfg-4 sizing call (csrc/fmk_fused.h): bars it handed to the footprint class kernels / to k_bar_dir / entries of
  * the tick-order redo list (float32 ties of the dollar columns and mean_spread) */
 int fmk_diag_fused_last(fmk_ctx *ctx, int64_t *n_fp_list, int64_t *n_dir_list, int64_t *n_redo);
+/* the schedule the last fmk_bars_flow_size[_defer]_dev call took: *mode 0 the two-pass schedules, 1 the one-pass kernel with the unit
+ * histogram, 2 the one-pass kernel with float64 volumes (written on every call, early returns included); *fill_used_staged 1 if the
+ * last footprint fill call consumed the level rows a one-pass sizing call had staged */
+int fmk_diag_fused_mode(fmk_ctx *ctx, int64_t *mode, int64_t *fill_used_staged);
+/* compute units of the context's device (the one-pass gate of cfg 4 counts bars per CU) */
+int fmk_diag_n_cu(fmk_ctx *ctx, int64_t *n_cu);
 /* the device's exp (csrc/fmk_exp.h: glibc's, restated) of n doubles on the device -- tests compare it with the host's exp() */
 int fmk_diag_exp_dev(fmk_ctx *ctx, const double *d_x, int64_t n, double *d_out);
 /* bars of the last fmk_comp_bar_footprints_fill_median_dev call whose median took the generic selection (bracket miss) */

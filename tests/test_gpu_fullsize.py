@@ -481,7 +481,8 @@ def test_all_bars_cfg2_against_threaded_oracle(big, host_cols, orc):
 
 
 def test_all_bars_cfg4_against_threaded_oracle(big, host_cols, orc):
-    _cfg4_all_bars(big, host_cols, orc, 60.0)
+    # the bench tape's one-minute bars (~1 200 ticks, dyadic sizes) take the one pass with the unit histogram by default
+    _cfg4_all_bars(big, host_cols, orc, 60.0, expect_mode=1)
 
 
 @pytest.mark.parametrize("interval", [3600.0, 86400.0])
@@ -502,19 +503,48 @@ def test_all_bars_cfg4_full_mantissa_sizes_against_threaded_oracle(big, host_col
     t.ctx.call("fmk_diag_fill_amounts_dev", C.c_uint64(42), c_i64(n), am2.p)
     t2 = engine.DeviceTrades(t.ctx, t.ts, t.price, am2, t.side)
     (ts, px, am, sd), m = host_cols
-    _cfg4_all_bars((engine, t2, n), ((ts, px, am2.view(0, m).to_host(), sd), m), orc, interval, tag="full_mantissa_sizes")
+    # (one-minute bars: a mean below 1 250 ticks, where the one pass without the unit histogram does not pay -- the two-pass schedules)
+    _cfg4_all_bars((engine, t2, n), ((ts, px, am2.view(0, m).to_host(), sd), m), orc, interval, tag="full_mantissa_sizes",
+                   expect_mode=0 if interval == 60.0 else None)
 
 
-def _cfg4_all_bars(big, host_cols, orc, interval, tag="dyadic_sizes"):
+def test_all_bars_cfg4_lognormal_full_mantissa_against_threaded_oracle(big, host_cols, orc):
+    """... and the primary cfg 4 figure of bench.py: bars of lognormal length (mean 1 200 ticks, sigma 1: what real one-minute bars look
+    like) on full-mantissa sizes -- the length census sends it to the two-pass schedules (sorted lanes, comp_bar_ohlcv's size classes,
+    the long-bar kernels); all bars of the full-size run again."""
+    import ctypes as C
+    engine, t, n = big
+    from finmlkit_amd._ffi import DeviceArray, c_i64
+    am2 = DeviceArray(t.ctx, n, np.float32)
+    t.ctx.call("fmk_diag_fill_amounts_dev", C.c_uint64(42), c_i64(n), am2.p)
+    t2 = engine.DeviceTrades(t.ctx, t.ts, t.price, am2, t.side)
+    rng = np.random.default_rng(7)                        # bench.py's bar lengths (seed 7), rebuilt here
+    lens = np.maximum(1, rng.lognormal(np.log(1200.0) - 0.5, 1.0, int(n / 1200 * 1.3)).astype(np.int64))
+    cih = np.concatenate([[-1], np.cumsum(lens) - 1])
+    cih = cih[cih <= n - 1].astype(np.int64)
+    (ts, px, am, sd), m = host_cols
+    _cfg4_all_bars((engine, t2, n), ((ts, px, am2.view(0, m).to_host(), sd), m), orc, None, tag="full_mantissa_sizes",
+                   ci=DeviceArray.from_host(t.ctx, cih), count_key="cfg4_full_mantissa_sizes_lognormal_bars", expect_mode=0)
+
+
+def _cfg4_all_bars(big, host_cols, orc, interval, tag="dyadic_sizes", ci=None, count_key=None, expect_mode=None):
+    """cfg 4 on all bars of the full-size run: time bars of `interval` seconds, or the close indices `ci` (a DeviceArray), recorded as
+    `count_key`; expect_mode: the schedule the sizing call must take (fmk_diag_fused_mode)."""
     import time
+    from tests.test_gpu_fused import fused_mode
     engine, t, n = big
     (ts, px, am, sd), m = host_cols
-    _, ci = t.time_bar_index(interval)
+    if ci is None:
+        _, ci = t.time_bar_index(interval)
     cih = ci.to_host()
     k = _bars_inside(cih, m, n)
     oci = cih[:k + 1]
     o, d, nz, off, flat, bar, bad = t.bars_fused(ci, 0.01, 3.0, want_median=True)
+    mode = fused_mode(t.ctx)
     assert int(bad.to_host()[0]) == 0 and int(nz.to_host()[0]) == 0
+    if expect_mode is not None:
+        assert mode[0] == expect_mode, f"cfg 4 took schedule {mode[0]}, expected {expect_mode}"
+        assert mode[1] == (expect_mode == 1)      # the fill consumed the staged rows exactly when the one pass staged them
     t0 = time.perf_counter()
     want_d = orc.comp_bar_directional_features(px, am, oci, sd)
     oo = orc.comp_bar_ohlcv(px, am, oci, want_median=True)
@@ -540,8 +570,9 @@ def _cfg4_all_bars(big, host_cols, orc, interval, tag="dyadic_sizes"):
     for key in ("buy_imbalances_sum", "sell_imbalances_sum", "cot_price_levels", "imb_max_run_signed", "vp_gini"):
         np.testing.assert_array_equal(bar[key].to_host()[:k], wbar[key], err_msg=key)
     np.testing.assert_allclose(bar["vp_skew"].to_host()[:k], wbar["vp_skew"], atol=1e-6)
-    print(f"cfg 4, {interval:.0f} s bars: {k} bars, {nl} footprint levels equal the oracle's; oracle {dt:.1f} s")
-    record(f"cfg4_{tag}_{interval:.0f}s_bars", ticks_compared=m, ticks_total=n, bars_compared=k, bars_total=len(cih) - 1,
+    count_key = count_key or f"cfg4_{tag}_{interval:.0f}s_bars"
+    print(f"{count_key}: {k} bars, {nl} footprint levels equal the oracle's; oracle {dt:.1f} s")
+    record(count_key, ticks_compared=m, ticks_total=n, bars_compared=k, bars_total=len(cih) - 1,
            footprint_levels_compared=nl)
 
 

@@ -1,6 +1,8 @@
 """GPU parity of the cfg-4 fused path (fmk_bars_flow_size_defer_dev + the footprint fill): OHLCV, then order-flow +
 footprints from ONE read of price/amount/side by the two-waves-per-bar kernel.  Checked against the CPU oracle, the
 reference-generated goldens and the separate reducers (same arithmetic -> identical bits)."""
+import zlib
+
 import numpy as np
 import pytest
 
@@ -21,8 +23,20 @@ def _fused(px, am, sd, ci, tick=0.01, imb=3.0):
             engine.to_host(bar), int(bad.to_host()[0]))
 
 
+def fused_mode(ctx):
+    """fmk_diag_fused_mode: (the schedule the last cfg 4 sizing call took: 0 two-pass, 1 one pass with the unit histogram, 2 one pass
+    with float64 volumes; 1 if the last footprint fill consumed the rows that call staged)"""
+    import ctypes as C
+    from finmlkit_amd._ffi import c_i64
+    mode, staged = c_i64(), c_i64()
+    ctx.call("fmk_diag_fused_mode", C.byref(mode), C.byref(staged))
+    return mode.value, staged.value
+
+
 def _check_all(orc, px, am, sd, ci, what, tick=0.01):
+    """-> fused_mode() right after the cfg 4 call"""
     t, cid, o, d, nz, off, flat, bar, bad = _fused(px, am, sd, ci, tick)
+    mode = fused_mode(t.ctx)
     assert bad == 0
     want_o = orc.comp_bar_ohlcv(px, am, ci)
     for k, w in zip(OHLCV_KEYS, want_o):
@@ -47,6 +61,7 @@ def _check_all(orc, px, am, sd, ci, what, tick=0.01):
     for k, v in {**engine.to_host(flat2), **engine.to_host(bar2)}.items():
         got = flat[k] if k in flat else bar[k]
         np.testing.assert_array_equal(got, v, err_msg=f"{what}: fused vs separate {k}")
+    return mode
 
 
 @pytest.mark.parametrize("case", ["syn_t60", "syn_t1", "syn_tick100", "syn_vol2048", "rnd_t120", "rnd_tick37"])
@@ -216,3 +231,203 @@ def test_one_pass_kernels_forced(orc, monkeypatch, n, interval, amounts, zeros, 
         sd[rng.random(n) < 0.1] = 0
     _, ci = orc._time_bar_indexer(ts, interval)
     _check_all(orc, px, am, sd, ci, f"FMK_FUSED={fused} n={n} iv={interval} {amounts}")
+
+
+# ---- the default gate of the one-pass kernels (bars_flow_fused_ok, FMK_FUSED unset), branch by branch ----------------------------------
+def _n_cu(ctx):
+    import ctypes as C
+    from finmlkit_amd._ffi import c_i64
+    v = c_i64()
+    ctx.call("fmk_diag_n_cu", C.byref(v))
+    return v.value
+
+
+def _gate_tape(kind, n_cu):
+    """-> (px, am, sd, ci) aimed at one branch of the gate: it takes the one pass for >= 8 bars per CU of about equal length (a census),
+    mean 256 .. 1 400 ticks, float32 sizes with a sample that certifies integer units (mode 1) or, from a mean of 1 250 ticks, sizes
+    that do not (mode 2); float64 sizes and negative sizes in the sample never."""
+    rng = np.random.default_rng(zlib.crc32(kind.encode()))
+    nb = 8 * n_cu + 40
+    mean = {"dyadic1300": 1300, "full1300": 1300, "short": 200}.get(kind, 600)
+    if kind == "one_short":
+        nb = 8 * n_cu - 1
+    if kind == "lognormal":                 # bench.py's cfg 4 bar lengths
+        n = 1200 * (nb + 200)
+        lens = np.maximum(1, rng.lognormal(np.log(1200.0) - 0.5, 1.0, int(n / 1200 * 1.3)).astype(np.int64))
+        ci = np.concatenate([[-1], np.cumsum(lens) - 1])
+        ci = ci[ci <= n - 1].astype(np.int64)
+    else:
+        lens = rng.integers(int(mean * 0.94), int(mean * 1.06) + 1, nb)
+        ci = np.concatenate([[-1], np.cumsum(lens) - 1]).astype(np.int64)
+        n = int(ci[-1]) + 1
+    px = np.round(100.0 + np.cumsum(rng.integers(-1, 2, n)) * 0.01, 2)
+    sd = rng.choice(np.array([-1, 1], np.int8), n)
+    if kind.startswith("full"):
+        am = rng.lognormal(-1, 1.2, n).astype(np.float32)
+    elif kind == "f64":
+        am = rng.lognormal(-1, 1.2, n)
+    else:
+        am = (rng.integers(1, 4097, n) / 1024.0).astype(np.float32)
+    if kind == "negative":                  # where k_fu_census samples: 16 amounts at each multiple of n / 4096
+        at = np.arange(0, 4096, 97) * (n // 4096)
+        am[at] = -am[at]
+    return px, am, sd, ci
+
+
+GATE_CASES = [("dyadic600", 1), ("full1300", 2), ("full600", 0), ("lognormal", 0), ("short", 0), ("one_short", 0), ("f64", 0),
+              ("negative", 0)]
+
+
+@pytest.mark.parametrize("kind,mode", GATE_CASES)
+def test_default_gate_takes_the_expected_schedule(orc, monkeypatch, kind, mode):
+    """FMK_FUSED unset: each tape is aimed at one branch of bars_flow_fused_ok; the schedule the library took (fmk_diag_fused_mode)
+    and every output against the oracle.  A change to the gate's thresholds or census that sends a tape elsewhere -- or switches the
+    one pass off -- fails here instead of leaving every parity test green."""
+    from finmlkit_amd import _ffi
+    monkeypatch.delenv("FMK_FUSED", raising=False)
+    n_cu = _n_cu(_ffi.default_context())
+    assert n_cu > 0
+    px, am, sd, ci = _gate_tape(kind, n_cu)
+    nb = len(ci) - 1
+    assert nb >= 8 * n_cu if kind != "one_short" else nb == 8 * n_cu - 1
+    got = _check_all(orc, px, am, sd, ci, f"gate tape {kind}")
+    assert got[0] == mode, f"{kind}: mode {got[0]}, expected {mode} ({nb} bars, mean {len(px) / nb:.0f} ticks)"
+    if mode == 1:
+        # the public call consumes the rows its sizing call staged (the fill does not fall back to the two-pass sweep)
+        t, *_ = _fused(px, am, sd, ci)
+        assert fused_mode(t.ctx) == (1, 1)
+
+
+# ---- the sizing / fill hand-off of the one-pass kernels (FuState): rows staged by one call never serve another ----------------------
+def _size_call(t, cid, tick, median=True):
+    """the first of engine.bars_fused's two calls (fmk_bars_flow_size_defer_dev) alone -> (ohlcv, directional, offsets, total, max_levels,
+    deferred)"""
+    import ctypes as C
+    from finmlkit_amd import engine
+    from finmlkit_amd._ffi import c_f64, c_i64
+    nb = cid.n - 1
+    o = t.alloc_ohlcv(nb, median)
+    off = engine.DeviceArray(t.ctx, nb + 1, np.int64)
+    tot, mx, deferred = c_i64(), c_i64(), C.c_int(0)
+    d = {k: engine.DeviceArray(t.ctx, nb, dt) for k, dt in engine.DIRECTIONAL_FIELDS}
+    dst = engine.DirectionalOut(**{k: d[k].ptr for k in d})
+    nz = engine.DeviceArray(t.ctx, 1, np.int64)
+    nz.zero()
+    t.ctx.call("fmk_bars_flow_size_defer_dev", t.price.p, t.amount.p, C.c_int(t.amount_is_f64), c_i64(t.n), cid.p, c_i64(cid.n),
+               t.side.p, c_f64(tick), o["open"].p, o["high"].p, o["low"].p, o["close"].p, o["volume"].p, o["vwap"].p, o["trades"].p,
+               o["median_trade_size"].p if median else None, C.byref(dst), nz.p, off.p, C.byref(tot), C.byref(mx), C.byref(deferred))
+    return o, d, off, tot.value, mx.value, deferred.value
+
+
+def _fill_call(t, cid, tick, o, off, tot, mx, median=None):
+    """the second call (fmk_comp_bar_footprints_fill_median_dev) -> (offsets, flat, per_bar, n_bad) on the host"""
+    import ctypes as C
+    from finmlkit_amd import engine
+    from finmlkit_amd._ffi import c_f64, c_i64
+    nb = cid.n - 1
+    flat = {k: engine.DeviceArray(t.ctx, tot, dt) for k, dt in engine.FOOTPRINT_FLAT_FIELDS}
+    bar = {k: engine.DeviceArray(t.ctx, nb, dt) for k, dt in engine.FOOTPRINT_BAR_FIELDS}
+    fst = engine.FootprintOut(**{k: v.ptr for k, v in {**flat, **bar}.items()})
+    bad = engine.DeviceArray(t.ctx, 1, np.int64)
+    bad.zero()
+    t.ctx.call("fmk_comp_bar_footprints_fill_median_dev", t.price.p, t.amount.p, C.c_int(t.amount_is_f64), c_i64(t.n), cid.p,
+               c_i64(cid.n), t.side.p, c_f64(tick), o["low"].p, c_f64(3.0), off.p, c_i64(mx), C.byref(fst), bad.p,
+               median.p if median is not None else None)
+    return off.to_host(), engine.to_host(flat), engine.to_host(bar), int(bad.to_host()[0])
+
+
+def _staged_tape(orc, n=300_000):
+    ts, px, am, sd = orc.synth(31, 0, n)
+    _, ci = orc._time_bar_indexer(ts, 60.0)
+    return ts, px, am, sd, ci
+
+
+def test_staged_rows_of_an_unfinished_call_do_not_serve_a_later_footprint_call(orc, monkeypatch):
+    """A one-pass sizing call (FMK_FUSED=2: integer units, level rows staged) that no fill follows -- engine.bars_fused when allocating
+    its outputs raises -- and then the stand-alone footprints of OTHER amounts and sides on the same close-index array: the rows of the
+    first call must not be emitted.  Price column, tick and close indices stay the same, so every layout agrees and an unfixed library
+    writes wrong values in bounds."""
+    from finmlkit_amd import engine
+    monkeypatch.setenv("FMK_FUSED", "2")
+    ts, px, am, sd, ci = _staged_tape(orc)
+    t = engine.DeviceTrades.from_numpy(np.zeros(len(px), np.int64), px, am, sd)
+    cid = engine.DeviceArray.from_host(t.ctx, ci)
+    o, d, off, tot, mx, deferred = _size_call(t, cid, 0.01)
+    assert fused_mode(t.ctx)[0] == 1
+    rng = np.random.default_rng(8)
+    am2 = (rng.integers(1, 257, len(px)) / 64.0).astype(np.float32)            # other dyadic sizes ...
+    sd2 = (-sd).astype(np.int8)                                                 # ... and every side flipped
+    t2 = engine.DeviceTrades(t.ctx, t.ts, t.price, engine.DeviceArray.from_host(t.ctx, am2), engine.DeviceArray.from_host(t.ctx, sd2))
+    off2, flat2, bar2, bad2 = t2.bar_footprints(cid, o["low"], o["high"], 0.01, 3.0)
+    staged = fused_mode(t.ctx)[1]
+    assert int(bad2.to_host()[0]) == 0
+    want_o = orc.comp_bar_ohlcv(px, am2, ci)
+    woff, wflat, wbar = orc.comp_bar_footprints_csr(px, am2, ci, sd2, 0.01, want_o[2], want_o[1], 3.0)
+    _check_fp(off2.to_host(), engine.to_host(flat2), engine.to_host(bar2), woff, wflat, wbar, "stale staged rows")
+    assert staged == 0
+    # ... and a finer tick for the same columns: more levels per bar, the same close indices
+    o, d, off, tot, mx, deferred = _size_call(t, cid, 0.01)
+    off3, flat3, bar3, bad3 = t.bar_footprints(cid, o["low"], o["high"], 0.005, 3.0)
+    staged = fused_mode(t.ctx)[1]
+    want_o = orc.comp_bar_ohlcv(px, am, ci)
+    woff, wflat, wbar = orc.comp_bar_footprints_csr(px, am, ci, sd, 0.005, want_o[2], want_o[1], 3.0)
+    _check_fp(off3.to_host(), engine.to_host(flat3), engine.to_host(bar3), woff, wflat, wbar, "stale staged rows, finer tick")
+    assert staged == 0
+
+
+def test_fill_after_trim_falls_back_to_the_two_pass_sweep(orc, monkeypatch):
+    """fmk_ctx_trim between the sizing call and the fill releases the staged rows: the fill then computes the footprints itself."""
+    from finmlkit_amd import engine
+    monkeypatch.setenv("FMK_FUSED", "2")
+    ts, px, am, sd, ci = _staged_tape(orc)
+    t = engine.DeviceTrades.from_numpy(np.zeros(len(px), np.int64), px, am, sd)
+    cid = engine.DeviceArray.from_host(t.ctx, ci)
+    o, d, off, tot, mx, deferred = _size_call(t, cid, 0.01)
+    assert fused_mode(t.ctx)[0] == 1 and deferred == 0
+    t.ctx.trim()
+    offh, flat, bar, bad = _fill_call(t, cid, 0.01, o, off, tot, mx)
+    assert fused_mode(t.ctx)[1] == 0 and bad == 0
+    want_o = orc.comp_bar_ohlcv(px, am, ci)
+    woff, wflat, wbar = orc.comp_bar_footprints_csr(px, am, ci, sd, 0.01, want_o[2], want_o[1], 3.0)
+    _check_fp(offh, flat, bar, woff, wflat, wbar, "fill after trim")
+    # (the same two calls without the trim: the fill takes the staged rows, with the same bits)
+    o, d, off, tot, mx, deferred = _size_call(t, cid, 0.01)
+    offh, flat, bar, bad = _fill_call(t, cid, 0.01, o, off, tot, mx)
+    assert fused_mode(t.ctx) == (1, 1) and bad == 0
+    _check_fp(offh, flat, bar, woff, wflat, wbar, "fill of the staged rows")
+
+
+# ---- the footprint median class at an odd max_levels (k_bar_footprints<.., MED>'s LDS layout) ----------------------------------------
+def test_footprint_median_class_at_odd_max_levels(orc, monkeypatch):
+    """Bars of 1 100 .. 1 500 ticks whose prices span 521 .. 1 001 levels at tick 0.01 (the widest exactly 1 001: max_levels is odd, and
+    the widest class takes lmax = max_levels), full-mantissa float32 sizes (the sorted tick-order sweep), the median left to the
+    footprint sweep: the layout with the median's candidate area in front of the sort table.  The two-pass schedule is the one that
+    defers the median (FMK_FUSED=0, the lane schedule, FMK_FLOW_MEDIAN_DEFER=1)."""
+    from finmlkit_amd import engine
+    monkeypatch.setenv("FMK_FUSED", "0")
+    monkeypatch.setenv("FMK_FLOW_LANES", "2")
+    monkeypatch.setenv("FMK_FLOW_SORT", "0")
+    monkeypatch.setenv("FMK_FLOW_MEDIAN_DEFER", "1")
+    rng = np.random.default_rng(1001)
+    nb = 300
+    lens = rng.integers(1100, 1501, nb)         # (about equal: the lane kernel keeps every bar, k_bar_dir_lanes' 70 % rule)
+    span = rng.integers(520, 1000, nb)
+    span[17] = 1000
+    lev = np.concatenate([np.concatenate([[0, s], rng.integers(0, s + 1, k - 2)]) for k, s in zip(lens, span)])
+    base = np.repeat(10_000 + rng.integers(-300, 300, nb), lens)
+    px = np.round((base + lev) * 0.01, 2)
+    n = len(px)
+    am = rng.lognormal(-1, 1.2, n).astype(np.float32)
+    sd = rng.choice(np.array([-1, 1], np.int8), n)
+    ci = np.concatenate([[-1], np.cumsum(lens) - 1]).astype(np.int64)
+    t = engine.DeviceTrades.from_numpy(np.zeros(n, np.int64), px, am, sd)
+    cid = engine.DeviceArray.from_host(t.ctx, ci)
+    o, d, off, tot, mx, deferred = _size_call(t, cid, 0.01)
+    assert mx == 1001 and deferred == 1 and fused_mode(t.ctx)[0] == 0
+    offh, flat, bar, bad = _fill_call(t, cid, 0.01, o, off, tot, mx, median=o["median_trade_size"])
+    assert bad == 0
+    want_o = orc.comp_bar_ohlcv(px, am, ci, want_median=True)
+    np.testing.assert_array_equal(o["median_trade_size"].to_host(), want_o[7])
+    woff, wflat, wbar = orc.comp_bar_footprints_csr(px, am, ci, sd, 0.01, want_o[2], want_o[1], 3.0)
+    _check_fp(offh, flat, bar, woff, wflat, wbar, "odd max_levels, median in the sweep")
+    _check_all(orc, px, am, sd, ci, "odd max_levels, median in the sweep")

@@ -385,3 +385,20 @@ def test_oracle_order_flow_near_tie_bar_with_a_nan_against_reference_vectors(orc
     got = orc.comp_bar_directional_features(px, am, ci, sd, raise_on_zero_div=False)
     for k, g, w in zip(G.DIR_KEYS, got, want):
         np.testing.assert_array_equal(g, w, err_msg=k)
+
+
+def test_oracle_order_flow_extrema_at_the_start_values_against_reference_vectors(orc):
+    """tests/golden/extrema_clamp.npz (oracle/gen_extrema_clamp.py): the reference's order-flow columns of whale-sized bars.  The
+    running extrema start at 1e9 / -1e9 (base.py:459-464), so bars whose signed volume or dollar sum stays beyond that from the first
+    tick report exactly the start value -- all-buy / all-sell bars of 1e9 .. 4e9 units (whole multiples of 2^20 and full mantissas),
+    bars whose sums cross +-1e9, bars where only the dollar sum passes 1e9."""
+    d = G.load("extrema_clamp")
+    got = orc.comp_bar_directional_features(d["price"], d["amount"], d["close_idx"], d["side"], raise_on_zero_div=False)
+    for k, g in zip(G.DIR_KEYS, got):
+        w = d["dir_" + k]
+        assert g.dtype == w.dtype, k
+        np.testing.assert_array_equal(g, w, err_msg=k)
+    # the tape reaches the start value in every one of the four columns, and leaves it in others
+    for k, v in (("cum_volumes_min", 1e9), ("cum_volumes_max", -1e9), ("cum_dollars_min", 1e9), ("cum_dollars_max", -1e9)):
+        at = d["dir_" + k] == np.float32(v)
+        assert 2 <= at.sum() < len(at), k
