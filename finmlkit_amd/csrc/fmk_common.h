@@ -70,6 +70,13 @@ struct fmk_mail {
         int saw_long;                      // k_bar_ohlcv_dir
     } bf;
     struct { unsigned long long sink; long long hops[2]; } diag;                               // fmk_diag.hip
+    struct Label {                         // fmk_label.hip
+        unsigned long long work;           // k_tb: next event of the persistent grid
+        long long skipped, opened, walked; // k_tb: events without a window, blocks opened, ticks walked (fmk_diag_label_last)
+        long long bad;                     // k_lb_precheck / k_lc_mark / k_lw_events: indices outside the tape
+        int64_t ts_ends[2];                // k_lb_precheck: ts[0], ts[n-1] (the tape's tick rate)
+        int64_t last[2];                   // host copy only: schedule (0 direct, 1 tables) and events of this context's last call
+    } label;
 };
 static_assert(sizeof(fmk_mail::fp_median) == 2 * sizeof(int), "k_bar_footprints adds to saw_long + 1");
 static_assert(alignof(fmk_mail) == 8, "the 64-bit atomics of the kernels need 8-byte fields");

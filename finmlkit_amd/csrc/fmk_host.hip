@@ -422,3 +422,72 @@ int fmk_volume_profile_rolling(fmk_ctx *ctx, const int64_t *bar_ts, const double
 }
 
 }  // extern "C"
+
+extern "C" {
+
+int fmk_triple_barrier(fmk_ctx *ctx, const int64_t *ts, const double *close_, int64_t n, const int64_t *event_idx,
+                       const double *targets, const int8_t *side, int64_t n_events, double bottom_mult, double top_mult,
+                       double vertical_barrier_sec, double min_close_time_sec, double min_ret, int8_t *labels, int64_t *touch_idx,
+                       double *ret, double *max_rb_ratio, int64_t *n_skipped)
+{
+    if (n_events <= 0) return fmk_set_error(ctx, FMK_E_ARG, "The event_idxs array must not be empty.");
+    if (n <= 0) return fmk_set_error(ctx, FMK_E_ARG, "triple_barrier: event indices outside the (empty) tape");
+    DevBag bag(ctx);
+    int64_t *d_ts, *d_ev, *d_touch, *d_skip;
+    double *d_c, *d_tg, *d_ret, *d_ratio;
+    int8_t *d_sd = nullptr, *d_lab;
+    FMK_TRY(bag.up(ts, n, &d_ts));
+    FMK_TRY(bag.up(close_, n, &d_c));
+    FMK_TRY(bag.up(event_idx, n_events, &d_ev));
+    FMK_TRY(bag.up(targets, n_events, &d_tg));
+    if (side) FMK_TRY(bag.up(side, n_events, &d_sd));
+    FMK_TRY(bag.out(n_events, &d_lab));
+    FMK_TRY(bag.out(n_events, &d_touch));
+    FMK_TRY(bag.out(n_events, &d_ret));
+    FMK_TRY(bag.out(n_events, &d_ratio));
+    FMK_TRY(bag.out(1, &d_skip));
+    FMK_TRY(fmk_memset(ctx, d_skip, 0, sizeof(int64_t)));
+    FMK_TRY(fmk_triple_barrier_dev(ctx, d_ts, d_c, n, d_ev, d_tg, d_sd, n_events, bottom_mult, top_mult, vertical_barrier_sec,
+                                   min_close_time_sec, min_ret, d_lab, d_touch, d_ret, d_ratio, d_skip));
+    FMK_TRY(down(ctx, labels, d_lab, n_events));
+    FMK_TRY(down(ctx, touch_idx, d_touch, n_events));
+    FMK_TRY(down(ctx, ret, d_ret, n_events));
+    FMK_TRY(down(ctx, max_rb_ratio, d_ratio, n_events));
+    FMK_TRY(down(ctx, n_skipped, d_skip, 1));
+    return FMK_OK;
+}
+
+int fmk_label_concurrency(fmk_ctx *ctx, const int64_t *event_idx, const int64_t *touch_idx, int64_t n_events, int64_t n,
+                          int16_t *concurrency)
+{
+    DevBag bag(ctx);
+    int64_t *d_ev, *d_touch;
+    int16_t *d_c;
+    FMK_TRY(bag.up(event_idx, n_events, &d_ev));
+    FMK_TRY(bag.up(touch_idx, n_events, &d_touch));
+    FMK_TRY(bag.out(n, &d_c));
+    FMK_TRY(fmk_label_concurrency_dev(ctx, d_ev, d_touch, n_events, n, d_c));
+    FMK_TRY(down(ctx, concurrency, d_c, n));
+    return FMK_OK;
+}
+
+int fmk_label_weights(fmk_ctx *ctx, const double *close_, const int16_t *concurrency, int64_t n, const int64_t *event_idx,
+                      const int64_t *touch_idx, int64_t n_events, double *avg_uniqueness, double *return_attribution)
+{
+    DevBag bag(ctx);
+    int64_t *d_ev, *d_touch;
+    int16_t *d_c;
+    double *d_p = nullptr, *d_u = nullptr, *d_a = nullptr;
+    if (close_) FMK_TRY(bag.up(close_, n, &d_p));
+    FMK_TRY(bag.up(concurrency, n, &d_c));
+    FMK_TRY(bag.up(event_idx, n_events, &d_ev));
+    FMK_TRY(bag.up(touch_idx, n_events, &d_touch));
+    if (avg_uniqueness) FMK_TRY(bag.out(n_events, &d_u));
+    if (return_attribution) FMK_TRY(bag.out(n_events, &d_a));
+    FMK_TRY(fmk_label_weights_dev(ctx, d_p, d_c, n, d_ev, d_touch, n_events, d_u, d_a));
+    FMK_TRY(down(ctx, avg_uniqueness, d_u, n_events));
+    FMK_TRY(down(ctx, return_attribution, d_a, n_events));
+    return FMK_OK;
+}
+
+}  // extern "C"

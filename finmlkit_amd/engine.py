@@ -379,6 +379,46 @@ class DeviceTrades:
         self.ctx.call("fmk_realized_vol_dev", r.p, c_i64(r.n), c_i64(int(window)), C.c_int(bool(is_sample)), out.p)
         return out
 
+    # ------------------------------------------------------------------ labels and sample weights
+    def triple_barrier(self, event_idx: DeviceArray, targets: DeviceArray, horizontal_barriers, vertical_barrier: float,
+                       min_close_time_sec: float, side: Optional[DeviceArray] = None, min_ret: float = 0.0):
+        """triple_barrier (label/tbm.py:11-158) on the resident tape; events, targets and sides are DeviceArrays (int64, float64,
+        int8).  -> (labels int8, touch_idx int64, returns float64, max_rb_ratios float64, n_skipped): n_skipped is a device
+        int64 counting the events whose window holds no later tick (label 0, NaN, touch_idx = event_idx)."""
+        if targets.n != event_idx.n:
+            raise ValueError("The lengths of event_idxs and targets must match.")
+        if side is not None and side.n != event_idx.n:
+            raise ValueError("The length of event_idxs must match the length of side.")
+        ne = event_idx.n
+        bottom, top = horizontal_barriers
+        out = (DeviceArray(self.ctx, ne, np.int8), DeviceArray(self.ctx, ne, np.int64), DeviceArray(self.ctx, ne, np.float64),
+               DeviceArray(self.ctx, ne, np.float64))
+        skipped = DeviceArray(self.ctx, 1, np.int64)
+        skipped.zero()
+        self.ctx.call("fmk_triple_barrier_dev", self.ts.p, self.price.p, c_i64(self.n), event_idx.p, targets.p,
+                      None if side is None else side.p, c_i64(ne), c_f64(bottom), c_f64(top), c_f64(vertical_barrier),
+                      c_f64(min_close_time_sec), c_f64(min_ret), out[0].p, out[1].p, out[2].p, out[3].p, skipped.p)
+        return out + (skipped,)
+
+    def label_concurrency(self, event_idx: DeviceArray, touch_idx: DeviceArray) -> DeviceArray:
+        """The concurrency column of average_uniqueness (label/weights.py:31-38): int16 per tick."""
+        if touch_idx.n != event_idx.n:
+            raise ValueError("Timestamps and lookahead indices must have the same length.")
+        out = DeviceArray(self.ctx, self.n, np.int16)
+        self.ctx.call("fmk_label_concurrency_dev", event_idx.p, touch_idx.p, c_i64(event_idx.n), c_i64(self.n), out.p)
+        return out
+
+    def label_weights(self, event_idx: DeviceArray, touch_idx: DeviceArray, concurrency: DeviceArray,
+                      want_attribution: bool = True) -> Tuple[DeviceArray, Optional[DeviceArray]]:
+        """average uniqueness and (not normalised) return attribution of the events from one pass over price + concurrency
+        (label/weights.py:41-47, 76-94) -> (avg_uniqueness, return_attribution or None)."""
+        ne = event_idx.n
+        avg = DeviceArray(self.ctx, ne, np.float64)
+        att = DeviceArray(self.ctx, ne, np.float64) if want_attribution else None
+        self.ctx.call("fmk_label_weights_dev", self.price.p, concurrency.p, c_i64(self.n), event_idx.p, touch_idx.p, c_i64(ne),
+                      avg.p, None if att is None else att.p)
+        return avg, att
+
 
 def to_host(d: Dict[str, DeviceArray]) -> Dict[str, np.ndarray]:
     return {k: v.to_host() for k, v in d.items()}

@@ -358,6 +358,43 @@ int fmk_cusum_bar_indexer_dev(fmk_ctx *ctx, const int64_t *d_ts, const double *d
 int fmk_cusum_bar_indexer(fmk_ctx *ctx, const int64_t *ts, const double *price, double *sigma, int64_t n,
                           double sigma_floor, double sigma_mult, int64_t *out, int64_t capacity, int64_t *n_out);
 
+/* ---- labels and sample weights on the tick tape: finmlkit/label/tbm.py, label/weights.py ------------------------
+ * triple_barrier (tbm.py:11-158) on the raw tape.  Per event: label (side labels -1 / +1; meta labels 0 / 1 when d_side is given),
+ * index of the first barrier touch, the return there and the max return / barrier ratio.  Labels, touch indices, returns and ratios
+ * are the reference's bit for bit (the host's log: csrc/fmk_log.h).  d_side == NULL: side labels.  Events may come in any order.
+ * An event whose window holds no later tick (t1_idx <= event_idx; the reference skips it and leaves its touch index
+ * uninitialised) gets label 0, NaN return and ratio, and its own event_idx as touch index; *d_n_skipped (device int64, may be
+ * NULL; the caller zeroes it) counts them.  Contract: prices finite and > 0, timestamps sorted.  FMK_E_ARG with the reference's
+ * messages: vertical_barrier <= 0, min_ret < 0, no events; also an event index outside [0, n).
+ * Two schedules (DESIGN.md "labels"): every tick of the path walked, or -- barriers hours long or disabled -- a (min, max) table of
+ * log(close) per 1024 ticks built per call, so that only the block holding the first touch is opened.  The call chooses by the
+ * ticks one vertical barrier spans at the tape's mean tick rate; it waits once, for that and for the index check.
+ * Host flavour: *n_skipped (host int64, may be NULL too) receives the count. */
+int fmk_triple_barrier_dev(fmk_ctx *ctx, const int64_t *d_ts, const double *d_close, int64_t n, const int64_t *d_event_idx,
+                           const double *d_targets, const int8_t *d_side, int64_t n_events, double bottom_mult, double top_mult,
+                           double vertical_barrier_sec, double min_close_time_sec, double min_ret, int8_t *d_labels,
+                           int64_t *d_touch_idx, double *d_ret, double *d_max_rb_ratio, int64_t *d_n_skipped);
+int fmk_triple_barrier(fmk_ctx *ctx, const int64_t *ts, const double *close_, int64_t n, const int64_t *event_idx,
+                       const double *targets, const int8_t *side, int64_t n_events, double bottom_mult, double top_mult,
+                       double vertical_barrier_sec, double min_close_time_sec, double min_ret, int8_t *labels, int64_t *touch_idx,
+                       double *ret, double *max_rb_ratio, int64_t *n_skipped);
+/* The concurrency column of average_uniqueness (weights.py:31-38): how many events [event_idx, touch_idx] cover each tick, int16
+ * with the reference's wrap-around.  n_events == 0: a zero column.  FMK_E_ARG: an event outside 0 <= event_idx <= touch_idx < n
+ * (the reference slices silently into something else there). */
+int fmk_label_concurrency_dev(fmk_ctx *ctx, const int64_t *d_event_idx, const int64_t *d_touch_idx, int64_t n_events, int64_t n,
+                              int16_t *d_concurrency);
+int fmk_label_concurrency(fmk_ctx *ctx, const int64_t *event_idx, const int64_t *touch_idx, int64_t n_events, int64_t n,
+                          int16_t *concurrency);
+/* average_uniqueness' weights (weights.py:41-47: mean of 1 / concurrency over the event) and return_attribution without its
+ * normalisation (weights.py:76-94: |sum of log(close[j] / close[j-1]) / concurrency[j]|) from ONE pass over close + concurrency
+ * (10 B/tick) that leaves per-block partial sums.  Either output may be NULL; d_close may be NULL when d_return_attribution is.
+ * Re-associated float64 sums (1e-9 relative for the positive terms of the first; the second within L * 2^-52 * sum|term|).
+ * FMK_E_ARG: an event outside 0 <= event_idx <= touch_idx < n. */
+int fmk_label_weights_dev(fmk_ctx *ctx, const double *d_close, const int16_t *d_concurrency, int64_t n, const int64_t *d_event_idx,
+                          const int64_t *d_touch_idx, int64_t n_events, double *d_avg_uniqueness, double *d_return_attribution);
+int fmk_label_weights(fmk_ctx *ctx, const double *close_, const int16_t *concurrency, int64_t n, const int64_t *event_idx,
+                      const int64_t *touch_idx, int64_t n_events, double *avg_uniqueness, double *return_attribution);
+
 /* ---- TradesData(preprocess=True) loops: finmlkit/bar/utils.py ("next" rank 4) ------------ */
 /* merge_split_trades (bar/utils.py:263-329): trades with the head's timestamp, maker flag and price (|dp| < 1e-8)
  * are merged, amounts summed in float32 in trade order; side = -1 if is_buyer_maker else 1 (is_buyer_maker may be

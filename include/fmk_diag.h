@@ -77,6 +77,9 @@ int fmk_diag_cusum_segments(int64_t *segments, double *rate);
 /* last CUSUM call: 1 if the one-pass form (csrc/fmk_cusum_onepass.h) answered, its fix-up launches, the chunks that had not merged
    within the first launch's limit, the number of chunks */
 int fmk_diag_cusum_onepass(int64_t *used, int64_t *fix_launches, int64_t *pending_first, int64_t *chunks);
+/* the last fmk_triple_barrier[_dev] call on this context: {schedule (0 every tick walked, 1 the block tables), events, events skipped (no tick in
+ * their window), blocks opened by the table schedule, ticks walked}; waits for the context's stream */
+int fmk_diag_label_last(fmk_ctx *ctx, int64_t *out5);
 
 #ifdef __cplusplus
 }
