@@ -93,6 +93,20 @@ def diag_lib() -> C.CDLL:
     return _diag
 
 
+OHLCV_PLAN_FIELDS = ("kind", "tile", "lanes", "nch", "grid", "block", "long_min", "first_stage")
+OHLCV_KINDS = ("small", "lanes", "rows", "pipelined")
+
+
+def ohlcv_plan(n, n_bars, amount_is_f64=False, want_median=True, time_bar_fused=False, n_cu=256, pipe_min_stage=4096) -> dict:
+    """fmk_diag_ohlcv_plan: the first-pass schedule comp_bar_ohlcv would take for these numbers (no context, no device)."""
+    out = (C.c_int64 * 8)()
+    check(lib().fmk_diag_ohlcv_plan(C.c_int64(n), C.c_int64(n_bars), C.c_int(int(amount_is_f64)), C.c_int(int(want_median)),
+                                    C.c_int(int(time_bar_fused)), C.c_int(n_cu), C.c_int64(pipe_min_stage), out))
+    plan = dict(zip(OHLCV_PLAN_FIELDS, (int(v) for v in out)))
+    plan["kind"] = OHLCV_KINDS[plan["kind"]]
+    return plan
+
+
 def check(rc: int, ctx=None, allow=()):
     """Map a C status to the exception type the reference raises for the same condition."""
     if rc == OK or rc in allow:

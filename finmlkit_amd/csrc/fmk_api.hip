@@ -104,7 +104,9 @@ int fmk_ctx_destroy(fmk_ctx *ctx)
         for (int i = 0; i < FMK_PROFILE_SLOTS; ++i) { (void)hipEventDestroy(ctx->kev[i][0]); (void)hipEventDestroy(ctx->kev[i][1]); }
     if (ctx->aux) {
         (void)hipStreamSynchronize(ctx->aux);
-        for (int i = 0; i < 4; ++i) (void)hipEventDestroy(ctx->aev[i]);
+        (void)hipEventDestroy(ctx->aux_fork);
+        (void)hipEventDestroy(ctx->aux_done);
+        (void)hipEventDestroy(ctx->aux_landed);
         (void)hipStreamDestroy(ctx->aux);
     }
     (void)hipStreamDestroy(ctx->stream);
@@ -428,6 +430,8 @@ int fmk_profile_read(fmk_ctx *ctx, double *ms, int capacity, int *count)
 
 int fmk_scratch(fmk_ctx *ctx, size_t bytes, void **out)
 {
+    if (ctx->aux && ctx->stream == ctx->aux)     // (inside FmkSide::run: the scratch and what the context's stream keeps in it)
+        return fmk_set_error(ctx, FMK_E_HIP, "fmk_scratch on the auxiliary stream: the context scratch belongs to the context's stream");
     if (bytes > ctx->scratch_bytes) {
         FMK_HIP(ctx, hipStreamSynchronize(ctx->stream));
         if (ctx->scratch) FMK_HIP(ctx, hipFree(ctx->scratch));
@@ -442,7 +446,7 @@ int fmk_scratch(fmk_ctx *ctx, size_t bytes, void **out)
 }
 
 // on = 1: park every fmk_free until on = 0 (then they are carried out in order).  For calls that launch on two streams at once.
-int fmk_pool_defer(fmk_ctx *ctx, int on)
+static int fmk_pool_defer(fmk_ctx *ctx, int on)
 {
     FmkPool *p = fmk_pool(ctx);
     if (on) { p->defer = true; return FMK_OK; }
@@ -454,21 +458,75 @@ int fmk_pool_defer(fmk_ctx *ctx, int on)
     return rc;
 }
 
-
-// the auxiliary stream of the pipelined time-bar step and its events (timing disabled: they only order the two streams)
-int fmk_ctx_aux(fmk_ctx *ctx)
+// the auxiliary stream and its events (timing disabled: they only order the two streams); everything is made, then published
+static int fmk_ctx_aux(fmk_ctx *ctx)
 {
     if (ctx->aux) return FMK_OK;
     FMK_HIP(ctx, hipSetDevice(ctx->device));
-    hipStream_t st;
+    hipStream_t st = nullptr;
+    hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
     // DEFAULT priority.  The lowest priority was this stream's first setting (its kernels run beside a launch of the context's stream and
     // must not take that launch's wave slots) -- the capped grids of those kernels do that on their own, and a lowest-priority queue
     // holding a blocked barrier packet makes every small dispatch of the context's queue take ~45 us instead of ~5: the sharded step,
     // which enqueues ~30 of them per step with the next step already queued, went from 2.35 to 2.9..3.2 ms (profiles/r04_sharded_step.txt);
     // the single-GPU step measures the same either way.
-    FMK_HIP(ctx, hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
-    for (int i = 0; i < 4; ++i) FMK_HIP(ctx, hipEventCreateWithFlags(&ctx->aev[i], hipEventDisableTiming));
+    hipError_t e = hipStreamCreateWithFlags(&st, hipStreamNonBlocking);
+    for (int i = 0; i < 3 && e == hipSuccess; ++i) e = hipEventCreateWithFlags(&ev[i], hipEventDisableTiming);
+    if (e != hipSuccess) {
+        for (int i = 0; i < 3; ++i) if (ev[i]) (void)hipEventDestroy(ev[i]);
+        if (st) (void)hipStreamDestroy(st);
+        FMK_HIP(ctx, e);
+    }
+    ctx->aux_fork = ev[0]; ctx->aux_done = ev[1]; ctx->aux_landed = ev[2];
     ctx->aux = st;
     return FMK_OK;
+}
+
+int FmkSide::fork(bool defer_pool)
+{
+    if (ctx->side_open) return fmk_set_error(ctx, FMK_E_HIP, "FmkSide::fork while another fork of this context is open");
+    FMK_TRY(fmk_ctx_aux(ctx));
+    FMK_HIP(ctx, hipEventRecord(ctx->aux_fork, ctx->stream));
+    FMK_HIP(ctx, hipStreamWaitEvent(ctx->aux, ctx->aux_fork, 0));
+    ctx->side_open = 1;
+    forked = true;
+    if (defer_pool) { (void)fmk_pool_defer(ctx, 1); parked = true; }
+    return FMK_OK;
+}
+
+int FmkSide::mark()
+{
+    FMK_HIP(ctx, hipEventRecord(ctx->aux_done, ctx->aux));
+    return FMK_OK;
+}
+
+int FmkSide::join()
+{
+    FMK_HIP(ctx, hipStreamWaitEvent(ctx->stream, ctx->aux_done, 0));
+    joined = true;
+    return FMK_OK;
+}
+
+int FmkSide::post(void *h_dst, const void *d_src, size_t bytes)
+{
+    FMK_HIP(ctx, hipMemcpyAsync(h_dst, d_src, bytes, hipMemcpyDeviceToHost, ctx->aux));
+    posted = true;
+    FMK_HIP(ctx, hipEventRecord(ctx->aux_landed, ctx->aux));
+    return FMK_OK;
+}
+
+int FmkSide::landed()
+{
+    FMK_HIP(ctx, hipEventSynchronize(ctx->aux_landed));
+    posted = false;
+    return FMK_OK;
+}
+
+FmkSide::~FmkSide()
+{
+    if (!forked) return;
+    if (!joined || posted) (void)hipStreamSynchronize(ctx->aux);
+    if (parked) (void)fmk_pool_defer(ctx, 0);
+    ctx->side_open = 0;
 }
 

@@ -1806,24 +1806,15 @@ static int bars_flow_fused(fmk_ctx *ctx, const double *d_price, const float *d_a
     // The medians of the bars of several tiles (more than FU_MAXT ticks) need nothing but the amounts: the long-bar kernels run on the
     // context's auxiliary stream BESIDE the one-pass kernels (on a tape of lognormal bar lengths they are 2.5 ms of a 14 ms call when
     // they come behind).  They cannot see the one-pass kernel's flag there, so they are launched whatever the tape holds (on a tape
-    // without such bars: an empty list).  While both streams carry launches of this call no freed block changes sides (fmk_pool_defer).
-    bool side_med = false;
-    if (d_median && nb >= 4096 && fmk_ctx_aux(ctx) == FMK_OK) {
-        FU_HIP(hipEventRecord(ctx->aev[0], ctx->stream));
-        FU_HIP(hipStreamWaitEvent(ctx->aux, ctx->aev[0], 0));
-        (void)fmk_pool_defer(ctx, 1);
-        hipStream_t keep = ctx->stream;
-        ctx->stream = ctx->aux;
-        rc = fmk_median_launch(ctx, d_amount, 0, d_close_idx, nb, FU_MAXT, nullptr, d_median, n);
-        ctx->stream = keep;
-        if (rc == FMK_OK && hipEventRecord(ctx->aev[1], ctx->aux) != hipSuccess) rc = fmk_set_error(ctx, FMK_E_HIP, "hipEventRecord");
-        if (rc != FMK_OK) { (void)hipStreamSynchronize(ctx->aux); (void)fmk_pool_defer(ctx, 0); return fail(rc); }
-        side_med = true;
+    // without such bars: an empty list).  While both streams carry launches of this call no freed block changes sides (fork(true)).
+    FmkSide side(ctx);                                                   // (an error return below: the side stream is drained first)
+    const bool side_med = d_median && nb >= 4096;
+    if (side_med) {
+        rc = side.fork(true);
+        if (rc == FMK_OK) rc = side.run([&] { return fmk_median_launch(ctx, d_amount, 0, d_close_idx, nb, FU_MAXT, nullptr, d_median, n); });
+        if (rc == FMK_OK) rc = side.mark();
+        if (rc != FMK_OK) return fail(rc);
     }
-    struct SideGuard {                                                   // (every return below passes here)
-        fmk_ctx *c; bool on;
-        ~SideGuard() { if (on) { (void)hipStreamSynchronize(c->aux); (void)fmk_pool_defer(c, 0); } }
-    } side_guard{ctx, side_med};
     if (units) {
         if (d_median)
             k_fu_bars<true, true><<<(unsigned)blocks, 256, 0, ctx->stream>>>(d_price, d_amount, d_side, d_close_idx, nb, n, price_tick_size, d_args);
@@ -1846,7 +1837,7 @@ static int bars_flow_fused(fmk_ctx *ctx, const double *d_price, const float *d_a
                                    d_volume, d_vwap, d_trades);
     if (rc == FMK_OK && d_median && !side_med) rc = fmk_median_launch(ctx, d_amount, 0, d_close_idx, nb, FU_MAXT, saw_long, d_median, n);
     if (rc != FMK_OK) return fail(rc);
-    if (side_med) FU_HIP(hipStreamWaitEvent(ctx->stream, ctx->aev[1], 0));
+    if (side_med && (rc = side.join()) != FMK_OK) return fail(rc);
     // the order flow of the listed bars (outside the class: empty, long, uncertified sizes, sides other than +-1, prices <= 0), then the
     // tick-order redo of both kernels' float32 ties
     int64_t dblocks = fmk_ceil_div(nb, 4);
@@ -1965,10 +1956,8 @@ extern "C" int fmk_comp_bar_directional_dev(fmk_ctx *ctx, const double *d_price,
     FMK_HIP(ctx, hipMemsetAsync(redo, 0, 8, ctx->stream));
     const unsigned rblocks = (unsigned)(blocks < 4096 ? blocks : 4096);
     // bars of more than BFW_MIN ticks: a workgroup per bar, from a list
-    const bool wide_on = true;
-    const int64_t skip_above = wide_on ? BFW_MIN : INT64_MAX;
+    const int64_t skip_above = BFW_MIN;
     auto wide = [&]() -> int {
-        if (!wide_on) return FMK_OK;
         int64_t *wl = nullptr;
         FMK_TRY(fmk_long_bar_list(ctx, d_close_idx, nb, n, BFW_MIN, nullptr, &wl));
         if (amount_is_f64)
@@ -2017,11 +2006,6 @@ extern "C" int fmk_comp_bar_directional_dev(fmk_ctx *ctx, const double *d_price,
         FMK_TRY(wide());
         bf_redo_launch<true>(ctx, rblocks, d_price, d_amount, d_side, d_close_idx, n, o, redo);
     } else {
-        const int dwpb = 4;                // one-wave workgroups (see fp_launch, fmk_footprint.hip)
-        if (dwpb == 1)
-            k_bar_dir<false, 1><<<(unsigned)(blocks * 4), 64, 0, ctx->stream>>>(d_price, d_amount, d_side, d_close_idx, nb, n, o,
-                                                                              (unsigned long long *)d_n_zero_div, redo, nullptr, skip_above);
-        else
         k_bar_dir<false><<<(unsigned)blocks, 256, 0, ctx->stream>>>(d_price, d_amount, d_side, d_close_idx, nb, n, o,
                                                                   (unsigned long long *)d_n_zero_div, redo, nullptr, skip_above);
         FMK_LAUNCH_CHECK(ctx);
@@ -2107,25 +2091,17 @@ static int bars_flow_size(fmk_ctx *ctx, const double *d_price, const void *d_amo
         // Long bars (hourly, daily), float32 sizes: comp_bar_ohlcv and the order-flow features share nothing but the input columns -- the
         // first runs on the context's auxiliary stream beside the second (cfg 4 at hourly / daily bars 12.1 / 16.0 -> 11.0 / 13.9 ms per
         // 1e9 ticks; streams of short bars gain nothing and keep the plain order).  While both streams carry launches of this call no
-        // freed block goes back to the allocator's free list (fmk_pool_defer).
+        // freed block goes back to the allocator's free list (fork(true)).
         if (long_bars && !amount_is_f64) {
-            FMK_TRY(fmk_ctx_aux(ctx));
-            FMK_HIP(ctx, hipEventRecord(ctx->aev[0], ctx->stream));
-            FMK_HIP(ctx, hipStreamWaitEvent(ctx->aux, ctx->aev[0], 0));
-            (void)fmk_pool_defer(ctx, 1);
-            hipStream_t keep = ctx->stream;
-            ctx->stream = ctx->aux;
-            int rc = fmk_comp_bar_ohlcv_dev(ctx, d_price, d_amount, amount_is_f64, n, d_close_idx, n_idx, d_open, d_high, d_low,
-                                            d_close, d_volume, d_vwap, d_trades, d_median);
-            ctx->stream = keep;
-            if (rc == FMK_OK && hipEventRecord(ctx->aev[1], ctx->aux) != hipSuccess) rc = fmk_set_error(ctx, FMK_E_HIP, "hipEventRecord");
-            if (rc == FMK_OK)
-                rc = fmk_comp_bar_directional_dev(ctx, d_price, d_amount, amount_is_f64, n, d_close_idx, n_idx, d_side, d_dir, d_n_zero_div);
-            if (rc == FMK_OK && hipStreamWaitEvent(ctx->stream, ctx->aev[1], 0) != hipSuccess) rc = fmk_set_error(ctx, FMK_E_HIP, "hipStreamWaitEvent");
-            if (rc != FMK_OK) (void)hipStreamSynchronize(ctx->aux);             // (nothing of this call may outlive its error return)
-            const int rf = fmk_pool_defer(ctx, 0);
-            FMK_TRY(rc);
-            FMK_TRY(rf);
+            FmkSide side(ctx);                                                  // (nothing of this call outlives an error return)
+            FMK_TRY(side.fork(true));
+            FMK_TRY(side.run([&] {
+                return fmk_comp_bar_ohlcv_dev(ctx, d_price, d_amount, amount_is_f64, n, d_close_idx, n_idx, d_open, d_high, d_low,
+                                              d_close, d_volume, d_vwap, d_trades, d_median);
+            }));
+            FMK_TRY(side.mark());
+            FMK_TRY(fmk_comp_bar_directional_dev(ctx, d_price, d_amount, amount_is_f64, n, d_close_idx, n_idx, d_side, d_dir, d_n_zero_div));
+            FMK_TRY(side.join());
         } else {
         FMK_TRY(fmk_comp_bar_ohlcv_dev(ctx, d_price, d_amount, amount_is_f64, n, d_close_idx, n_idx, d_open, d_high, d_low,
                                        d_close, d_volume, d_vwap, d_trades, d_median));
@@ -2178,24 +2154,15 @@ static int bars_flow_size(fmk_ctx *ctx, const double *d_price, const void *d_amo
         //  amounts-only pass, run beside it)
         const char *dv0 = getenv("FMK_FLOW_MEDIAN_DEFER");
         const bool side_median = !sort_mode && d_median && !(median_deferred && dv0 && atoi(dv0));
+        FmkSide side(ctx);                                                       // (an error return below: the side stream is drained first)
         if (side_ohlcv || side_median) {
             if (side_ohlcv) oo.ohlc_max = 1344;                                  // 64 * FMK_SMALL_NCH: the reach of k_bar_median_small's class
-            FMK_TRY(fmk_ctx_aux(ctx));
-            FMK_HIP(ctx, hipEventRecord(ctx->aev[0], ctx->stream));              // (the close indices may come from a launch still in flight)
-            FMK_HIP(ctx, hipStreamWaitEvent(ctx->aux, ctx->aev[0], 0));
-            (void)fmk_pool_defer(ctx, 1);                                        // until the streams are joined: no freed block changes sides
+            // (the close indices may come from a launch still in flight; until the side ends no freed block changes sides)
+            FMK_TRY(side.fork(true));
         }
-        struct DeferGuard {                                                      // (every return below passes here)
-            fmk_ctx *c; bool on;
-            ~DeferGuard() { if (on) { (void)hipStreamSynchronize(c->aux); (void)fmk_pool_defer(c, 0); } }
-        } defer_guard{ctx, side_ohlcv || side_median};
         if (side_median) {
-            hipStream_t keep = ctx->stream;
-            ctx->stream = ctx->aux;
-            const int rc = fmk_median_small_launch(ctx, (const float *)d_amount, d_close_idx, nb, d_median, n);
-            ctx->stream = keep;
-            FMK_TRY(rc);
-            FMK_HIP(ctx, hipEventRecord(ctx->aev[1], ctx->aux));
+            FMK_TRY(side.run([&] { return fmk_median_small_launch(ctx, (const float *)d_amount, d_close_idx, nb, d_median, n); }));
+            FMK_TRY(side.mark());
         }
         k_bar_dir_lanes<true><<<(unsigned)lblocks, 64 * DL_WAVES, 0, ctx->stream>>>(d_price, (const float *)d_amount, d_side,
                                                                                    d_close_idx, nb, n, o,
@@ -2209,11 +2176,6 @@ static int bars_flow_size(fmk_ctx *ctx, const double *d_price, const void *d_amo
         }
         int64_t blocks = fmk_ceil_div(nb, 4);
         if (blocks > 2048) blocks = 2048;
-        const int dwpb = 4;
-        if (dwpb == 1)
-            k_bar_dir<false, 1><<<(unsigned)(blocks * 4), 64, 0, ctx->stream>>>(d_price, d_amount, d_side, d_close_idx, nb, n, o,
-                                                                              (unsigned long long *)d_n_zero_div, redo, long_list);
-        else
         k_bar_dir<false><<<(unsigned)blocks, 256, 0, ctx->stream>>>(d_price, d_amount, d_side, d_close_idx, nb, n, o,
                                                                    (unsigned long long *)d_n_zero_div, redo, long_list);
         bf_redo_launch<false>(ctx, (unsigned)blocks, d_price, d_amount, d_side, d_close_idx, n, o, redo);
@@ -2223,15 +2185,14 @@ static int bars_flow_size(fmk_ctx *ctx, const double *d_price, const void *d_amo
             FMK_HIP(ctx, le);
         }
         if (side_ohlcv) {
-            hipStream_t keep = ctx->stream;
-            ctx->stream = ctx->aux;                                              // every launch, wait and allocation of the call below: the auxiliary stream
-            int rc = fmk_median_small_ohlcv_long_launch(ctx, d_price, (const float *)d_amount, d_close_idx, nb, n, d_open, d_high, d_low,
-                                                        d_close, d_volume, d_vwap, d_trades, d_median);
-            ctx->stream = keep;
+            const int rc = side.run([&] {                                        // every launch, wait and allocation of this call: the auxiliary stream
+                return fmk_median_small_ohlcv_long_launch(ctx, d_price, (const float *)d_amount, d_close_idx, nb, n, d_open, d_high, d_low,
+                                                          d_close, d_volume, d_vwap, d_trades, d_median);
+            });
             if (perm) { (void)fmk_free(ctx, perm); perm = nullptr; }
             FMK_TRY(rc);
-            FMK_HIP(ctx, hipEventRecord(ctx->aev[1], ctx->aux));
-            FMK_HIP(ctx, hipStreamWaitEvent(ctx->stream, ctx->aev[1], 0));
+            FMK_TRY(side.mark());
+            FMK_TRY(side.join());
             return fmk_footprints_size(ctx, d_low, d_high, n_idx - 1, price_tick_size, d_level_offsets, total_levels,
                                        max_levels);
         }
@@ -2250,7 +2211,7 @@ static int bars_flow_size(fmk_ctx *ctx, const double *d_price, const void *d_amo
             return fmk_footprints_size(ctx, d_low, d_high, n_idx - 1, price_tick_size, d_level_offsets, total_levels,
                                        max_levels);
         }
-        if (side_median) FMK_HIP(ctx, hipStreamWaitEvent(ctx->stream, ctx->aev[1], 0));    // the medians of the auxiliary stream
+        if (side_median) FMK_TRY(side.join());                                   // the medians of the auxiliary stream
         if (n_long > nb / 50) {
             FMK_TRY(fmk_comp_bar_ohlcv_dev(ctx, d_price, d_amount, 0, n, d_close_idx, n_idx, d_open, d_high, d_low, d_close, d_volume,
                                            d_vwap, d_trades, d_median));

@@ -112,9 +112,12 @@ struct fmk_ctx {
     int idx_stale[3];
     // pinned staging buffers / streams of fmk_h2d_columns (fmk_upload.hip), made on first use
     void *upload;
-    // auxiliary stream + events of the pipelined time-bar step (fmk_ohlcv.hip), made on first use (fmk_ctx_aux)
+    // auxiliary stream, made on first use (fmk_ctx_aux), and the events that order it against the context's stream.  Reached through
+    // FmkSide (below) alone: aux_fork "the context's stream has come this far", aux_done "the side work is queued up to here",
+    // aux_landed "the copy to the host that FmkSide::post queued has arrived"; side_open: a fork has not ended yet
     hipStream_t aux;
-    hipEvent_t aev[4];
+    hipEvent_t aux_fork, aux_done, aux_landed;
+    int side_open;
     // cfg 4 in one pass (fmk_fused.h): what the sizing call leaves for the fill call -- staged level rows, the list of bars the class
     // kernels still have to serve (fmk_barflow.hip: FuState); released by the fill call, the next sizing call, trim and destroy
     void *fused;
@@ -127,8 +130,6 @@ int fmk_fused_fill(fmk_ctx *ctx, const double *d_price, const void *d_amount, in
                    int64_t n_idx, const int8_t *d_side, double price_tick_size, const double *d_bar_lows, double imbalance_factor,
                    const int64_t *d_level_offsets, int64_t max_levels, const fmk_footprint_out *d_out, int64_t *d_n_bad_level,
                    int *handled);
-int fmk_ctx_aux(fmk_ctx *ctx);
-int fmk_pool_defer(fmk_ctx *ctx, int on);   // park fmk_free while a call launches on two streams (fmk_api.hip)
 // fmk_indexers.hip: the time-bar indexer in stages (sample table, then edges [k0, k1) on a given stream, with the long-bar census)
 int fmk_time_bar_coarse_launch(fmk_ctx *ctx, const int64_t *d_ts, int64_t n, const int64_t **coarse, int64_t *m_out, int *clear);
 int fmk_time_bar_index_stage(fmk_ctx *ctx, hipStream_t st, const int64_t *d_ts, int64_t n, int64_t e0, int64_t d, int64_t ne,
@@ -200,6 +201,37 @@ int fmk_long_bar_list(fmk_ctx *ctx, const int64_t *d_close_idx, int64_t nb, int6
 #define FMK_LAUNCH_CHECK(ctx) FMK_HIP(ctx, hipGetLastError())
 
 static inline int64_t fmk_ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
+
+// One excursion of a call onto the context's auxiliary stream (fmk_api.hip), the only way there.  Rules:
+//  - one fork per context at a time: fork() while another FmkSide of the context is open is an error;
+//  - the context scratch belongs to the context's stream: fmk_scratch inside run() is an error;
+//  - success paths wait on the device only (events); a host wait happens in landed() and nowhere else;
+//  - an FmkSide that goes out of scope forked but not joined (any early return), or with a post() nobody waited for, drains the
+//    auxiliary stream first: no work of a call outlives its return on that stream;
+//  - fork(true) parks every fmk_free of the context until the FmkSide ends, so that no block freed on one stream is handed to the
+//    other (the allocator's free list follows ONE stream's order); fork(false) is for excursions without fmk_free in between.
+struct FmkSide {
+    explicit FmkSide(fmk_ctx *c) : ctx(c) {}
+    FmkSide(const FmkSide &) = delete;
+    FmkSide &operator=(const FmkSide &) = delete;
+    ~FmkSide();
+    int fork(bool defer_pool);             // the auxiliary stream waits for what the context's stream holds now
+    hipStream_t stream() const { return ctx->aux; }      // for callees that take a stream argument (after fork)
+    template <class F> int run(F &&f)      // f() with the auxiliary stream as ctx->stream: callees that launch on the context's stream
+    {
+        if (!forked) return fmk_set_error(ctx, FMK_E_HIP, "FmkSide::run without a fork");
+        struct Restore { fmk_ctx *c; hipStream_t keep; ~Restore() { c->stream = keep; } } restore{ctx, ctx->stream};
+        ctx->stream = ctx->aux;
+        return f();
+    }
+    int mark();                            // "side done": what the auxiliary stream holds now
+    int join();                            // the context's stream waits for the mark
+    int post(void *h_dst, const void *d_src, size_t bytes);   // behind the mark: a copy to pinned host memory, then "landed"
+    int landed();                          // the host waits for that copy (and for nothing behind it)
+private:
+    fmk_ctx *ctx;
+    bool forked = false, parked = false, joined = false, posted = false;
+};
 
 #ifdef __HIPCC__
 // ---------------------------------------------------------------------------------------

@@ -1654,35 +1654,29 @@ int fmk_footprints_fill_classes(fmk_ctx *ctx, const double *d_price, const void 
     // The classes take disjoint bars, and on a tape whose bars differ in length the first class (<= 128 levels) does nearly all the
     // work while each wider one walks a few long bars with little parallelism (lognormal one-minute bars: 5.4 ms + six launches of
     // 0.15 .. 0.36 ms one after the other).  So the wider LDS classes run BESIDE the first one, on the context's auxiliary stream
-    // (round 4).
-    hipStream_t side = nullptr;
+    // (round 4).  No fmk_free between fork and join (fp_launch allocates nothing): fork(false).
     {
-        if (max_levels > LMAX[0] && lmin_start == 0 && fmk_ctx_aux(ctx) == FMK_OK) {
-            side = ctx->aux;
-            hipError_t e = hipEventRecord(ctx->aev[3], ctx->stream);
-            if (e == hipSuccess) e = hipStreamWaitEvent(side, ctx->aev[3], 0);
-            if (e != hipSuccess) side = nullptr;
+        FmkSide side(ctx);
+        const bool forked = max_levels > LMAX[0] && lmin_start == 0;
+        if (forked) rc = side.fork(false);
+        for (int k = 0; k < NCLS && rc == FMK_OK; ++k) {
+            if (k > 0 && max_levels <= LMAX[k - 1]) break;
+            // (the widest class of a call needs no more LDS than the call's widest bar)
+            const int lm = (k >= 3 && max_levels < LMAX[k]) ? (int)max_levels : LMAX[k];
+            if (LMAX[k] > lmin_start && LMAX[k] > lmin) {
+                hipStream_t st = (k > 0 && forked) ? side.stream() : nullptr;
+                rc = amount_is_f64
+                         ? fp_launch<true>(ctx, d_price, d_amount, d_side, d_close_idx, nb, price_tick_size, d_bar_lows,
+                                           imb_mult, d_level_offsets, lmin, lm, WPB[k], o, bad, rest, nullptr, nullptr, skip_above, skip_lmax, st)
+                         : fp_launch<false>(ctx, d_price, d_amount, d_side, d_close_idx, nb, price_tick_size, d_bar_lows,
+                                            imb_mult, d_level_offsets, lmin, lm, WPB[k], o, bad, rest, d_median, saw_long, skip_above, skip_lmax, st);
+            }
+            lmin = LMAX[k];
         }
-    }
-    for (int k = 0; k < NCLS && rc == FMK_OK; ++k) {
-        if (k > 0 && max_levels <= LMAX[k - 1]) break;
-        // (the widest class of a call needs no more LDS than the call's widest bar)
-        const int lm = (k >= 3 && max_levels < LMAX[k]) ? (int)max_levels : LMAX[k];
-        if (LMAX[k] > lmin_start && LMAX[k] > lmin) {
-            hipStream_t st = (k > 0 && side) ? side : nullptr;
-            rc = amount_is_f64
-                     ? fp_launch<true>(ctx, d_price, d_amount, d_side, d_close_idx, nb, price_tick_size, d_bar_lows,
-                                       imb_mult, d_level_offsets, lmin, lm, WPB[k], o, bad, rest, nullptr, nullptr, skip_above, skip_lmax, st)
-                     : fp_launch<false>(ctx, d_price, d_amount, d_side, d_close_idx, nb, price_tick_size, d_bar_lows,
-                                        imb_mult, d_level_offsets, lmin, lm, WPB[k], o, bad, rest, d_median, saw_long, skip_above, skip_lmax, st);
-        }
-        lmin = LMAX[k];
-    }
-    if (side) {                                                     // join: everything behind this point sees every class' results
-        hipError_t e = hipEventRecord(ctx->aev[3], side);
-        if (e == hipSuccess) e = hipStreamWaitEvent(ctx->stream, ctx->aev[3], 0);
-        if (e != hipSuccess && rc == FMK_OK) rc = fmk_set_error(ctx, FMK_E_HIP, "footprints: joining the side stream: %s", hipGetErrorString(e));
-    }
+        // join: everything behind this point sees every class' results
+        if (forked && rc == FMK_OK) rc = side.mark();
+        if (forked && rc == FMK_OK) rc = side.join();
+    }   // (an error above: the side stream is drained here, before the blocks below go back to the allocator)
     // the long bars the workgroup kernel handed back (float64 amounts in tick order): the same classes once more, in list mode
     if (wide_defer && rc == FMK_OK) {
         lmin = 0;

@@ -7,15 +7,21 @@
 // bar ends.  No atomics, no MFMA: bounded by HBM read bandwidth, 12 B/tick (f32 amounts) +
 // 8 B/bar read + 60..68 B/bar written.
 //
-// Two kernels:
-//   k_bar_ohlcv_small  bars of <= 64*NCH ticks (up to 21 chunks = 1344 ticks: every 1-minute bar of the
-//                      benchmark stream).  ALL loads of the bar are issued up front (one HBM round
-//                      trip per bar instead of one per unrolled batch), and -- when the median trade
-//                      size is requested (base.py:403) -- the amounts that are already in registers
-//                      feed the exact order-statistic search of fmk_median.h directly: the amount
-//                      column is read ONCE for OHLCV + median.
-//   k_bar_ohlcv        any bar length (unroll-4 streaming loop); with min_cnt > 0 it only takes the
-//                      bars the small kernel skipped.  Long bars get their median from k_bar_median.
+// The first pass of a call takes one of these schedules (ohlcv_plan decides from the mean bar length, the number of bars, the
+// amount type and whether the median is wanted; tests/test_ohlcv_plan.py pins the table):
+//   k_bar_ohlcv_small<.., NCH>  one wave per bar, bars of <= 64*NCH ticks, NCH = 4 / 10 / 21 (21 chunks = 1344 ticks: every
+//                      1-minute bar of the benchmark stream).  ALL loads of the bar are issued up front (one HBM round
+//                      trip per bar instead of one per unrolled batch), and -- when the median trade size is requested
+//                      (base.py:403) -- the amounts that are already in registers feed the exact order-statistic search
+//                      of fmk_median.h directly: the amount column is read ONCE for OHLCV + median.
+//   the pipelined step   k_bar_ohlcv_small<.., 21> in two launches with the time-bar indexer in two stages beside them
+//                      (fmk_time_bars_ohlcv_dev on 1-minute-sized bars, float32 amounts: ohlcv_pipelined)
+//   k_bar_ohlcv_lanes<.., TILE>  one LANE per bar, streams of <= 56 (with the median: <= 32) ticks per bar, float32 amounts
+//   k_bar_ohlcv_rows<.., 16 | 8>  sixteen / eight lanes per bar, streams of up to 210 / (with the median) 33 .. 63 ticks per bar
+// and the bars that pass leaves behind take (ohlcv_leftovers):
+//   k_bar_ohlcv_phased / k_bar_ohlcv_mid   float32 bars of 1 345 .. 16 384 ticks from lists, a wave / a workgroup per bar
+//   k_bar_ohlcv        any bar length (unroll-4 streaming loop), only the bars nobody else took; the workgroup classes of
+//                      oh_wide_launch beyond 16 384 ticks.  Long bars get their median from fmk_median_launch.
 //
 // Floating point: price*volume is rounded before it is added (-ffp-contract=off), exactly
 // like the reference; the per-bar float64 sums are accumulated lane-strided and then
@@ -1498,14 +1504,133 @@ __global__ __launch_bounds__(256) void k_bar_ohlcv_phased(const double *__restri
     }
 }
 
-static unsigned ohlcv_grid(fmk_ctx *ctx, int64_t nb)
+// ---------------------------------------------------------------------------------------------------------------------
+// The first pass of a comp_bar_ohlcv call: WHICH kernel serves the stream is decided from plain numbers (ohlcv_plan: no HIP call,
+// no context; fmk_diag_ohlcv_plan shows it without a device) and carried out by ohlcv_launch.  Mean bar length (the tick array's
+// length over the bars is an upper bound) picks the schedule; the bars longer than the plan's long_min are left to ohlcv_leftovers.
+// ---------------------------------------------------------------------------------------------------------------------
+enum OhlcvKind {
+    OHLCV_SMALL = 0,       // k_bar_ohlcv_small<.., nch>: one wave per bar, bars of <= 64 * nch ticks
+    OHLCV_LANES = 1,       // k_bar_ohlcv_lanes<.., tile>: one LANE per bar, bars of <= 64 ticks (float32 amounts)
+    OHLCV_ROWS = 2,        // k_bar_ohlcv_rows<.., lanes>: 16 / 8 lanes per bar, bars of <= 256 / 128 ticks (float32 amounts)
+    OHLCV_PIPELINED = 3    // k_bar_ohlcv_small<.., 21> twice, the time-bar indexer in two stages beside it (ohlcv_pipelined)
+};
+struct OhlcvPlan {
+    int kind;
+    int tile;              // OHLCV_LANES: ticks per tile
+    int lanes;             // OHLCV_ROWS: lanes per bar
+    int nch;               // OHLCV_SMALL / OHLCV_PIPELINED: the kernel's chunk cap
+    unsigned grid, block;  // of the first kernel (OHLCV_PIPELINED: of the first stage's launch)
+    int64_t long_min;      // bars of more ticks are left behind
+    int64_t first_stage;   // OHLCV_PIPELINED: bars of the first stage
+};
+constexpr int64_t OHLCV_MIN_BARS = 64;          // fewer bars: the wave-per-bar kernels whatever the mean
+constexpr int64_t OHLCV_MID_MAX = 210;          // mean ticks per bar up to which the 65..256-tick instantiations serve the stream
+constexpr int64_t OHLCV_MID2_MAX = 600;         // ... and the <= 640-tick instantiation; above: the 1-minute schedule
+constexpr int64_t OHLCV_ROWS_MIN = 57;          // mean ticks per bar from which rows replace the lane schedule (without the median)
+// With the median: eight lanes per bar (bars of <= 128 ticks) serve streams of 33 .. 63 ticks per bar,
+// sixteen lanes per bar from 64 (profiles/r04_short_bars.txt: 5.8 / 5.3 / 4.9 / 4.3 ms at 34 / 40 / 46 / 60 ticks against the lane
+// schedule's 7.0 / 6.6 / 7.0 / 8.9; the half rows are ahead of the rows up to ~100 ticks on equal bars, but a stream's longer bars
+// -- twice its mean -- must still fit the schedule: 63 x 2 <= 128).  Without the median the lane schedule stays ahead up to 56.
+// (Four lanes per bar, sixteen bars per wave, was measured too: 6.9 / 6.2 / 5.4 ms at 20 / 26 / 34 ticks -- behind; not dispatched.)
+constexpr int64_t OHLCV_HALF_MIN = 33;
+// bars of 45 .. 64 ticks fill a 1 024-tick tile with 16 .. 22 bars only: a 2 048-tick tile for those -- 50 / 60-tick bars 7.4 / 9.5 ->
+// 6.7 / 8.9 ms per 1e9 ticks, 34 / 40-tick bars are better off with the small tile (7.0 / 6.6 against 7.9 / 7.4) (profiles/r04_short_bars.txt)
+constexpr int64_t OHLCV_BIG_TILE_MIN = 45;
+constexpr int64_t OHLCV_PIPE_SPLIT = 8;         // 1 / share of the bars in the first stage of the pipelined time-bar step
+constexpr int64_t OHLCV_PIPE_MIN_STAGE = 4096;  // bars in the first stage from which the step is pipelined (FMK_TB_PIPE_MIN_STAGE)
+
+// workgroups of a grid-stride launch: `blocks`, at most per_cu per CU, at least one
+static unsigned ohlcv_capped(int64_t blocks, int n_cu, int per_cu)
 {
-    int64_t blocks = fmk_ceil_div(nb, 4);
-    const int per_cu = 64;                  // workgroups per CU in the grid
-    int64_t cap = (int64_t)ctx->n_cu * per_cu;   // grid-stride beyond this
+    const int64_t cap = (int64_t)n_cu * per_cu;
     if (blocks > cap) blocks = cap;
     if (blocks < 1) blocks = 1;
     return (unsigned)blocks;
+}
+
+static unsigned ohlcv_grid(fmk_ctx *ctx, int64_t nb) { return ohlcv_capped(fmk_ceil_div(nb, 4), ctx->n_cu, 64); }
+
+static OhlcvPlan ohlcv_plan(int64_t n, int64_t nb, bool amount_is_f64, bool want_median, bool time_bar_fused, int n_cu,
+                            int64_t pipe_min_stage)
+{
+    const int64_t mean = n / nb;
+    const bool f32 = !amount_is_f64, many = nb >= OHLCV_MIN_BARS;
+    const int64_t rows_from = want_median ? FMK_PACKED_MAX_MEAN : OHLCV_ROWS_MIN;
+    // launch bounds measured on MI355X: forcing >4 waves/SIMD on the fused-median kernel makes the compiler
+    // serialise the up-front loads (2.7 ms -> 3.5..4.3 ms at N = 1e9); 4 waves/SIMD (102 VGPRs) is the optimum.
+    OhlcvPlan pl{OHLCV_SMALL, 0, 0, FMK_SMALL_NCH, ohlcv_capped(fmk_ceil_div(nb, 4), n_cu, 64), 256, 64 * FMK_SMALL_NCH, 0};
+    if (f32 && time_bar_fused && mean > OHLCV_MID2_MAX && nb / OHLCV_PIPE_SPLIT >= pipe_min_stage && pipe_min_stage >= 256) {
+        pl.kind = OHLCV_PIPELINED;
+        pl.first_stage = (nb / OHLCV_PIPE_SPLIT) & ~(int64_t)255;
+        pl.grid = ohlcv_capped(fmk_ceil_div(pl.first_stage, 4), n_cu, 64);
+    } else if (f32 && want_median && many && mean >= OHLCV_HALF_MIN && mean < rows_from) {
+        pl.kind = OHLCV_ROWS; pl.lanes = 8; pl.nch = 0; pl.long_min = 128;
+        pl.grid = ohlcv_capped(fmk_ceil_div(fmk_ceil_div(nb, 8), OHR_WAVES), n_cu, 32); pl.block = 64 * OHR_WAVES;
+    } else if (f32 && many && mean <= FMK_PACKED_MAX_MEAN && mean < rows_from) {
+        // several whole bars per LANE below FMK_PACKED_MAX_MEAN ticks per bar, one bar per wave above
+        pl.kind = OHLCV_LANES; pl.tile = mean >= OHLCV_BIG_TILE_MIN ? 2048 : 1024; pl.nch = 0; pl.long_min = 64;
+        pl.grid = ohlcv_capped(fmk_ceil_div(fmk_ceil_div(nb, 64), 2), n_cu, 96); pl.block = 128;
+    } else if (f32 && many && mean <= OHLCV_MID_MAX) {
+        // streams of 65..256-tick bars (float32 amounts): sixteen lanes per bar, four bars per wave; longer bars are left
+        pl.kind = OHLCV_ROWS; pl.lanes = 16; pl.nch = 0; pl.long_min = 256;
+        pl.grid = ohlcv_capped(fmk_ceil_div(fmk_ceil_div(nb, 4), OHR_WAVES), n_cu, 32); pl.block = 64 * OHR_WAVES;
+    } else if (mean <= OHLCV_MID_MAX) {
+        // streams of 65..256-tick bars: the instantiation without the long classes (eight waves per SIMD); longer bars are left
+        pl.nch = 4; pl.long_min = 256; pl.grid = ohlcv_capped(fmk_ceil_div(nb, 4), n_cu, 128);
+    } else if (mean <= OHLCV_MID2_MAX) {
+        // ... and of 257..640-tick bars: size classes up to 10 chunks (six waves per SIMD)
+        pl.nch = 10; pl.long_min = 640; pl.grid = ohlcv_capped(fmk_ceil_div(nb, 4), n_cu, 96);
+    }
+    return pl;
+}
+
+extern "C" int fmk_diag_ohlcv_plan(int64_t n, int64_t n_bars, int amount_is_f64, int want_median, int time_bar_fused, int n_cu,
+                                   int64_t pipe_min_stage, int64_t *out8)
+{
+    if (n < 1 || n_bars < 1 || n_cu < 1 || !out8) return fmk_set_error(nullptr, FMK_E_ARG, "ohlcv_plan: bad arguments");
+    const OhlcvPlan pl = ohlcv_plan(n, n_bars, amount_is_f64 != 0, want_median != 0, time_bar_fused != 0, n_cu, pipe_min_stage);
+    const int64_t v[8] = {pl.kind, pl.tile, pl.lanes, pl.nch, pl.grid, pl.block, pl.long_min, pl.first_stage};
+    memcpy(out8, v, sizeof v);
+    return FMK_OK;
+}
+
+// The one place where a plan becomes a kernel instantiation (`grid`: the plan's, or the second stage's of the pipelined step).
+template <bool AF64, bool MEDIAN>
+static void ohlcv_first_pass(const OhlcvPlan &pl, unsigned grid, hipStream_t st, const double *p, const void *a, const int64_t *ci,
+                             int64_t nb, int64_t n, int *saw_long, const OhlcvOut &o)
+{
+    if constexpr (!AF64) {
+        const float *af = (const float *)a;
+        if (pl.kind == OHLCV_ROWS && pl.lanes == 8) {                // (planned with the median only)
+            if constexpr (MEDIAN) k_bar_ohlcv_rows<true, 8><<<grid, pl.block, 0, st>>>(p, af, ci, nb, n, saw_long, o);
+            return;
+        }
+        if (pl.kind == OHLCV_ROWS) { k_bar_ohlcv_rows<MEDIAN><<<grid, pl.block, 0, st>>>(p, af, ci, nb, n, saw_long, o); return; }
+        if (pl.kind == OHLCV_LANES) {
+            if (pl.tile == 2048) k_bar_ohlcv_lanes<MEDIAN, 2048><<<grid, pl.block, 0, st>>>(p, af, ci, nb, n, saw_long, o);
+            else k_bar_ohlcv_lanes<MEDIAN, 1024><<<grid, pl.block, 0, st>>>(p, af, ci, nb, n, saw_long, o);
+            return;
+        }
+    }
+    if (pl.nch == 4) k_bar_ohlcv_small<AF64, MEDIAN, 4><<<grid, pl.block, 0, st>>>(p, a, ci, nb, n, saw_long, o);
+    else if (pl.nch == 10) k_bar_ohlcv_small<AF64, MEDIAN, 10><<<grid, pl.block, 0, st>>>(p, a, ci, nb, n, saw_long, o);
+    else k_bar_ohlcv_small<AF64, MEDIAN><<<grid, pl.block, 0, st>>>(p, a, ci, nb, n, saw_long, o);
+}
+
+// float32 bars of 1 345 .. 2 048, .. 3 072, .. 4 096, .. 6 144 ticks: a wave per bar with 32 / 48 / 64 / 96 key registers; 6 145 .. 8 192
+// and .. 16 384: a workgroup per bar (the lists of fmk_long_bar_lists, in this order)
+static const int64_t OHLCV_LIST_EDGE[7] = {OHM_MIN, 2048, 3072, 4096, 6144, 8192, OHM_MAX};
+template <bool MEDIAN>
+static void ohlcv_list_kernels(unsigned g, hipStream_t st, const double *p, const float *af, const int64_t *ci, int64_t *const *list,
+                               const int *go, const OhlcvOut &o)
+{
+    k_bar_ohlcv_phased<MEDIAN, 32, 16><<<g, 256, 0, st>>>(p, af, ci, list[0], go, o);
+    k_bar_ohlcv_phased<MEDIAN, 48, 8><<<g, 256, 0, st>>>(p, af, ci, list[1], go, o);
+    k_bar_ohlcv_phased<MEDIAN, 64, 8><<<g, 256, 0, st>>>(p, af, ci, list[2], go, o);
+    k_bar_ohlcv_phased<MEDIAN, 96, 8><<<g, 256, 0, st>>>(p, af, ci, list[3], go, o);
+    k_bar_ohlcv_mid<MEDIAN, 32, 256><<<g, 256, 0, st>>>(p, af, ci, list[4], go, o);
+    k_bar_ohlcv_mid<MEDIAN, 32, 512><<<g / 2, 512, 0, st>>>(p, af, ci, list[5], go, o);
 }
 
 // What the first kernel of a comp_bar_ohlcv call left behind (bars longer than `long_min` ticks; `saw_long`: its flag)
@@ -1513,45 +1638,26 @@ template <bool AF64>
 static int ohlcv_leftovers(fmk_ctx *ctx, const double *p, const void *a, const int64_t *ci, int64_t nb, int64_t n,
                            const OhlcvOut &o, int *saw_long, int64_t long_min, unsigned grid)
 {
-    // long bars (if any): the generic kernels exit at once when the flag is clear.  float32 bars of 1 345 .. 8 192 ticks: one pass by
-    // a workgroup each, median included
+    // long bars (if any): the generic kernels exit at once when the flag is clear.  float32 bars of 1 345 .. 16 384 ticks: one pass by
+    // a wave or a workgroup each, median included
     int64_t skip_lo = 0, skip_hi = 0;
     if constexpr (!AF64) {
-        {
-            skip_lo = OHM_MIN;
-            skip_hi = OHM_MAX;
-            // 1 345 .. 2 048, .. 3 072, .. 4 096, .. 6 144 ticks: a wave per bar with 32 / 48 / 64 / 96 key registers; 6 145 .. 8 192: a workgroup per bar
-            constexpr int NL = 6;
-            int64_t *list[NL] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-            static const int64_t edge[NL + 1] = {OHM_MIN, 2048, 3072, 4096, 6144, 8192, OHM_MAX};
-            int rc = fmk_long_bar_lists(ctx, ci, nb, n, NL, edge, saw_long, list);      // (one pass, one allocation: list[0] owns it)
-            // measured per 1e9 ticks, ohlcv + median (profiles/r03_median_humps.txt): 4 400 / 5 200 / 6 000-tick bars 3.6 / 3.4 / 3.1 ms
-            // with 96 key registers per lane against 5.1 / 4.5 / 4.0 ms by the workgroup kernel; 7 000 / 8 000-tick bars 5.5 / 5.2 ms
-            // with 128 key registers (spills) against 3.6 / 3.3 ms by the workgroup kernel
-            if (rc == FMK_OK) {
-                const float *af = (const float *)a;
-                const unsigned g = (unsigned)(ctx->n_cu * 8);
-                if (o.median) {
-                    k_bar_ohlcv_phased<true, 32, 16><<<g, 256, 0, ctx->stream>>>(p, af, ci, list[0], saw_long, o);
-                    k_bar_ohlcv_phased<true, 48, 8><<<g, 256, 0, ctx->stream>>>(p, af, ci, list[1], saw_long, o);
-                    k_bar_ohlcv_phased<true, 64, 8><<<g, 256, 0, ctx->stream>>>(p, af, ci, list[2], saw_long, o);
-                    k_bar_ohlcv_phased<true, 96, 8><<<g, 256, 0, ctx->stream>>>(p, af, ci, list[3], saw_long, o);
-                    k_bar_ohlcv_mid<true, 32, 256><<<g, 256, 0, ctx->stream>>>(p, af, ci, list[4], saw_long, o);
-                    k_bar_ohlcv_mid<true, 32, 512><<<g / 2, 512, 0, ctx->stream>>>(p, af, ci, list[5], saw_long, o);
-                } else {
-                    k_bar_ohlcv_phased<false, 32, 16><<<g, 256, 0, ctx->stream>>>(p, af, ci, list[0], saw_long, o);
-                    k_bar_ohlcv_phased<false, 48, 8><<<g, 256, 0, ctx->stream>>>(p, af, ci, list[1], saw_long, o);
-                    k_bar_ohlcv_phased<false, 64, 8><<<g, 256, 0, ctx->stream>>>(p, af, ci, list[2], saw_long, o);
-                    k_bar_ohlcv_phased<false, 96, 8><<<g, 256, 0, ctx->stream>>>(p, af, ci, list[3], saw_long, o);
-                    k_bar_ohlcv_mid<false, 32, 256><<<g, 256, 0, ctx->stream>>>(p, af, ci, list[4], saw_long, o);
-                    k_bar_ohlcv_mid<false, 32, 512><<<g / 2, 512, 0, ctx->stream>>>(p, af, ci, list[5], saw_long, o);
-                }
-            }
-            const hipError_t le = hipGetLastError();
-            if (list[0]) (void)fmk_free(ctx, list[0]);
-            FMK_TRY(rc);
-            FMK_HIP(ctx, le);
+        skip_lo = OHM_MIN;
+        skip_hi = OHM_MAX;
+        int64_t *list[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+        const int rc = fmk_long_bar_lists(ctx, ci, nb, n, 6, OHLCV_LIST_EDGE, saw_long, list);   // (one pass, one allocation: list[0] owns it)
+        // measured per 1e9 ticks, ohlcv + median (profiles/r03_median_humps.txt): 4 400 / 5 200 / 6 000-tick bars 3.6 / 3.4 / 3.1 ms
+        // with 96 key registers per lane against 5.1 / 4.5 / 4.0 ms by the workgroup kernel; 7 000 / 8 000-tick bars 5.5 / 5.2 ms
+        // with 128 key registers (spills) against 3.6 / 3.3 ms by the workgroup kernel
+        if (rc == FMK_OK) {
+            const unsigned g = (unsigned)(ctx->n_cu * 8);
+            if (o.median) ohlcv_list_kernels<true>(g, ctx->stream, p, (const float *)a, ci, list, saw_long, o);
+            else ohlcv_list_kernels<false>(g, ctx->stream, p, (const float *)a, ci, list, saw_long, o);
         }
+        const hipError_t le = hipGetLastError();
+        if (list[0]) (void)fmk_free(ctx, list[0]);
+        FMK_TRY(rc);
+        FMK_HIP(ctx, le);
     }
     k_bar_ohlcv<AF64><<<grid, 256, 0, ctx->stream>>>(p, a, ci, nb, n, long_min, saw_long, o, skip_lo, skip_hi);
     int wide_median_done = 0;
@@ -1568,165 +1674,80 @@ static int ohlcv_leftovers(fmk_ctx *ctx, const double *p, const void *a, const i
     return FMK_OK;
 }
 
+// ---- the pipelined time-bar step (round 4; float32 amounts, the 1-minute schedule).  The indexer (0.13 ms: sample table + one
+// search per clock edge, bound by random line fetches) used to stand in front of a 2.2 ms kernel that cannot start without it, and the
+// call ended with a read-back of the long-bar flag (memset + copy + host wait + the host's way back into the next call: another
+// 0.05 ms of idle device per step; rocprofv3 timeline in profiles/r04_step_timeline.txt).  Now: sample table and the edges of the
+// first 1/8 of the bars on the context's stream (~25 us), OHLCV + median of those bars, and BESIDE that launch the remaining edges
+// on the auxiliary stream; the second OHLCV launch waits for them by event.  Both index stages also take the census (is any bar
+// longer than 1 344 ticks?), so the flag reaches the host while the first OHLCV launch is still running: the call decides about the
+// leftover passes and returns without ever waiting for a kernel it launched.
+static int ohlcv_pipelined(fmk_ctx *ctx, const OhlcvPlan &pl, const double *p, const void *a, int64_t nb, int64_t n, const OhlcvOut &o,
+                           const TbFuse *tb)
+{
+    const int idx_bpc = 2;                 // workgroups per CU of the second index stage (0: no cap)
+    int *saw_long = &ctx->d_mail->ohlcv.saw_long, *h_saw = &ctx->h_mail->ohlcv.saw_long;
+    const int64_t *ci = tb->idx, *coarse = nullptr;
+    int64_t m = 0;
+    const int64_t ne = nb + 1, ka = pl.first_stage;
+    {
+        FmkSide side(ctx);                 // (no fmk_free between fork and join: nothing to park.  An error return below drains the side)
+        FMK_TRY(fmk_time_bar_coarse_launch(ctx, tb->ts, n, &coarse, &m, saw_long));          // (also clears the flag)
+        FMK_TRY(fmk_time_bar_index_stage(ctx, ctx->stream, tb->ts, n, tb->e0, tb->d, ne, coarse, m, 0, ka + 1, tb->clock, tb->idx,
+                                         saw_long, pl.long_min, 0));
+        FMK_TRY(side.fork(false));
+        FMK_TRY(fmk_time_bar_index_stage(ctx, side.stream(), tb->ts, n, tb->e0, tb->d, ne, coarse, m, ka + 1, ne, tb->clock, tb->idx,
+                                         saw_long, pl.long_min, (int64_t)ctx->n_cu * idx_bpc));
+        FMK_TRY(side.mark());
+        // (also in enqueue-only mode: this wait ends when the index stages do, ~0.1 ms into a 2 ms launch -- the device never idles
+        //  for it, and it saves the ~36 empty launches of the leftover passes, 0.25 ms per step of the sharded path)
+        FMK_TRY(side.post(h_saw, saw_long, sizeof(int)));
+        for (int stage = 0; stage < 2; ++stage) {
+            const int64_t b0 = stage ? ka : 0, cnt = stage ? nb - ka : ka;
+            OhlcvOut q = o;
+            q.open += b0; q.high += b0; q.low += b0; q.close += b0; q.vol += b0; q.vwap += b0; q.trades += b0;
+            if (q.median) q.median += b0;
+            if (stage) FMK_TRY(side.join());
+            const int sl = (ctx->profile_on) ? (ctx->profile_n++ & (FMK_PROFILE_SLOTS - 1)) : -1;      // each launch of the dominant kernel on its own
+            if (sl >= 0) FMK_HIP(ctx, hipEventRecord(ctx->kev[sl][0], ctx->stream));
+            const unsigned g = stage ? ohlcv_grid(ctx, cnt) : pl.grid;
+            if (o.median) ohlcv_first_pass<false, true>(pl, g, ctx->stream, p, a, ci + b0, cnt, n, saw_long, q);
+            else ohlcv_first_pass<false, false>(pl, g, ctx->stream, p, a, ci + b0, cnt, n, saw_long, q);
+            FMK_LAUNCH_CHECK(ctx);
+            if (sl >= 0) FMK_HIP(ctx, hipEventRecord(ctx->kev[sl][1], ctx->stream));
+        }
+        FMK_TRY(side.landed());            // the index stages' census: long before the kernels end
+    }
+    if (*h_saw == 0) return FMK_OK;
+    return ohlcv_leftovers<false>(ctx, p, a, ci, nb, n, o, saw_long, pl.long_min, ohlcv_grid(ctx, nb));
+}
+
+// tb: the close indices are not there yet (fmk_time_bars_ohlcv_dev) -- the 1-minute schedule pipelines the indexer with the bar
+// kernel in two stages (ohlcv_pipelined), every other schedule runs the separate indexer first
 template <bool AF64>
 static int ohlcv_launch(fmk_ctx *ctx, const double *p, const void *a, const int64_t *ci, int64_t nb, int64_t n,
-                        const OhlcvOut &o_in, int variant, const TbFuse *tb = nullptr)
+                        const OhlcvOut &o_in, const TbFuse *tb = nullptr)
 {
     OhlcvOut o = o_in;
-    const unsigned grid = ohlcv_grid(ctx, nb);
-    // tb: the close indices are not there yet (fmk_time_bars_ohlcv_dev) -- the 1-minute schedule pipelines the indexer with the bar
-    // kernel in two stages, every other schedule runs the separate indexer first
-    int64_t pipe_ka = 0;                     // > 0: bars [0, pipe_ka) are the first stage of the pipelined time-bar step
+    const char *msv = tb ? getenv("FMK_TB_PIPE_MIN_STAGE") : nullptr;   // developer knob (tests), read on every time-bar call
+    const OhlcvPlan pl = ohlcv_plan(n, nb, AF64, o.median != nullptr, tb != nullptr, ctx->n_cu, msv ? atoll(msv) : OHLCV_PIPE_MIN_STAGE);
     if (tb) {
-        const int mid2 = 600;
-        // PIPELINED time-bar step (the default for the 1-minute schedule, float32 amounts): the indexer in two stages -- see below
-        const int split = 8;               // 1 / share of the bars in the first stage (0: off)
-        const char *msv = getenv("FMK_TB_PIPE_MIN_STAGE");            // developer knob (tests): bars in the first stage from which the
-        const int64_t min_stage = msv ? atoll(msv) : 4096;            // step is pipelined (read on every call)
-        if (!AF64 && split >= 2 && variant != 0 && n / nb > mid2 && nb / split >= min_stage && min_stage >= 256) {
-            pipe_ka = (nb / split) & ~(int64_t)255;
-        } else
-            FMK_TRY(fmk_time_bar_indexer_dev(ctx, tb->ts, n, tb->e0, tb->d, nb + 1, tb->clock, tb->idx));
+        if (pl.kind != OHLCV_PIPELINED) FMK_TRY(fmk_time_bar_indexer_dev(ctx, tb->ts, n, tb->e0, tb->d, nb + 1, tb->clock, tb->idx));
         ci = tb->idx;
     }
     if (AF64) {   // redo list of near-tie volume sums (fmk_f32tie.h); nothing else here uses the context scratch
         FMK_TRY(fmk_scratch(ctx, (size_t)(nb + 32) * 8, (void **)&o.vol_redo));
         FMK_HIP(ctx, hipMemsetAsync(o.vol_redo, 0, 8, ctx->stream));
     }
+    if constexpr (!AF64)
+        if (pl.kind == OHLCV_PIPELINED) return ohlcv_pipelined(ctx, pl, p, a, nb, n, o, tb);
     // time the dominant launch only (the one-bar boundary launch of a sharded step is not it)
-    const int slot = (ctx->profile_on && nb >= 64 && pipe_ka == 0) ? (ctx->profile_n++ & (FMK_PROFILE_SLOTS - 1)) : -1;
+    const int slot = (ctx->profile_on && nb >= 64) ? (ctx->profile_n++ & (FMK_PROFILE_SLOTS - 1)) : -1;
     if (slot >= 0) FMK_HIP(ctx, hipEventRecord(ctx->kev[slot][0], ctx->stream));
-    if (variant == 0) {   // generic streaming kernel only (+ stand-alone median)
-        k_bar_ohlcv<AF64><<<grid, 256, 0, ctx->stream>>>(p, a, ci, nb, n, 0, nullptr, o);
-        FMK_LAUNCH_CHECK(ctx);
-        if (slot >= 0) FMK_HIP(ctx, hipEventRecord(ctx->kev[slot][1], ctx->stream));
-        FMK_TRY(oh_wide_launch<AF64>(ctx, p, a, ci, nb, n, nullptr, o));
-        if (AF64) {
-            k_bar_vol_redo<<<grid < 4096 ? grid : 4096, 256, 0, ctx->stream>>>((const double *)a, ci, o.vol, o.vol_redo);
-            FMK_LAUNCH_CHECK(ctx);
-        }
-        if (o.median) return fmk_median_launch(ctx, a, AF64, ci, nb, 0, nullptr, o.median, n);
-        return FMK_OK;
-    }
-    if constexpr (!AF64) {
-        if (pipe_ka > 0) {
-            // ---- the pipelined time-bar step (round 4).  The indexer (0.13 ms: sample table + one search per clock edge, bound by
-            // random line fetches) used to stand in front of a 2.2 ms kernel that cannot start without it, and the call ended with a
-            // read-back of the long-bar flag (memset + copy + host wait + the host's way back into the next call: another 0.05 ms
-            // of idle device per step; rocprofv3 timeline in profiles/r04_step_timeline.txt).  Now: sample table and the edges of
-            // the first 1/8 of the bars on the context's stream (~25 us), OHLCV + median of those bars, and BESIDE that launch the
-            // remaining edges on the auxiliary stream; the second OHLCV launch waits for them by event.  Both index stages also take
-            // the census (is any bar longer than 1 344 ticks?), so the flag reaches the host while the first OHLCV launch is still
-            // running: the call decides about the leftover passes and returns without ever waiting for a kernel it launched.
-            FMK_TRY(fmk_ctx_aux(ctx));
-            const int idx_bpc = 2;         // workgroups per CU of the second index stage (0: no cap)
-            int *saw_long = &ctx->d_mail->ohlcv.saw_long;
-            const int64_t *coarse = nullptr;
-            int64_t m = 0;
-            const int64_t ne = nb + 1, long_min = 64 * FMK_SMALL_NCH;
-            FMK_TRY(fmk_time_bar_coarse_launch(ctx, tb->ts, n, &coarse, &m, saw_long));          // (also clears the flag)
-            FMK_TRY(fmk_time_bar_index_stage(ctx, ctx->stream, tb->ts, n, tb->e0, tb->d, ne, coarse, m, 0, pipe_ka + 1, tb->clock,
-                                             tb->idx, saw_long, long_min, 0));
-            FMK_HIP(ctx, hipEventRecord(ctx->aev[0], ctx->stream));
-            FMK_HIP(ctx, hipStreamWaitEvent(ctx->aux, ctx->aev[0], 0));
-            FMK_TRY(fmk_time_bar_index_stage(ctx, ctx->aux, tb->ts, n, tb->e0, tb->d, ne, coarse, m, pipe_ka + 1, ne, tb->clock,
-                                             tb->idx, saw_long, long_min, (int64_t)ctx->n_cu * idx_bpc));
-            FMK_HIP(ctx, hipEventRecord(ctx->aev[1], ctx->aux));
-            // (also in enqueue-only mode: this wait ends when the index stages do, ~0.1 ms into a 2 ms launch -- the device never idles
-            //  for it, and it saves the ~36 empty launches of the leftover passes, 0.25 ms per step of the sharded path)
-            int *h_saw = &ctx->h_mail->ohlcv.saw_long;
-            FMK_HIP(ctx, hipMemcpyAsync(h_saw, saw_long, sizeof(int), hipMemcpyDeviceToHost, ctx->aux));
-            FMK_HIP(ctx, hipEventRecord(ctx->aev[2], ctx->aux));
-            for (int stage = 0; stage < 2; ++stage) {
-                const int64_t b0 = stage ? pipe_ka : 0, cnt = stage ? nb - pipe_ka : pipe_ka;
-                OhlcvOut q = o;
-                q.open += b0; q.high += b0; q.low += b0; q.close += b0; q.vol += b0; q.vwap += b0; q.trades += b0;
-                if (q.median) q.median += b0;
-                if (stage) FMK_HIP(ctx, hipStreamWaitEvent(ctx->stream, ctx->aev[1], 0));
-                const int sl = (ctx->profile_on) ? (ctx->profile_n++ & (FMK_PROFILE_SLOTS - 1)) : -1;      // each launch of the dominant kernel on its own
-                if (sl >= 0) FMK_HIP(ctx, hipEventRecord(ctx->kev[sl][0], ctx->stream));
-                const unsigned g = ohlcv_grid(ctx, cnt);
-                if (!o.median) k_bar_ohlcv_small<AF64, false><<<g, 256, 0, ctx->stream>>>(p, a, ci + b0, cnt, n, saw_long, q);
-                else k_bar_ohlcv_small<AF64, true><<<g, 256, 0, ctx->stream>>>(p, a, ci + b0, cnt, n, saw_long, q);
-                FMK_LAUNCH_CHECK(ctx);
-                if (sl >= 0) FMK_HIP(ctx, hipEventRecord(ctx->kev[sl][1], ctx->stream));
-            }
-            {
-                FMK_HIP(ctx, hipEventSynchronize(ctx->aev[2]));          // the index stages' census: long before the kernels end
-                if (*h_saw == 0) return FMK_OK;
-            }
-            return ohlcv_leftovers<AF64>(ctx, p, a, ci, nb, n, o, saw_long, 64 * FMK_SMALL_NCH, grid);
-        }
-    }
-    // small bars: all loads up front (+ fused median); long bars: generic kernels on the rest
-    // launch bounds measured on MI355X: forcing >4 waves/SIMD on the fused-median kernel makes the compiler
-    // serialise the up-front loads (2.7 ms -> 3.5..4.3 ms at N = 1e9); 4 waves/SIMD (102 VGPRs) is the optimum.
-    int *saw_long = &ctx->d_mail->ohlcv.saw_long;            // set by the small kernel iff a long bar exists
+    int *saw_long = &ctx->d_mail->ohlcv.saw_long;            // set by the first kernel iff it left a bar behind
     FMK_HIP(ctx, hipMemsetAsync(saw_long, 0, sizeof(int), ctx->stream));
-    // mean bar length (the tick array's length over the bars is an upper bound) picks the schedule: several whole bars per
-    // LANE below FMK_PACKED_MAX_MEAN ticks per bar (k_bar_ohlcv_lanes), one bar per wave above
-    const int packed_max = FMK_PACKED_MAX_MEAN;              // (0 disables the packed schedule)
-    int64_t long_min = 64 * FMK_SMALL_NCH;
-    const int mid_max = 210;                 // mean ticks per bar up to which the 65..256-tick instantiation serves the stream
-    const int mid2_max = 600;                // ... and the <= 640-tick instantiation
-    const int rows_on = 1;                   // the sixteen-lanes-per-bar schedule
-    const int rows_min = 57;                 // mean ticks per bar from which rows replace the lane schedule (without the median)
-    // With the median: eight lanes per bar (bars of <= 128 ticks) serve streams of 33 .. 63 ticks per bar,
-    // sixteen lanes per bar from 64 (profiles/r04_short_bars.txt: 5.8 / 5.3 / 4.9 / 4.3 ms at 34 / 40 / 46 / 60 ticks against the lane
-    // schedule's 7.0 / 6.6 / 7.0 / 8.9; the half rows are ahead of the rows up to ~100 ticks on equal bars, but a stream's longer bars
-    // -- twice its mean -- must still fit the schedule: 63 x 2 <= 128).  Without the median the lane schedule stays ahead up to 56.
-    // (Four lanes per bar, sixteen bars per wave, was measured too: 6.9 / 6.2 / 5.4 ms at 20 / 26 / 34 ticks -- behind; not dispatched.)
-    const int half_min = 33;
-    const int64_t rows_from = o.median ? 64 : rows_min;
-    if (!AF64 && rows_on && o.median && half_min > 0 && nb >= 64 && n / nb >= half_min && n / nb < rows_from) {
-        if constexpr (!AF64) {
-            int64_t blocks = fmk_ceil_div(fmk_ceil_div(nb, 8), OHR_WAVES);
-            const int64_t cap = (int64_t)ctx->n_cu * 32;
-            if (blocks > cap) blocks = cap;
-            k_bar_ohlcv_rows<true, 8><<<(unsigned)blocks, 64 * OHR_WAVES, 0, ctx->stream>>>(p, (const float *)a, ci, nb, n, saw_long, o);
-        }
-        long_min = 128;
-    } else if (!AF64 && nb >= 64 && n / nb <= packed_max && !(rows_on && n / nb >= rows_from)) {
-        int64_t blocks = fmk_ceil_div(fmk_ceil_div(nb, 64), 2);
-        const int64_t cap = (int64_t)ctx->n_cu * 96;
-        if (blocks > cap) blocks = cap;
-        // bars of 45 .. 64 ticks fill a 1 024-tick tile with 16 .. 22 bars only: a 2 048-tick tile for those -- 50 / 60-tick bars 7.4 / 9.5 ->
-        // 6.7 / 8.9 ms per 1e9 ticks, 34 / 40-tick bars are better off with the small tile (7.0 / 6.6 against 7.9 / 7.4) (profiles/r04_short_bars.txt)
-        if (n / nb > 44) {
-            if (!o.median) k_bar_ohlcv_lanes<false, 2048><<<(unsigned)blocks, 128, 0, ctx->stream>>>(p, (const float *)a, ci, nb, n, saw_long, o);
-            else k_bar_ohlcv_lanes<true, 2048><<<(unsigned)blocks, 128, 0, ctx->stream>>>(p, (const float *)a, ci, nb, n, saw_long, o);
-        } else
-        if (!o.median) k_bar_ohlcv_lanes<false, 1024><<<(unsigned)blocks, 128, 0, ctx->stream>>>(p, (const float *)a, ci, nb, n, saw_long, o);
-        else k_bar_ohlcv_lanes<true, 1024><<<(unsigned)blocks, 128, 0, ctx->stream>>>(p, (const float *)a, ci, nb, n, saw_long, o);
-        long_min = 64;
-    } else if (!AF64 && rows_on && nb >= 64 && n / nb <= mid_max) {
-        // streams of 65..256-tick bars (float32 amounts): sixteen lanes per bar, four bars per wave; longer bars are left
-        if constexpr (!AF64) {
-            int64_t blocks = fmk_ceil_div(fmk_ceil_div(nb, 4), OHR_WAVES);
-            const int64_t cap = (int64_t)ctx->n_cu * 32;
-            if (blocks > cap) blocks = cap;
-            if (!o.median) k_bar_ohlcv_rows<false><<<(unsigned)blocks, 64 * OHR_WAVES, 0, ctx->stream>>>(p, (const float *)a, ci, nb, n, saw_long, o);
-            else k_bar_ohlcv_rows<true><<<(unsigned)blocks, 64 * OHR_WAVES, 0, ctx->stream>>>(p, (const float *)a, ci, nb, n, saw_long, o);
-        }
-        long_min = 256;
-    } else if (n / nb <= mid_max) {
-        // streams of 65..256-tick bars: the instantiation without the long classes (eight waves per SIMD); longer bars are left
-        int64_t blocks = fmk_ceil_div(nb, 4);
-        const int64_t cap = (int64_t)ctx->n_cu * 128;
-        if (blocks > cap) blocks = cap;
-        if (!o.median) k_bar_ohlcv_small<AF64, false, 4><<<(unsigned)blocks, 256, 0, ctx->stream>>>(p, a, ci, nb, n, saw_long, o);
-        else k_bar_ohlcv_small<AF64, true, 4><<<(unsigned)blocks, 256, 0, ctx->stream>>>(p, a, ci, nb, n, saw_long, o);
-        long_min = 256;
-    } else if (mid_max > 0 && n / nb <= mid2_max) {
-        // ... and of 257..640-tick bars: size classes up to 10 chunks (six waves per SIMD)
-        int64_t blocks = fmk_ceil_div(nb, 4);
-        const int64_t cap = (int64_t)ctx->n_cu * 96;
-        if (blocks > cap) blocks = cap;
-        if (!o.median) k_bar_ohlcv_small<AF64, false, 10><<<(unsigned)blocks, 256, 0, ctx->stream>>>(p, a, ci, nb, n, saw_long, o);
-        else k_bar_ohlcv_small<AF64, true, 10><<<(unsigned)blocks, 256, 0, ctx->stream>>>(p, a, ci, nb, n, saw_long, o);
-        long_min = 640;
-    } else if (!o.median) k_bar_ohlcv_small<AF64, false><<<grid, 256, 0, ctx->stream>>>(p, a, ci, nb, n, saw_long, o);
-    else k_bar_ohlcv_small<AF64, true><<<grid, 256, 0, ctx->stream>>>(p, a, ci, nb, n, saw_long, o);
+    if (o.median) ohlcv_first_pass<AF64, true>(pl, pl.grid, ctx->stream, p, a, ci, nb, n, saw_long, o);
+    else ohlcv_first_pass<AF64, false>(pl, pl.grid, ctx->stream, p, a, ci, nb, n, saw_long, o);
     FMK_LAUNCH_CHECK(ctx);
     if (slot >= 0) FMK_HIP(ctx, hipEventRecord(ctx->kev[slot][1], ctx->stream));
     // Everything below serves the bars the first kernel left behind -- six list kernels, six size classes, the generic kernel, the
@@ -1735,15 +1756,14 @@ static int ohlcv_launch(fmk_ctx *ctx, const double *p, const void *a, const int6
     // one 4-byte copy and a wait for the kernel that is the call's work anyway.  fmk_ctx_set_enqueue_only(ctx, 1) (the sharded
     // step: two waits per step cost it 0.9 ms) : enqueue everything without looking.
     if constexpr (!AF64) {
-        if (n <= long_min) return FMK_OK;                          // no bar is longer than the tick array (the sharded step's boundary bar)
-        const int census_sync = 1;
-        if (census_sync && !ctx->enqueue_only) {
+        if (n <= pl.long_min) return FMK_OK;                       // no bar is longer than the tick array (the sharded step's boundary bar)
+        if (!ctx->enqueue_only) {
             int saw = 0;
             FMK_TRY(fmk_read_back(ctx, &saw, saw_long, sizeof saw));
             if (saw == 0) return FMK_OK;
         }
     }
-    return ohlcv_leftovers<AF64>(ctx, p, a, ci, nb, n, o, saw_long, long_min, grid);
+    return ohlcv_leftovers<AF64>(ctx, p, a, ci, nb, n, o, saw_long, pl.long_min, ohlcv_grid(ctx, nb));
 }
 
 // comp_bar_ohlcv (without the median) for the bars longer than min_cnt that another kernel left behind (`go`: its flag)
@@ -1796,9 +1816,8 @@ extern "C" int fmk_comp_bar_ohlcv_dev(fmk_ctx *ctx, const double *d_price, const
     FMK_HIP(ctx, hipSetDevice(ctx->device));
     const int64_t nb = n_idx - 1;
     OhlcvOut o{d_open, d_high, d_low, d_close, d_volume, d_vwap, d_trades, d_median, nullptr};
-    const int variant = 1;     // (0: the generic kernels only)
-    return amount_is_f64 ? ohlcv_launch<true>(ctx, d_price, d_amount, d_close_idx, nb, n, o, variant)
-                         : ohlcv_launch<false>(ctx, d_price, d_amount, d_close_idx, nb, n, o, variant);
+    return amount_is_f64 ? ohlcv_launch<true>(ctx, d_price, d_amount, d_close_idx, nb, n, o)
+                         : ohlcv_launch<false>(ctx, d_price, d_amount, d_close_idx, nb, n, o);
 }
 
 // _time_bar_indexer + comp_bar_ohlcv in one call (TimeBarKit.build_ohlcv on resident columns; bench.py's step): the results of
@@ -1818,7 +1837,6 @@ extern "C" int fmk_time_bars_ohlcv_dev(fmk_ctx *ctx, const int64_t *d_ts, const 
     const int64_t nb = n_edges - 1;
     OhlcvOut o{d_open, d_high, d_low, d_close, d_volume, d_vwap, d_trades, d_median, nullptr};
     const TbFuse tb{d_ts, first_edge, delta, ts_first, ts_last, d_clock, d_close_idx};
-    const int variant = 1;
-    return amount_is_f64 ? ohlcv_launch<true>(ctx, d_price, d_amount, d_close_idx, nb, n, o, variant, &tb)
-                         : ohlcv_launch<false>(ctx, d_price, d_amount, d_close_idx, nb, n, o, variant, &tb);
+    return amount_is_f64 ? ohlcv_launch<true>(ctx, d_price, d_amount, d_close_idx, nb, n, o, &tb)
+                         : ohlcv_launch<false>(ctx, d_price, d_amount, d_close_idx, nb, n, o, &tb);
 }

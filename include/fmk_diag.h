@@ -80,6 +80,13 @@ int fmk_diag_cusum_onepass(int64_t *used, int64_t *fix_launches, int64_t *pendin
 /* the last fmk_triple_barrier[_dev] call on this context: {schedule (0 every tick walked, 1 the block tables), events, events skipped (no tick in
  * their window), blocks opened by the table schedule, ticks walked}; waits for the context's stream */
 int fmk_diag_label_last(fmk_ctx *ctx, int64_t *out5);
+/* the first-pass schedule fmk_comp_bar_ohlcv_dev / fmk_time_bars_ohlcv_dev (time_bar_fused = 1) would take for n ticks in n_bars bars
+ * on a device of n_cu compute units (csrc/fmk_ohlcv.hip: ohlcv_plan; pipe_min_stage: what FMK_TB_PIPE_MIN_STAGE holds, default 4096).
+ * Plain numbers, no context, no device.  out8 = {kind (0 wave per bar, 1 lane per bar, 2 rows, 3 the pipelined time-bar step), lane
+ * tile in ticks, lanes per bar, chunk cap of the wave-per-bar kernel, grid, block size, long_min (bars of more ticks are left to the
+ * later passes), bars of the pipelined step's first stage}; fields that do not apply to the kind are 0 */
+int fmk_diag_ohlcv_plan(int64_t n, int64_t n_bars, int amount_is_f64, int want_median, int time_bar_fused, int n_cu,
+                        int64_t pipe_min_stage, int64_t *out8);
 
 #ifdef __cplusplus
 }
