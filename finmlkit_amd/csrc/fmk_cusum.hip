@@ -774,3 +774,6 @@ extern "C" int fmk_cusum_bar_indexer_dev(fmk_ctx *ctx, const int64_t *d_ts, cons
     if (n_rounds) *n_rounds = rounds;
     return FMK_OK;
 }
+
+// the symmetric CUSUM event filter (finmlkit/sampling/filters.py): kernels of its own on the scheme of fmk_cusum_onepass.h
+#include "fmk_cusum_filter.h"

@@ -490,4 +490,25 @@ int fmk_label_weights(fmk_ctx *ctx, const double *close_, const int16_t *concurr
     return FMK_OK;
 }
 
+int fmk_cusum_filter(fmk_ctx *ctx, const double *x, int64_t n, const double *thr, int64_t n_thr, int64_t *out, int64_t capacity,
+                     int64_t *n_out)
+{
+    if (n <= 1) return fmk_set_error(ctx, FMK_E_ARG, "Input time series must have at least 2 elements.");
+    if (n_thr != 1 && n_thr != n)
+        return fmk_set_error(ctx, FMK_E_ARG, "Threshold array must either contain 1 const. element or len(raw_time_series) elements.");
+    DevBag bag(ctx);
+    double *d_x, *d_thr;
+    int64_t *d_o = nullptr;
+    FMK_TRY(bag.up(x, n, &d_x));
+    FMK_TRY(bag.up(thr, n_thr, &d_thr));
+    if (out) FMK_TRY(bag.out(n - 1, &d_o));                       // at most one event per tick from 1 on
+    int64_t m = 0;
+    FMK_TRY(fmk_cusum_filter_dev(ctx, d_x, n, d_thr, n_thr, d_o, out ? n - 1 : 0, &m, nullptr));
+    if (n_out) *n_out = m;
+    if (!out) return FMK_OK;
+    if (capacity < m)
+        return fmk_set_error(ctx, FMK_E_CAPACITY, "cusum_filter: %lld event indices, capacity %lld", (long long)m, (long long)capacity);
+    return down(ctx, out, (const int64_t *)d_o, m);
+}
+
 }  // extern "C"

@@ -379,6 +379,33 @@ class DeviceTrades:
         self.ctx.call("fmk_realized_vol_dev", r.p, c_i64(r.n), c_i64(int(window)), C.c_int(bool(is_sample)), out.p)
         return out
 
+    # ------------------------------------------------------------------ event sampling
+    def cusum_filter(self, threshold, series: Optional[DeviceArray] = None) -> DeviceArray:
+        """cusum_filter (sampling/filters.py:7-70) on a resident float64 series (default: the price column) -> int64 event indices
+        on the device, as `triple_barrier` takes them.  `threshold`: a float, or a DeviceArray with one value per element."""
+        x = self.price if series is None else series
+        if x.n <= 1:
+            raise ValueError("Input time series must have at least 2 elements.")
+        if isinstance(threshold, DeviceArray):
+            if threshold.n != 1 and threshold.n != x.n:
+                raise ValueError("Threshold array must either contain 1 const. element or len(raw_time_series) elements.")
+            thr = threshold
+        else:
+            thr = DeviceArray.from_host(self.ctx, np.array([threshold], dtype=np.float64))
+        # one call when the guess holds (an event per 64 ticks or fewer); otherwise the count it reports sizes the second
+        m = c_i64()
+        out = DeviceArray(self.ctx, max(1024, x.n // 64), np.int64)
+        args = (x.p, c_i64(x.n), thr.p, c_i64(thr.n))
+        if self.ctx.call("fmk_cusum_filter_dev", *args, out.p, c_i64(out.n), C.byref(m), None, allow=(_ffi.E_CAPACITY,)) != _ffi.OK:
+            out = DeviceArray(self.ctx, m.value, np.int64)
+            self.ctx.call("fmk_cusum_filter_dev", *args, out.p, c_i64(out.n), C.byref(m), None)
+        if m.value == out.n:
+            return out
+        ev = DeviceArray(self.ctx, m.value, np.int64)                  # an array of its own: `out` is released with this frame
+        if m.value:
+            self.ctx.call("fmk_d2d", ev.p, out.p, C.c_size_t(ev.nbytes))
+        return ev
+
     # ------------------------------------------------------------------ labels and sample weights
     def triple_barrier(self, event_idx: DeviceArray, targets: DeviceArray, horizontal_barriers, vertical_barrier: float,
                        min_close_time_sec: float, side: Optional[DeviceArray] = None, min_ret: float = 0.0):

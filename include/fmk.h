@@ -358,6 +358,19 @@ int fmk_cusum_bar_indexer_dev(fmk_ctx *ctx, const int64_t *d_ts, const double *d
 int fmk_cusum_bar_indexer(fmk_ctx *ctx, const int64_t *ts, const double *price, double *sigma, int64_t n,
                           double sigma_floor, double sigma_mult, int64_t *out, int64_t capacity, int64_t *n_out);
 
+/* ---- the symmetric CUSUM event filter: finmlkit/sampling/filters.py:7-70 ------------------------------------------
+ * cusum_filter on any float64 series x of n >= 2 elements: for i = 1 .. n-1, ret = log(x[i] / x[i-1]) (the host's log:
+ * csrc/fmk_log.h), s_pos = max(0, s_pos + ret), s_neg = min(0, s_neg + ret); s_neg < -thr[i] resets s_neg and emits i, else
+ * s_pos > thr[i] resets s_pos and emits i (the negative side first, strict comparisons).  thr: one constant (n_thr == 1) or one
+ * value per element (n_thr == n).  The indices are the reference's bit for bit on every input (NaN / non-positive x, NaN /
+ * negative / infinite thresholds included).  d_out == NULL: count only (*n_out).  *n_rounds (may be NULL): launches over the
+ * chunks (pass A + fix-ups).  FMK_E_ARG with the reference's messages: n <= 1, n_thr not 1 or n.  FMK_E_CAPACITY: capacity <
+ * *n_out (which is set).  FMK_CUSUM_FILTER_FORM=onepass|fixed forces one of the two schedules (tests). */
+int fmk_cusum_filter_dev(fmk_ctx *ctx, const double *d_x, int64_t n, const double *d_thr, int64_t n_thr, int64_t *d_out,
+                         int64_t capacity, int64_t *n_out, int64_t *n_rounds);
+int fmk_cusum_filter(fmk_ctx *ctx, const double *x, int64_t n, const double *thr, int64_t n_thr, int64_t *out, int64_t capacity,
+                     int64_t *n_out);
+
 /* ---- labels and sample weights on the tick tape: finmlkit/label/tbm.py, label/weights.py ------------------------
  * triple_barrier (tbm.py:11-158) on the raw tape.  Per event: label (side labels -1 / +1; meta labels 0 / 1 when d_side is given),
  * index of the first barrier touch, the return there and the max return / barrier ratio.  Labels, touch indices, returns and ratios

@@ -80,6 +80,10 @@ int fmk_diag_cusum_onepass(int64_t *used, int64_t *fix_launches, int64_t *pendin
 /* the last fmk_triple_barrier[_dev] call on this context: {schedule (0 every tick walked, 1 the block tables), events, events skipped (no tick in
  * their window), blocks opened by the table schedule, ticks walked}; waits for the context's stream */
 int fmk_diag_label_last(fmk_ctx *ctx, int64_t *out5);
+/* last fmk_cusum_filter[_dev] call of this process: the form that answered (0 pass A + the wave-per-chunk fix-up, 1 the
+ * lane-per-chunk re-walk took over), launches after pass A (fix-ups and re-walks), the chunks that had not merged within the first
+ * fix-up launch's limit, the number of chunks */
+int fmk_diag_cusum_filter_last(int64_t *form, int64_t *fix_launches, int64_t *pending_first, int64_t *chunks);
 /* the first-pass schedule fmk_comp_bar_ohlcv_dev / fmk_time_bars_ohlcv_dev (time_bar_fused = 1) would take for n ticks in n_bars bars
  * on a device of n_cu compute units (csrc/fmk_ohlcv.hip: ohlcv_plan; pipe_min_stage: what FMK_TB_PIPE_MIN_STAGE holds, default 4096).
  * Plain numbers, no context, no device.  out8 = {kind (0 wave per bar, 1 lane per bar, 2 rows, 3 the pipelined time-bar step), lane
