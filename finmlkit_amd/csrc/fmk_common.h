@@ -77,6 +77,11 @@ struct fmk_mail {
         int64_t ts_ends[2];                // k_lb_precheck: ts[0], ts[n-1] (the tape's tick rate)
         int64_t last[2];                   // host copy only: schedule (0 direct, 1 tables) and events of this context's last call
     } label;
+    struct Brk {                           // fmk_break.hip
+        int nonpos;                        // k_brk_log: an element <= 0
+        unsigned long long pairs, skipped; // k_brk_pairs: (t, n) pairs walked, pairs the den <= 1e-16 test dropped
+        int64_t last[4];                   // host copy only: outputs, slabs per tile span, slab elements, tiles of the last call
+    } brk;
 };
 static_assert(sizeof(fmk_mail::fp_median) == 2 * sizeof(int), "k_bar_footprints adds to saw_long + 1");
 static_assert(alignof(fmk_mail) == 8, "the 64-bit atomics of the kernels need 8-byte fields");

@@ -511,4 +511,36 @@ int fmk_cusum_filter(fmk_ctx *ctx, const double *x, int64_t n, const double *thr
     return down(ctx, out, (const int64_t *)d_o, m);
 }
 
+// both flavours of the CSW CUSUM test: window_size < 0 selects developing
+static int cusum_test_host(fmk_ctx *ctx, const double *x, int64_t n, int64_t window_size, int64_t warmup_period, double *up,
+                           double *dn, double *crit_up, double *crit_down)
+{
+    DevBag bag(ctx);
+    double *d_x, *d_o;
+    FMK_TRY(bag.up(x, n, &d_x));
+    FMK_TRY(bag.out(4 * n, &d_o));
+    if (window_size < 0)
+        FMK_TRY(fmk_cusum_test_developing_dev(ctx, d_x, n, warmup_period, d_o, d_o + n, d_o + 2 * n, d_o + 3 * n));
+    else
+        FMK_TRY(fmk_cusum_test_rolling_dev(ctx, d_x, n, window_size, warmup_period, d_o, d_o + n, d_o + 2 * n, d_o + 3 * n));
+    FMK_TRY(down(ctx, up, (const double *)d_o, n));
+    FMK_TRY(down(ctx, dn, (const double *)d_o + n, n));
+    FMK_TRY(down(ctx, crit_up, (const double *)d_o + 2 * n, n));
+    return down(ctx, crit_down, (const double *)d_o + 3 * n, n);
+}
+
+int fmk_cusum_test_rolling(fmk_ctx *ctx, const double *x, int64_t n, int64_t window_size, int64_t warmup_period, double *up,
+                           double *dn, double *crit_up, double *crit_down)
+{
+    if (warmup_period < 2) return fmk_set_error(ctx, FMK_E_ARG, "warmup_period must be at least 2.");
+    return cusum_test_host(ctx, x, n, window_size < 0 ? 0 : window_size, warmup_period, up, dn, crit_up, crit_down);
+}
+
+int fmk_cusum_test_developing(fmk_ctx *ctx, const double *x, int64_t n, int64_t warmup_period, double *up, double *dn,
+                              double *crit_up, double *crit_down)
+{
+    if (warmup_period < 2) return fmk_set_error(ctx, FMK_E_ARG, "warmup_period must be at least 2.");
+    return cusum_test_host(ctx, x, n, -1, warmup_period, up, dn, crit_up, crit_down);
+}
+
 }  // extern "C"

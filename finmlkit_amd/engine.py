@@ -406,6 +406,21 @@ class DeviceTrades:
             self.ctx.call("fmk_d2d", ev.p, out.p, C.c_size_t(ev.nbytes))
         return ev
 
+    # ------------------------------------------------------------------ structural breaks
+    def cusum_test_rolling(self, window_size: int = 1000, warmup_period: int = 30, series: Optional[DeviceArray] = None):
+        """cusum_test_rolling (feature/core/structural_break/cusum.py:179-274) on a resident float64 series (default: the price
+        column) -> (up, down, crit_up, crit_down), four resident float64 arrays.  ValueError when a price is <= 0."""
+        if warmup_period < 2:
+            raise ValueError("warmup_period must be at least 2.")
+        x = self.price if series is None else series
+        if x.dtype != np.float64:
+            raise TypeError(f"cusum_test_rolling: the series must be float64, not {x.dtype}")
+        out = tuple(DeviceArray(self.ctx, x.n, np.float64) for _ in range(4))
+        if x.n:
+            self.ctx.call("fmk_cusum_test_rolling_dev", x.p, c_i64(x.n), c_i64(max(0, int(window_size))), c_i64(int(warmup_period)),
+                          *[o.p for o in out])
+        return out
+
     # ------------------------------------------------------------------ labels and sample weights
     def triple_barrier(self, event_idx: DeviceArray, targets: DeviceArray, horizontal_barriers, vertical_barrier: float,
                        min_close_time_sec: float, side: Optional[DeviceArray] = None, min_ret: float = 0.0):

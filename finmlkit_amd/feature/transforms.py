@@ -1,4 +1,5 @@
-"""The tick-level transforms of the hot path: `ReturnT`, `EWMST`, `RealizedVolatility` (+ `Compose`).
+"""The tick-level transforms of the hot path: `ReturnT`, `EWMST`, `RealizedVolatility` (+ `Compose`), and the structural-break
+transform `CUSUMTest` (reference transforms.py:631-708).
 
 Counterparts of finmlkit/feature/transforms.py:89-117 (ReturnT), :308-332 (EWMST) and the
 pipeline part of finmlkit/feature/kit.py:Compose (:630-720), enough to run the QuickStart flow
@@ -16,6 +17,7 @@ import pandas as pd
 
 from .. import _ffi
 from .._ffi import DeviceArray, c_f64, c_i64
+from .core.structural_break.cusum import cusum_test_rolling
 from .core.utils import comp_lagged_returns
 from .core.volatility import ewmst, realized_vol
 
@@ -122,6 +124,75 @@ class RealizedVolatility(SISOTransform):
             return DeviceArray.from_host(ts.ctx, np.full(y.n, np.nan))
         ts.ctx.call("fmk_realized_vol_dev", y.p, c_i64(y.n), c_i64(int(self.window)), C.c_int(bool(self.is_sample)), out.p)
         return out
+
+
+class SIMOTransform:
+    """One input column, several output series.  By default series i is named "<input column>_<produces[i]>"; a subclass may
+    name its outputs otherwise by overriding `output_name` (CUSUMTest does)."""
+
+    def __init__(self, input_col: str, output_cols):
+        self.requires = [input_col]
+        self.produces = [str(c) for c in output_cols]
+
+    @property
+    def output_name(self):
+        prefix = self.requires[0] + "_"
+        return [prefix + suffix for suffix in self.produces]
+
+    def __call__(self, x: pd.DataFrame, *, backend: str = "nb"):
+        assert backend in ("pd", "nb", "hip"), "Backend must be 'pd', 'nb' or 'hip'."
+        if not isinstance(x, pd.DataFrame):
+            raise TypeError("Input must be a pandas DataFrame")
+        col = self.requires[0]
+        if col not in x.columns:
+            raise ValueError(f"Input column {col} not found in DataFrame")
+        arrays = self._hip(x[col].values)
+        names = self.output_name
+        assert len(arrays) == len(names), f"{type(self).__name__} made {len(arrays)} arrays for {len(names)} names"
+        return tuple(pd.Series(a, index=x.index, name=nm) for a, nm in zip(arrays, names))
+
+    def _hip(self, values):
+        """The input column as a NumPy array -> one array per output."""
+        raise NotImplementedError
+
+
+class CUSUMTest(SIMOTransform):
+    """Rolling Chu-Stinchcombe-White CUSUM test as six features (reference transforms.py:631-708): per side a score (statistic
+    minus critical value, clipped to +-10), a flag (score > 0) and an age (bars since the last flag, clipped to `max_age`).  The
+    four arrays of the test come from the device (csrc/fmk_break.hip); score, flag and age are host arithmetic on them."""
+
+    def __init__(self, window_size: int = 50, warmup_period: int = 30, max_age: int = 144, input_col: str = "close"):
+        base_up, base_down = f"cumote_up{window_size}", f"cumote_down{window_size}"
+        super().__init__(input_col, [f"{base_up}_score", f"{base_down}_score", f"{base_up}_flag", f"{base_down}_flag",
+                                     f"{base_up}_age", f"{base_down}_age"])
+        self.window_size = window_size
+        self.warmup_period = warmup_period
+        self.max_age = max_age
+
+    @staticmethod
+    def features(up, down, crit_up, crit_down, max_age: int):
+        """(up, down, crit_up, crit_down) -> (score_up, score_down, flag_up, flag_down, age_up, age_down): float64, bool, uint8."""
+        out_score, out_flag, out_age = [], [], []
+        pos = np.arange(len(up), dtype=np.int64)
+        for stat, crit in ((up, crit_up), (down, crit_down)):
+            with np.errstate(invalid="ignore"):
+                brk = stat - crit
+                flag = (brk > 0).astype(np.bool_)
+                out_score.append(np.clip(brk, -10, 10))
+            # every flag starts a group (the elements before the first flag are one too); the age is the position inside it
+            start = np.maximum.accumulate(np.where(flag, pos, 0))
+            out_flag.append(flag)
+            out_age.append(np.clip(pos - start, 0, max_age).astype(np.uint8))
+        return (*out_score, *out_flag, *out_age)
+
+    @property
+    def output_name(self):
+        """As in the reference: the six names carry no input-column prefix."""
+        return self.produces
+
+    def _hip(self, values):
+        four = cusum_test_rolling(values, self.window_size, self.warmup_period)
+        return self.features(*four, self.max_age)
 
 
 class Compose(SISOTransform):

@@ -371,6 +371,26 @@ int fmk_cusum_filter_dev(fmk_ctx *ctx, const double *d_x, int64_t n, const doubl
 int fmk_cusum_filter(fmk_ctx *ctx, const double *x, int64_t n, const double *thr, int64_t n_thr, int64_t *out, int64_t capacity,
                      int64_t *n_out);
 
+/* ---- the Chu-Stinchcombe-White CUSUM test on levels: finmlkit/feature/core/structural_break/cusum.py -------------
+ * cusum_test_rolling / cusum_test_developing on a float64 price series x of n elements -> four float64 arrays of n elements: the
+ * one-sided statistics (up, down) and their critical values, bit for bit what the reference's code gives with the host's log()
+ * (csrc/fmk_log.h) as its np.log -- the log it has when Numba compiles it; interpreted, NumPy's own log rounds a few arguments
+ * in a thousand differently -- NaN positions included (every window's variance summed in index order; the first n that attains a side's
+ * maximum gives its critical value).  Output t looks back to base(t) = max(0, t - window_size) (developing: 0); outputs below
+ * warmup_period are NaN.  Rolling raises window_size to warmup_period + 2, returns all-NaN when n < warmup_period + 2 and checks
+ * the prices first; developing checks nothing (log of 0 or a negative number flows through).  window_size may be anything: a
+ * window that does not fit one LDS staging is walked in slabs (FMK_BREAK_SLAB=<elements> shrinks the slab: tests only).
+ * FMK_E_ARG: "All close prices must be positive." (rolling: an element <= 0; NaN passes), "warmup_period must be at least 2."
+ * (the reference divides by zero or reads out of bounds there), n >= 2^31.  The rolling call waits once, for the price check. */
+int fmk_cusum_test_rolling_dev(fmk_ctx *ctx, const double *d_x, int64_t n, int64_t window_size, int64_t warmup_period,
+                               double *d_up, double *d_down, double *d_crit_up, double *d_crit_down);
+int fmk_cusum_test_developing_dev(fmk_ctx *ctx, const double *d_x, int64_t n, int64_t warmup_period, double *d_up, double *d_down,
+                                  double *d_crit_up, double *d_crit_down);
+int fmk_cusum_test_rolling(fmk_ctx *ctx, const double *x, int64_t n, int64_t window_size, int64_t warmup_period, double *up,
+                           double *down, double *crit_up, double *crit_down);
+int fmk_cusum_test_developing(fmk_ctx *ctx, const double *x, int64_t n, int64_t warmup_period, double *up, double *down,
+                              double *crit_up, double *crit_down);
+
 /* ---- labels and sample weights on the tick tape: finmlkit/label/tbm.py, label/weights.py ------------------------
  * triple_barrier (tbm.py:11-158) on the raw tape.  Per event: label (side labels -1 / +1; meta labels 0 / 1 when d_side is given),
  * index of the first barrier touch, the return there and the max return / barrier ratio.  Labels, touch indices, returns and ratios

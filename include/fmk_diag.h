@@ -84,6 +84,12 @@ int fmk_diag_label_last(fmk_ctx *ctx, int64_t *out5);
  * lane-per-chunk re-walk took over), launches after pass A (fix-ups and re-walks), the chunks that had not merged within the first
  * fix-up launch's limit, the number of chunks */
 int fmk_diag_cusum_filter_last(int64_t *form, int64_t *fix_launches, int64_t *pending_first, int64_t *chunks);
+/* the last fmk_cusum_test_{rolling,developing}[_dev] call on this context: {outputs computed, (t, n) pairs walked, slabs one tile's
+ * span took (> 1: the window did not fit one LDS staging), quotients formed (the pairs that passed den > 1e-16; there is no
+ * screening: one exact quotient per such pair), slab elements, workgroups}; waits for the context's stream */
+int fmk_diag_cusum_test_last(fmk_ctx *ctx, int64_t *out6);
+/* d_out[i] = sqrt(d_in[i]) as the device's float64 sqrt rounds it (the one fmk_break.hip uses; tests compare it with the host's) */
+int fmk_diag_device_sqrt(fmk_ctx *ctx, const double *d_in, int64_t n, double *d_out);
 /* the first-pass schedule fmk_comp_bar_ohlcv_dev / fmk_time_bars_ohlcv_dev (time_bar_fused = 1) would take for n ticks in n_bars bars
  * on a device of n_cu compute units (csrc/fmk_ohlcv.hip: ohlcv_plan; pipe_min_stage: what FMK_TB_PIPE_MIN_STAGE holds, default 4096).
  * Plain numbers, no context, no device.  out8 = {kind (0 wave per bar, 1 lane per bar, 2 rows, 3 the pipelined time-bar step), lane
