@@ -125,12 +125,17 @@ __device__ __forceinline__ bool tb_walk(const double *__restrict__ close, int64_
     return false;
 }
 
-// extrema of ret over a table entry: ret is monotone in log(close) for every side (side 0: +-0.0 everywhere)
+// extrema of ret over a table entry: ret is monotone in log(close) for every side (side 0: +-0.0 everywhere).  An image that is
+// NaN (inf - inf with an infinite base, +-inf * 0) is left out like the walk leaves out a NaN tick: every non-NaN ret of the
+// entry is then the other image, so fmax / fmin give the entry's extrema (both NaN: no tick of it can touch).  Side 0 over a
+// finite base: +-0.0 at every finite tick and NaN elsewhere, which (-inf, +inf) extrema cannot tell from "NaN everywhere"; the entry
+// says 0 and the walk of the block decides (0 touches only a barrier that is <= 0 / >= 0, and 0 changes neither ratio).
 __device__ __forceinline__ void lb_entry(const LbMinMax e, double base, double s, double &hi, double &lo)
 {
+    if (s == 0.0 && isfinite(base)) { hi = lo = 0.0; return; }
     const double r1 = (e.mx - base) * s, r2 = (e.mn - base) * s;
-    hi = r1 > r2 ? r1 : r2;
-    lo = r1 > r2 ? r2 : r1;
+    hi = fmax(r1, r2);
+    lo = fmin(r1, r2);
 }
 
 template <bool TABLE>

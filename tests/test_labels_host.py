@@ -32,6 +32,45 @@ def load_cases():
 CASES = load_cases()
 
 
+def load_odd():
+    """tests/golden/labels_odd.*: planted tapes (stored), label cases and weights cases recorded from the reference."""
+    z = np.load(os.path.join(GOLD, "labels_odd.npz"))
+    man = json.load(open(os.path.join(GOLD, "labels_odd.json")))
+    tapes = {k[5:-3]: (z[k], z[k[:-3] + ".close"]) for k in z.files if k.startswith("tape_") and k.endswith(".ts")}
+    cases, weights = {}, {}
+    for name, m in man.items():
+        if name.startswith("_"):
+            continue
+        c = {k.split(".", 1)[1]: z[k] for k in z.files if k.startswith(name + ".")}
+        c["ts"], c["close"] = tapes[m["tape"]]
+        if m.get("weights"):
+            weights[name] = c
+            continue
+        c.update(hb=(float(m["horizontal_barriers"][0]), float(m["horizontal_barriers"][1])), vb=float(m["vertical_barrier"]),
+                 mc=m["min_close_time_sec"], min_ret=m["min_ret"], meta=m["meta"], n_skipped=m["skipped"],
+                 made_for_skipping=m["made_for_skipping"])
+        c.setdefault("side", None)
+        cases[name] = c
+    return cases, weights, man
+
+
+ODD, ODD_WEIGHTS, ODD_MANIFEST = load_odd()
+# the least the odd-value fixture has to exercise, over all its recorded events
+ODD_MINIMA = {"base_minus_inf": 8, "base_plus_inf": 8, "base_nan": 8, "nan_inside_path": 50, "touch_at_infinite_return": 20,
+              "side_zero": 20, "target_nan": 10, "target_zero": 10, "target_negative": 10, "target_infinite": 10,
+              "two_whole_blocks_in_window": 100}
+
+
+def same_bits(got, want):
+    """bit for bit, the sign of an infinity and of a zero included; every NaN equals every NaN"""
+    got, want = np.asarray(got), np.asarray(want)
+    if got.dtype != want.dtype or got.shape != want.shape:
+        return False
+    if got.dtype.kind == "f":
+        return bool(np.all((got.view("u8") == want.view("u8")) | (np.isnan(got) & np.isnan(want))))
+    return bool(np.array_equal(got, want))
+
+
 def rel_close(got, want, rtol):
     got, want = np.asarray(got), np.asarray(want)
     both_nan = np.isnan(got) & np.isnan(want)
@@ -74,6 +113,78 @@ def test_helper_reproduces_the_reference(orc, name):
     attn, _ = H.return_attribution(c["event_idx"], c["touch_idx"], px, conc, True)
     scale = len(att) / att.sum()
     assert np.all(np.abs(attn - c["return_attribution_norm"]) <= bound * scale + 1e-12 * attn)
+
+
+def test_host_log_is_the_hosts_log_extended():
+    import math
+    assert H.host_log(0.0) == -math.inf and H.host_log(-0.0) == -math.inf and H.host_log(math.inf) == math.inf
+    assert math.isnan(H.host_log(-5.0)) and math.isnan(H.host_log(-math.inf)) and math.isnan(H.host_log(math.nan))
+    assert H.host_log(5e-324) == math.log(5e-324) and H.host_log(101.25) == math.log(101.25)
+    col = H.log_column(np.array([0.0, -1.0, 2.0, math.inf]))
+    assert col[0] == -math.inf and math.isnan(col[1]) and col[2] == math.log(2.0) and col[3] == math.inf
+
+
+@pytest.mark.parametrize("which", ["scalar", "vectorised"])
+@pytest.mark.parametrize("name", sorted(ODD))
+def test_odd_fixture_against_the_yardstick(name, which):
+    """Every event of the fixture, all four outputs and the skipped mask, bit for bit: the events recorded from the reference
+    and the ones it cannot answer (side=None with a NaN final return), which the fixture holds by the project's definition."""
+    c = ODD[name]
+    fn = H.triple_barrier_scalar if which == "scalar" else H.triple_barrier
+    got = fn(c["ts"], c["close"], c["event_idx"], c["targets"], c["hb"], c["vb"], c["mc"], c["side"], c["min_ret"])
+    assert same_bits(got[4], c["skipped"]) and int(got[4].sum()) == c["n_skipped"]
+    for g, k in zip(got, ("labels", "touch_idx", "returns", "ratios")):
+        assert same_bits(g, c[k]), f"{name}/{which}/{k}"
+    rec = c["recorded"]
+    assert c["meta"] and rec.all() or not c["meta"] and (~rec).sum() * 10 <= len(rec)
+    assert np.all(np.isnan(c["returns"][~rec])) and np.all(c["labels"][~rec] == 1)         # the project's definition
+    assert c["made_for_skipping"] or c["n_skipped"] * 100 <= len(rec)
+
+
+def test_odd_fixture_covers_the_cases_of_the_issue():
+    totals = dict.fromkeys(ODD_MINIMA, 0)
+    for name, m in ODD_MANIFEST.items():
+        if not name.startswith("_") and not m.get("weights"):
+            for k in totals:
+                totals[k] += m["counts"][k]
+    print(totals)
+    assert totals == ODD_MANIFEST["_totals"]
+    assert not {k: v for k, v in totals.items() if v < ODD_MINIMA[k]}
+    # what can be counted from the arrays alone, counted again
+    side_zero = targets = 0
+    for c in ODD.values():
+        live = c["recorded"] & ~c["skipped"]
+        side_zero += int((c["side"][live] == 0).sum()) if c["side"] is not None else 0
+        targets += int(np.isnan(c["targets"][live]).sum())
+    assert side_zero == totals["side_zero"] and targets == totals["target_nan"]
+    assert {c["hb"] for c in ODD.values()} >= {(1.0, 1.0), (0.0, 0.0), (np.inf, 1.0), (1.0, np.inf)}
+    assert any(min(c["hb"]) < 0 for c in ODD.values()) and {c["mc"] == 0 for c in ODD.values()} == {True, False}
+    assert {np.isinf(c["vb"]) for c in ODD.values()} == {True, False}
+    for ts, px in {id(c["ts"]): (c["ts"], c["close"]) for c in ODD.values()}.values():
+        assert len(ts) == 6 * 1024 + 37 and ts[0] > 1.6e18 and (np.diff(ts) == 0).sum() > 10 and np.all(np.diff(ts) >= 0)
+        assert np.any(ts.astype(np.float64).astype(np.int64) != ts)                        # float64(ts) rounds
+        assert np.isnan(px).any() and (px == 0).any() and (px < 0).any() and np.isinf(px).any()
+    zero = ODD["zero_sym"]["close"]
+    assert np.signbit(zero[zero == 0]).any() and ((zero > 0) & (zero < 2.3e-308)).any()   # -0.0 and a subnormal
+    for name, w in ODD_WEIGHTS.items():
+        whole = (w["touch_idx"] + 1) // 1024 - (w["event_idx"] + 1023) // 1024
+        assert {0, 1, 2, 3, 4, 5} <= set(np.maximum(whole, 0).tolist()), name
+        hand = w["hand_concurrency"]
+        for k in range(1, 6):                                    # runs of 0 or of negative counts across every block boundary
+            assert np.all(hand[k * 1024 - 2:k * 1024 + 2] <= 0), name
+        assert (hand == 0).any() and (hand < 0).any()
+
+
+@pytest.mark.parametrize("name", sorted(ODD_WEIGHTS))
+def test_odd_weights_fixture_against_the_yardstick(name):
+    w = ODD_WEIGHTS[name]
+    avg, conc = H.average_uniqueness(w["ts"], w["event_idx"], w["touch_idx"])
+    assert same_bits(conc, w["concurrency"]) and same_bits(avg, w["avg_uniqueness"])
+    for cc, key in ((w["concurrency"], "return_attribution"), (w["hand_concurrency"], "return_attribution_hand")):
+        att, bound = H.return_attribution(w["event_idx"], w["touch_idx"], w["close"], cc, False)
+        fin = np.isfinite(w[key])
+        assert fin.sum() >= 20 and (~fin).sum() >= 20
+        assert np.all(np.abs(att[fin] - w[key][fin]) <= bound[fin]) and same_bits(att[~fin], w[key][~fin])
 
 
 def test_header_declares_and_library_exports_the_label_entry_points():
