@@ -543,4 +543,40 @@ int fmk_cusum_test_developing(fmk_ctx *ctx, const double *x, int64_t n, int64_t 
     return cusum_test_host(ctx, x, n, -1, warmup_period, up, dn, crit_up, crit_down);
 }
 
+// the rolling-window moments (fmk_rolling.hip): one series up, one down.  which: 0 sma, 1 zscore, 2 rolling variance, 3 variance ratio
+static int rolling_host(fmk_ctx *ctx, int which, const double *x, int64_t n, int64_t window, int64_t ddof, int64_t extra, double *out)
+{
+    if (window < 1) return fmk_set_error(ctx, FMK_E_ARG, "window must be at least 1.");
+    if (which == 1 && ddof >= window) return fmk_set_error(ctx, FMK_E_ARG, "comp_zscore: window - ddof must be positive.");
+    DevBag bag(ctx);
+    double *d_x, *d_o;
+    FMK_TRY(bag.up(x, n, &d_x));
+    FMK_TRY(bag.out(n, &d_o));
+    if (which == 0) FMK_TRY(fmk_sma_dev(ctx, d_x, n, window, d_o));
+    else if (which == 1) FMK_TRY(fmk_zscore_dev(ctx, d_x, n, window, ddof, d_o));
+    else if (which == 2) FMK_TRY(fmk_rolling_variance_dev(ctx, d_x, n, window, ddof, extra, d_o));
+    else FMK_TRY(fmk_variance_ratio_1_4_dev(ctx, d_x, n, window, ddof, (int)extra, d_o));
+    return down(ctx, out, (const double *)d_o, n);
+}
+
+int fmk_sma(fmk_ctx *ctx, const double *x, int64_t n, int64_t window, double *out)
+{
+    return rolling_host(ctx, 0, x, n, window, 0, 0, out);
+}
+
+int fmk_zscore(fmk_ctx *ctx, const double *x, int64_t n, int64_t window, int64_t ddof, double *out)
+{
+    return rolling_host(ctx, 1, x, n, window, ddof, 0, out);
+}
+
+int fmk_rolling_variance(fmk_ctx *ctx, const double *x, int64_t n, int64_t window, int64_t ddof, int64_t min_periods, double *out)
+{
+    return rolling_host(ctx, 2, x, n, window, ddof, min_periods, out);
+}
+
+int fmk_variance_ratio_1_4(fmk_ctx *ctx, const double *price, int64_t n, int64_t window, int64_t ddof, int is_log, double *out)
+{
+    return rolling_host(ctx, 3, price, n, window, ddof, is_log != 0, out);
+}
+
 }  // extern "C"

@@ -379,6 +379,37 @@ class DeviceTrades:
         self.ctx.call("fmk_realized_vol_dev", r.p, c_i64(r.n), c_i64(int(window)), C.c_int(bool(is_sample)), out.p)
         return out
 
+    # ------------------------------------------------------------------ rolling-window moments (csrc/fmk_rolling.hip)
+    def _rolling(self, name: str, y: DeviceArray, window: int, *extra) -> DeviceArray:
+        if int(window) < 1:
+            raise ValueError("window must be at least 1.")
+        if y.dtype != np.float64:
+            raise TypeError(f"{name}: the series must be float64, not {y.dtype}")
+        out = DeviceArray(self.ctx, y.n, np.float64)
+        if y.n:
+            self.ctx.call(name, y.p, c_i64(y.n), c_i64(int(window)), *extra, out.p)
+        return out
+
+    def sma(self, y: DeviceArray, window: int) -> DeviceArray:
+        """sma (feature/core/ma.py:46-62) of a resident float64 series."""
+        return self._rolling("fmk_sma_dev", y, window)
+
+    def zscore(self, y: DeviceArray, window: int, ddof: int = 0) -> DeviceArray:
+        """comp_zscore (feature/core/utils.py:67-90) of a resident float64 series; ValueError when window - ddof <= 0."""
+        if int(window) >= 1 and int(window) - int(ddof) <= 0:
+            raise ValueError("comp_zscore: window - ddof must be positive.")
+        return self._rolling("fmk_zscore_dev", y, window, c_i64(int(ddof)))
+
+    def rolling_variance(self, y: DeviceArray, window: int, ddof: int = 1, min_periods: int = 1) -> DeviceArray:
+        """rolling_variance_nb (feature/core/volatility.py:440-478) of a resident float64 series."""
+        return self._rolling("fmk_rolling_variance_dev", y, window, c_i64(int(ddof)), c_i64(int(min_periods)))
+
+    def variance_ratio_1_4(self, window: int = 32, ddof: int = 0, ret_type: str = "log",
+                           series: Optional[DeviceArray] = None) -> DeviceArray:
+        """variance_ratio_1_4_core (feature/core/volatility.py:481-540) on a resident float64 series (default: the price column)."""
+        x = self.price if series is None else series
+        return self._rolling("fmk_variance_ratio_1_4_dev", x, window, c_i64(int(ddof)), C.c_int(ret_type == "log"))
+
     # ------------------------------------------------------------------ event sampling
     def cusum_filter(self, threshold, series: Optional[DeviceArray] = None) -> DeviceArray:
         """cusum_filter (sampling/filters.py:7-70) on a resident float64 series (default: the price column) -> int64 event indices

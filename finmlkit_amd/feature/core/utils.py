@@ -1,4 +1,4 @@
-"""Drop-in for finmlkit/feature/core/utils.py::comp_lagged_returns, computed on the MI355X."""
+"""Drop-in for finmlkit/feature/core/utils.py::comp_lagged_returns and ::comp_zscore, computed on the MI355X."""
 from __future__ import annotations
 
 import ctypes as C
@@ -8,6 +8,7 @@ from numpy.typing import NDArray
 
 from ... import _ffi
 from ..._ffi import c_f64, c_i64, ptr
+from .ma import rolling_call
 
 
 def comp_lagged_returns(timestamps: NDArray[np.int64], close: NDArray[np.float64], return_window_sec: float,
@@ -22,3 +23,12 @@ def comp_lagged_returns(timestamps: NDArray[np.int64], close: NDArray[np.float64
     ctx.call("fmk_comp_lagged_returns", ptr(ts), ptr(c), c_i64(len(c)), c_f64(return_window_sec),
              C.c_int(bool(is_log)), ptr(out))
     return out
+
+
+def comp_zscore(x: NDArray[np.float64], window: int, ddof: int) -> NDArray[np.float64]:
+    """Reference: finmlkit/feature/core/utils.py:67-90: (x[i] - mean) / std of the window ending at i, mean and the squared deviations
+    summed left to right, NaN where std == 0 and before the first full window.  `window - ddof <= 0` raises ValueError (the
+    reference divides by zero or takes the root of a negative number there)."""
+    if int(window) >= 1 and int(window) - int(ddof) <= 0:
+        raise ValueError("comp_zscore: window - ddof must be positive.")
+    return rolling_call("fmk_zscore", x, window, c_i64(int(ddof)))

@@ -1,8 +1,9 @@
 """Drop-in for the tick-level estimators of finmlkit/feature/core/volatility.py on the MI355X.
 
 The estimators that run on the raw tick frame are on the hot path: `ewmst`,
-`ewmst_mean0`, `ewms` and `realized_vol`.  The bar-level indicators of that module (Bollinger, Parkinson,
-ATR, variance ratio) are out of scope.
+`ewmst_mean0`, `ewms` and `realized_vol`; `rolling_variance_nb` and `variance_ratio_1_4_core` (the reference's
+microstructure-noise detector) run on a resident series too (csrc/fmk_rolling.hip).  The other bar-level indicators
+of that module (Bollinger, Parkinson, ATR) are out of scope.
 """
 from __future__ import annotations
 
@@ -13,6 +14,7 @@ from numpy.typing import NDArray
 
 from ... import _ffi
 from ..._ffi import c_f64, c_i64, ptr
+from .ma import rolling_call
 
 
 def _ewmst(timestamps, y, half_life, sigma_floor, mean0):
@@ -55,3 +57,15 @@ def realized_vol(r: NDArray[np.float64], window: int, is_sample: bool) -> NDArra
     out = np.empty(len(rr), np.float64)
     ctx.call("fmk_realized_vol", ptr(rr), c_i64(len(rr)), c_i64(int(window)), C.c_int(bool(is_sample)), ptr(out))
     return out
+
+
+def rolling_variance_nb(series: NDArray[np.float64], window: int, ddof: int = 1, min_periods: int = 1) -> NDArray[np.float64]:
+    """Reference: finmlkit/feature/core/volatility.py:440-478: per window the count, sum and sum of squares of the non-NaN
+    elements, max(0, (sum_sq / cnt - mean^2) * (cnt / (cnt - ddof))) when cnt >= min_periods and cnt > ddof, NaN otherwise."""
+    return rolling_call("fmk_rolling_variance", series, window, c_i64(int(ddof)), c_i64(int(min_periods)))
+
+
+def variance_ratio_1_4_core(price: NDArray[np.float64], window: int, ddof: int, ret_type: str) -> NDArray[np.float64]:
+    """Reference: finmlkit/feature/core/volatility.py:481-540: var(1-step returns) / (var(4-step returns) / 4) over `window`;
+    `ret_type` "log" takes log returns (the host's log), anything else simple returns."""
+    return rolling_call("fmk_variance_ratio_1_4", price, window, c_i64(int(ddof)), C.c_int(ret_type == "log"))

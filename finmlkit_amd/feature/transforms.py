@@ -1,12 +1,13 @@
-"""The tick-level transforms of the hot path: `ReturnT`, `EWMST`, `RealizedVolatility` (+ `Compose`), and the structural-break
-transform `CUSUMTest` (reference transforms.py:631-708).
+"""The tick-level transforms of the hot path: `ReturnT`, `EWMST`, `RealizedVolatility` (+ `Compose`), the rolling-window moments
+`SMA`, `ZScore` and `VarianceRatio14` (reference transforms.py:549-574, :335-359, :867-897), and the structural-break transform
+`CUSUMTest` (reference transforms.py:631-708).
 
 Counterparts of finmlkit/feature/transforms.py:89-117 (ReturnT), :308-332 (EWMST) and the
 pipeline part of finmlkit/feature/kit.py:Compose (:630-720), enough to run the QuickStart flow
     Compose(ReturnT(window, input_col="price"), EWMST(half_life))(trades.data)
 on the MI355X.  The reference's `backend="nb"` (Numba) and `"pd"` both map to the HIP path here
 (the reference's own `_pd` of these two transforms already delegates to the Numba kernel).
-The other ~37 bar-level transforms of the reference are out of scope.
+The other ~34 bar-level transforms of the reference are out of scope.
 """
 from __future__ import annotations
 
@@ -18,8 +19,9 @@ import pandas as pd
 from .. import _ffi
 from .._ffi import DeviceArray, c_f64, c_i64
 from .core.structural_break.cusum import cusum_test_rolling
-from .core.utils import comp_lagged_returns
-from .core.volatility import ewmst, realized_vol
+from .core.ma import sma
+from .core.utils import comp_lagged_returns, comp_zscore
+from .core.volatility import ewmst, realized_vol, variance_ratio_1_4_core
 
 
 class SISOTransform:
@@ -124,6 +126,79 @@ class RealizedVolatility(SISOTransform):
             return DeviceArray.from_host(ts.ctx, np.full(y.n, np.nan))
         ts.ctx.call("fmk_realized_vol_dev", y.p, c_i64(y.n), c_i64(int(self.window)), C.c_int(bool(self.is_sample)), out.p)
         return out
+
+
+class _Rolling(SISOTransform):
+    """A rolling-window moment (csrc/fmk_rolling.hip): `_host` is the NumPy-level function, `_entry` the device entry point, and
+    `_args()` what both take after the window."""
+    _host = None
+    _entry = ""
+
+    def _args(self):
+        return ()
+
+    def _c_args(self):
+        return tuple(c_i64(int(v)) for v in self._args())
+
+    def _hip(self, x):
+        res = type(self)._host(np.asarray(self._prepare_input_nb(x), dtype=np.float64), self.window, *self._args())
+        return self._prepare_output_nb(x.index, res)
+
+    def _dev(self, ts, y):
+        if int(self.window) < 1:
+            raise ValueError("window must be at least 1.")
+        out = DeviceArray(ts.ctx, y.n, np.float64)
+        if y.n:
+            ts.ctx.call(self._entry, y.p, c_i64(y.n), c_i64(int(self.window)), *self._c_args(), out.p)
+        return out
+
+
+class SMA(_Rolling):
+    """Simple moving average (reference transforms.py:549-574; the reference's "pd" backend is pandas' rolling mean, this is its
+    Numba kernel on either backend)."""
+    _host = staticmethod(sma)
+    _entry = "fmk_sma_dev"
+
+    def __init__(self, window: int, input_col: str = "x"):
+        super().__init__(input_col, f"sma{window}")
+        self.window = window
+
+
+class ZScore(_Rolling):
+    """Rolling z-score (reference transforms.py:335-359)."""
+    _host = staticmethod(comp_zscore)
+    _entry = "fmk_zscore_dev"
+
+    def __init__(self, window: int, input_col: str, ddof: int = 0):
+        super().__init__(input_col, f"z{window}")
+        self.window = window
+        self.ddof = ddof
+
+    def _args(self):
+        return (self.ddof,)
+
+    def _dev(self, ts, y):
+        if int(self.window) >= 1 and int(self.window) - int(self.ddof) <= 0:
+            raise ValueError("comp_zscore: window - ddof must be positive.")
+        return super()._dev(ts, y)
+
+
+class VarianceRatio14(_Rolling):
+    """var(1-step returns) / (var(4-step returns) / 4) (reference transforms.py:867-897)."""
+    _host = staticmethod(variance_ratio_1_4_core)
+    _entry = "fmk_variance_ratio_1_4_dev"
+
+    def __init__(self, window: int = 32, input_col: str = "close", ret_type: str = "log", ddof: int = 0):
+        super().__init__(input_col, f"var_ratio_1_4_{window}")
+        self.window = window
+        self.ret_type = ret_type
+        self.ddof = ddof
+
+    def _args(self):
+        return (self.ddof, self.ret_type)
+
+    def _c_args(self):
+        return (c_i64(int(self.ddof)), C.c_int(self.ret_type == "log"))
 
 
 class SIMOTransform:

@@ -391,6 +391,32 @@ int fmk_cusum_test_rolling(fmk_ctx *ctx, const double *x, int64_t n, int64_t win
 int fmk_cusum_test_developing(fmk_ctx *ctx, const double *x, int64_t n, int64_t warmup_period, double *up, double *down,
                               double *crit_up, double *crit_down);
 
+/* ---- rolling-window moments: finmlkit/feature/core/ma.py (sma), utils.py (comp_zscore), volatility.py (rolling_variance_nb,
+ * variance_ratio_1_4_core) on a float64 series of n elements -> one float64 array of n elements, NaN before the first full window
+ * (everywhere when window > n).  Bit for bit the reference's evaluation order as Numba compiles it: every window summed on its own,
+ * left to right, one rounded addition per element, nothing contracted (interpreted NumPy sums pairwise from 8 elements up and
+ * differs there); NaN positions included.
+ *   sma:      (1.0 / window) * sum.
+ *   zscore:   mean = sum / window, std = sqrt(sum((x - mean)^2) / (window - ddof)), (x[t] - mean) / std, NaN where std == 0.
+ *   rolling_variance: cnt, s, q over the non-NaN elements; cnt >= min_periods and cnt > ddof: m = s / cnt,
+ *             max(0, (q / cnt - m * m) * (cnt / (cnt - ddof))), else NaN.
+ *   variance_ratio_1_4: r1 = log(p[i] / p[i-1]) (is_log; the host's log: csrc/fmk_log.h; NaN where a price is NaN or <= 0) or
+ *             p[i] / p[i-1] - 1 (NaN where a price is NaN or p[i-1] <= 0), r4 = ((r1[i] + r1[i-1]) + r1[i-2]) + r1[i-3], v1 / v4 the
+ *             rolling variances (min_periods 1), out = v1 / (v4 / 4) where both are numbers and v4 > 0; all NaN when n < window + 4.
+ *             Scratch (3 n float64) comes from the context's pool.
+ * FMK_E_ARG, checked before a device is touched: window < 1, n >= 2^31, zscore with window - ddof <= 0 (the reference divides by
+ * zero or takes the root of a negative number there). */
+int fmk_sma_dev(fmk_ctx *ctx, const double *d_x, int64_t n, int64_t window, double *d_out);
+int fmk_sma(fmk_ctx *ctx, const double *x, int64_t n, int64_t window, double *out);
+int fmk_zscore_dev(fmk_ctx *ctx, const double *d_x, int64_t n, int64_t window, int64_t ddof, double *d_out);
+int fmk_zscore(fmk_ctx *ctx, const double *x, int64_t n, int64_t window, int64_t ddof, double *out);
+int fmk_rolling_variance_dev(fmk_ctx *ctx, const double *d_x, int64_t n, int64_t window, int64_t ddof, int64_t min_periods,
+                             double *d_out);
+int fmk_rolling_variance(fmk_ctx *ctx, const double *x, int64_t n, int64_t window, int64_t ddof, int64_t min_periods, double *out);
+int fmk_variance_ratio_1_4_dev(fmk_ctx *ctx, const double *d_price, int64_t n, int64_t window, int64_t ddof, int is_log,
+                               double *d_out);
+int fmk_variance_ratio_1_4(fmk_ctx *ctx, const double *price, int64_t n, int64_t window, int64_t ddof, int is_log, double *out);
+
 /* ---- labels and sample weights on the tick tape: finmlkit/label/tbm.py, label/weights.py ------------------------
  * triple_barrier (tbm.py:11-158) on the raw tape.  Per event: label (side labels -1 / +1; meta labels 0 / 1 when d_side is given),
  * index of the first barrier touch, the return there and the max return / barrier ratio.  Labels, touch indices, returns and ratios
