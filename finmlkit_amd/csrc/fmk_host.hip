@@ -579,4 +579,48 @@ int fmk_variance_ratio_1_4(fmk_ctx *ctx, const double *price, int64_t n, int64_t
     return rolling_host(ctx, 3, price, n, window, ddof, is_log != 0, out);
 }
 
+// the windowed order statistics (fmk_order.hip): one series up (three for %K), one down.  which: 0 burst ratio, 1 roc, 2 pct_change
+static int order_host(fmk_ctx *ctx, int which, const double *x, int64_t n, int64_t arg, double *out)
+{
+    if (which == 0 && arg < 1) return fmk_set_error(ctx, FMK_E_ARG, "window must be at least 1.");
+    if (which == 1 && arg < 0) return fmk_set_error(ctx, FMK_E_ARG, "roc: period must not be negative.");
+    if (which == 2 && arg < 0) return fmk_set_error(ctx, FMK_E_ARG, "pct_change: periods must not be negative.");
+    DevBag bag(ctx);
+    double *d_x, *d_o;
+    FMK_TRY(bag.up(x, n, &d_x));
+    FMK_TRY(bag.out(n, &d_o));
+    if (which == 0) FMK_TRY(fmk_burst_ratio_dev(ctx, d_x, n, arg, d_o));
+    else if (which == 1) FMK_TRY(fmk_roc_dev(ctx, d_x, n, arg, d_o));
+    else FMK_TRY(fmk_pct_change_dev(ctx, d_x, n, arg, d_o));
+    return down(ctx, out, (const double *)d_o, n);
+}
+
+int fmk_burst_ratio(fmk_ctx *ctx, const double *x, int64_t n, int64_t window, double *out)
+{
+    return order_host(ctx, 0, x, n, window, out);
+}
+
+int fmk_roc(fmk_ctx *ctx, const double *x, int64_t n, int64_t period, double *out)
+{
+    return order_host(ctx, 1, x, n, period, out);
+}
+
+int fmk_pct_change(fmk_ctx *ctx, const double *x, int64_t n, int64_t periods, double *out)
+{
+    return order_host(ctx, 2, x, n, periods, out);
+}
+
+int fmk_stoch_k(fmk_ctx *ctx, const double *close, const double *low, const double *high, int64_t n, int64_t length, double *out)
+{
+    if (length < 1) return fmk_set_error(ctx, FMK_E_ARG, "stoch_k: length must be at least 1.");
+    DevBag bag(ctx);
+    double *d_c, *d_l, *d_h, *d_o;
+    FMK_TRY(bag.up(close, n, &d_c));
+    FMK_TRY(bag.up(low, n, &d_l));
+    FMK_TRY(bag.up(high, n, &d_h));
+    FMK_TRY(bag.out(n, &d_o));
+    FMK_TRY(fmk_stoch_k_dev(ctx, d_c, d_l, d_h, n, length, d_o));
+    return down(ctx, out, (const double *)d_o, n);
+}
+
 }  // extern "C"

@@ -410,6 +410,45 @@ class DeviceTrades:
         x = self.price if series is None else series
         return self._rolling("fmk_variance_ratio_1_4_dev", x, window, c_i64(int(ddof)), C.c_int(ret_type == "log"))
 
+    # ------------------------------------------------------------------ windowed order statistics (csrc/fmk_order.hip)
+    def _f64(self, name: str, *series) -> None:
+        for y in series:
+            if y.dtype != np.float64:
+                raise TypeError(f"{name}: the series must be float64, not {y.dtype}")
+
+    def burst_ratio(self, y: DeviceArray, window: int) -> DeviceArray:
+        """comp_burst_ratio (feature/core/utils.py:92-108) of a resident float64 series: y / its rolling median."""
+        return self._rolling("fmk_burst_ratio_dev", y, window)
+
+    def _lagged(self, name: str, y: DeviceArray, lag: int, message: str) -> DeviceArray:
+        if int(lag) < 0:
+            raise ValueError(message)
+        self._f64(name, y)
+        out = DeviceArray(self.ctx, y.n, np.float64)
+        if y.n:
+            self.ctx.call(name, y.p, c_i64(y.n), c_i64(int(lag)), out.p)
+        return out
+
+    def roc(self, y: DeviceArray, period: int) -> DeviceArray:
+        """roc (feature/core/momentum.py:6-22) of a resident float64 series."""
+        return self._lagged("fmk_roc_dev", y, period, "roc: period must not be negative.")
+
+    def pct_change(self, y: DeviceArray, periods: int) -> DeviceArray:
+        """pct_change (feature/core/utils.py:110-124) of a resident float64 series."""
+        return self._lagged("fmk_pct_change_dev", y, periods, "pct_change: periods must not be negative.")
+
+    def stoch_k(self, close: DeviceArray, low: DeviceArray, high: DeviceArray, length: int) -> DeviceArray:
+        """stoch_k (feature/core/momentum.py:68-112) of three resident float64 series of one length."""
+        if int(length) < 1:
+            raise ValueError("stoch_k: length must be at least 1.")
+        self._f64("fmk_stoch_k_dev", close, low, high)
+        if not close.n == low.n == high.n:
+            raise ValueError("stoch_k: close, low and high must have the same length.")
+        out = DeviceArray(self.ctx, close.n, np.float64)
+        if close.n:
+            self.ctx.call("fmk_stoch_k_dev", close.p, low.p, high.p, c_i64(close.n), c_i64(int(length)), out.p)
+        return out
+
     # ------------------------------------------------------------------ event sampling
     def cusum_filter(self, threshold, series: Optional[DeviceArray] = None) -> DeviceArray:
         """cusum_filter (sampling/filters.py:7-70) on a resident float64 series (default: the price column) -> int64 event indices

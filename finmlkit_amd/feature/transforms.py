@@ -1,13 +1,14 @@
 """The tick-level transforms of the hot path: `ReturnT`, `EWMST`, `RealizedVolatility` (+ `Compose`), the rolling-window moments
-`SMA`, `ZScore` and `VarianceRatio14` (reference transforms.py:549-574, :335-359, :867-897), and the structural-break transform
-`CUSUMTest` (reference transforms.py:631-708).
+`SMA`, `ZScore` and `VarianceRatio14` (reference transforms.py:549-574, :335-359, :867-897), the windowed order statistics
+`BurstRatio`, `ROC`, `PctChange` and `StochK` (reference transforms.py:362-385, :155-177, :180-203, :276-305), and the
+structural-break transform `CUSUMTest` (reference transforms.py:631-708).
 
 Counterparts of finmlkit/feature/transforms.py:89-117 (ReturnT), :308-332 (EWMST) and the
 pipeline part of finmlkit/feature/kit.py:Compose (:630-720), enough to run the QuickStart flow
     Compose(ReturnT(window, input_col="price"), EWMST(half_life))(trades.data)
 on the MI355X.  The reference's `backend="nb"` (Numba) and `"pd"` both map to the HIP path here
 (the reference's own `_pd` of these two transforms already delegates to the Numba kernel).
-The other ~34 bar-level transforms of the reference are out of scope.
+The other ~30 bar-level transforms of the reference are out of scope.
 """
 from __future__ import annotations
 
@@ -20,7 +21,8 @@ from .. import _ffi
 from .._ffi import DeviceArray, c_f64, c_i64
 from .core.structural_break.cusum import cusum_test_rolling
 from .core.ma import sma
-from .core.utils import comp_lagged_returns, comp_zscore
+from .core.momentum import LENGTH_MESSAGE, PERIOD_MESSAGE, roc, stoch_k
+from .core.utils import PERIODS_MESSAGE, comp_burst_ratio, comp_lagged_returns, comp_zscore, pct_change
 from .core.volatility import ewmst, realized_vol, variance_ratio_1_4_core
 
 
@@ -199,6 +201,121 @@ class VarianceRatio14(_Rolling):
 
     def _c_args(self):
         return (c_i64(int(self.ddof)), C.c_int(self.ret_type == "log"))
+
+
+class BurstRatio(_Rolling):
+    """series / rolling median (reference transforms.py:362-385)."""
+    _host = staticmethod(comp_burst_ratio)
+    _entry = "fmk_burst_ratio_dev"
+
+    def __init__(self, window: int, input_col: str):
+        super().__init__(input_col, f"burst{window}")
+        self.window = window
+
+
+class _Lagged(SISOTransform):
+    """An elementwise function of x[t] and x[t - periods] (csrc/fmk_order.hip)."""
+    _host = None
+    _entry = ""
+    _message = ""
+
+    def _hip(self, x):
+        res = type(self)._host(np.asarray(self._prepare_input_nb(x), dtype=np.float64), self.periods)
+        return self._prepare_output_nb(x.index, res)
+
+    def _dev(self, ts, y):
+        if int(self.periods) < 0:
+            raise ValueError(self._message)
+        out = DeviceArray(ts.ctx, y.n, np.float64)
+        if y.n:
+            ts.ctx.call(self._entry, y.p, c_i64(y.n), c_i64(int(self.periods)), out.p)
+        return out
+
+
+class ROC(_Lagged):
+    """Rate of change in percent (reference transforms.py:155-177; both backends are the kernel, as the reference's `_pd` falls
+    back to Numba)."""
+    _host = staticmethod(roc)
+    _entry = "fmk_roc_dev"
+    _message = PERIOD_MESSAGE
+
+    def __init__(self, periods: int, input_col: str = "close"):
+        super().__init__(input_col, f"roc{periods}")
+        self.periods = periods
+
+
+class PctChange(_Lagged):
+    """Percentage change over a lag (reference transforms.py:180-203).  backend="pd" is pandas' own `Series.pct_change`, as in the
+    reference: it divides by a base <= 0 where the kernel gives NaN, and it returns the series under the input column's name."""
+    _host = staticmethod(pct_change)
+    _entry = "fmk_pct_change_dev"
+    _message = PERIODS_MESSAGE
+
+    def __init__(self, window: int, input_col: str = "close"):
+        super().__init__(input_col, f"pctc{window}")
+        self.periods = window
+
+    def _pd(self, x):
+        return x[self.requires[0]].pct_change(self.periods)
+
+    def __call__(self, x: pd.DataFrame, *, backend: str = "nb") -> pd.Series:
+        assert backend in ("pd", "nb", "hip"), "Backend must be 'pd', 'nb' or 'hip'."
+        self._validate_input(x)
+        return self._pd(x) if backend == "pd" else self._hip(x)
+
+
+class MISOTransform:
+    """Multiple-input single-output transform with the reference's interface (feature/base.py:504-716): `requires` lists the input
+    columns, the output column is named `produces[0]` without an input prefix, `_prepare_input_nb` gives a dict of arrays."""
+
+    def __init__(self, input_cols, output_col: str):
+        self.requires = [input_cols] if isinstance(input_cols, str) else list(input_cols)
+        self.produces = [output_col]
+
+    @property
+    def output_name(self) -> str:
+        return self.produces[0]
+
+    def _validate_input(self, x) -> bool:
+        if not isinstance(x, pd.DataFrame):
+            raise TypeError("Input must be a pandas DataFrame")
+        missing_cols = [col for col in self.requires if col not in x.columns]
+        if missing_cols:
+            raise ValueError(f"Input columns {missing_cols} not found in DataFrame")
+        return True
+
+    def _prepare_input_nb(self, x: pd.DataFrame):
+        return {col: x[col].values for col in self.requires}
+
+    def _prepare_output_nb(self, idx, y) -> pd.Series:
+        return pd.Series(y, index=idx, name=self.output_name)
+
+    def __call__(self, x: pd.DataFrame, *, backend: str = "nb") -> pd.Series:
+        assert backend in ("pd", "nb", "hip"), "Backend must be 'pd', 'nb' or 'hip'."
+        self._validate_input(x)
+        return self._hip(x)
+
+    def _hip(self, x):
+        raise NotImplementedError
+
+
+class StochK(MISOTransform):
+    """Stochastic oscillator %K (reference transforms.py:276-305).  The reference hands its columns (high, low, close) to a core
+    function declared (close, low, high): the `high` column takes the place of `close` and the `close` column that of `high`.
+    The transform's output is the reference's, so the same call is made here; `core.momentum.stoch_k` keeps the declared order."""
+
+    def __init__(self, length: int = 14, input_cols=None):
+        if input_cols is None:
+            input_cols = ["high", "low", "close"]
+        super().__init__(input_cols, f"stochk{length}")
+        self.length = length
+
+    def _hip(self, x):
+        if int(self.length) < 1:
+            raise ValueError(LENGTH_MESSAGE)
+        cols = self._prepare_input_nb(x)
+        high, low, close = (np.asarray(cols[c], dtype=np.float64) for c in self.requires[:3])
+        return self._prepare_output_nb(x.index, stoch_k(high, low, close, self.length))
 
 
 class SIMOTransform:

@@ -417,6 +417,32 @@ int fmk_variance_ratio_1_4_dev(fmk_ctx *ctx, const double *d_price, int64_t n, i
                                double *d_out);
 int fmk_variance_ratio_1_4(fmk_ctx *ctx, const double *price, int64_t n, int64_t window, int64_t ddof, int is_log, double *out);
 
+/* ---- windowed order statistics: finmlkit/feature/core/utils.py (comp_burst_ratio, pct_change), momentum.py (roc, stoch_k) on float64
+ * series of n elements -> one float64 array of n elements.  A median, a minimum and a maximum are selections without an evaluation
+ * order; the arithmetic after them is the reference's, one rounded operation each, nothing contracted: every output is the
+ * reference's bits (its pure-Python mode), NaN positions included.
+ *   burst_ratio: NaN before window - 1 (everywhere when window > n); W = x[i - window + 1 .. i]: NaN when W holds a NaN (np.median),
+ *             med = the middle element of sorted W (odd window) or (a + b) / 2.0 over the two middle ones (even window),
+ *             out = x[i] / med when med > 0, NaN otherwise.  Windows up to 3073 sort a tile's span in LDS; longer ones select by
+ *             bisection over the key's bits (csrc/fmk_order.hip); no window <= n is refused.
+ *   stoch_k:  NaN before length - 1 (everywhere when length > n); lo = min(low[W]), hi = max(high[W]),
+ *             out = (100.0 * (close[t] - lo)) / (hi - lo) when hi > lo, NaN otherwise and when low or high holds a NaN in W (the
+ *             reference carries its extremes and is path-dependent there: a documented deviation).  Signed zeros among low / high
+ *             are not part of the contract.
+ *   roc:      NaN before period; ((x[i] - x[i - period]) / x[i - period]) * 100.0, a zero divisor giving the IEEE result.
+ *   pct_change: NaN before periods; base = x[t - periods]: (x[t] - base) / base when base > 0, NaN otherwise.
+ * No scratch memory is taken.  FMK_E_ARG, checked before a device is touched and before any pointer is looked at: window < 1,
+ * length < 1, period < 0, periods < 0, n >= 2^31. */
+int fmk_burst_ratio_dev(fmk_ctx *ctx, const double *d_x, int64_t n, int64_t window, double *d_out);
+int fmk_burst_ratio(fmk_ctx *ctx, const double *x, int64_t n, int64_t window, double *out);
+int fmk_stoch_k_dev(fmk_ctx *ctx, const double *d_close, const double *d_low, const double *d_high, int64_t n, int64_t length,
+                    double *d_out);
+int fmk_stoch_k(fmk_ctx *ctx, const double *close, const double *low, const double *high, int64_t n, int64_t length, double *out);
+int fmk_roc_dev(fmk_ctx *ctx, const double *d_x, int64_t n, int64_t period, double *d_out);
+int fmk_roc(fmk_ctx *ctx, const double *x, int64_t n, int64_t period, double *out);
+int fmk_pct_change_dev(fmk_ctx *ctx, const double *d_x, int64_t n, int64_t periods, double *d_out);
+int fmk_pct_change(fmk_ctx *ctx, const double *x, int64_t n, int64_t periods, double *out);
+
 /* ---- labels and sample weights on the tick tape: finmlkit/label/tbm.py, label/weights.py ------------------------
  * triple_barrier (tbm.py:11-158) on the raw tape.  Per event: label (side labels -1 / +1; meta labels 0 / 1 when d_side is given),
  * index of the first barrier touch, the return there and the max return / barrier ratio.  Labels, touch indices, returns and ratios
