@@ -44,6 +44,63 @@ def distinct_sizes(n, seed):
     return (np.random.default_rng(seed).permutation(n) + 1) / 8.0
 
 
+SUBNORMAL = 5e-324                    # the smallest positive float64
+HOSTILE = (0.0, -0.0, SUBNORMAL, -2.5e-310, math.inf, -math.inf, sys.float_info.max)
+
+
+def _magnitudes(rng, n):
+    """exp(normal(0, 3)): all-distinct full-mantissa values over some twenty binades."""
+    return np.exp(rng.normal(0.0, 3.0, n))
+
+
+def signed_sizes(n, seed, share=0.01):
+    """All-distinct full-mantissa magnitudes, about 45 % of them negated, then `share` of the elements each overwritten with 0.0,
+    -0.0, the smallest subnormal, a negative subnormal, +inf, -inf and DBL_MAX.  No NaN."""
+    rng = np.random.default_rng(seed)
+    x = _magnitudes(rng, n)
+    x[rng.random(n) < 0.45] *= -1.0
+    cls = rng.random(n)
+    for k, v in enumerate(HOSTILE):
+        x[(cls >= k * share) & (cls < (k + 1) * share)] = v
+    return x
+
+
+def alternating_sizes(n, seed):
+    """The same magnitudes, negative at even indices and positive at odd ones: the median of an odd window alternates between the
+    largest negative and the smallest positive element, that of an even window is their mean."""
+    x = _magnitudes(np.random.default_rng(seed), n)
+    x[0::2] *= -1.0
+    return x
+
+
+def signed_ohlc_walk(n, seed, hostile=False):
+    """-> (close, low, high) around zero: a cumulative sum of normals that crosses it, `low` / `high` at random distances, -inf
+    planted once in `low` (index 40) and +inf once in `high` (index n - 41; both only where n >= 100).  hostile: `low` and `high`
+    are signed_sizes series instead, sorted into order element by element, and `close` lies between them or on one of them."""
+    rng = np.random.default_rng(seed)
+    if hostile:
+        a, b = signed_sizes(n, seed + 1, 0.02), signed_sizes(n, seed + 2, 0.02)
+        low, high = np.minimum(a, b), np.maximum(a, b)
+        pick = rng.integers(0, 3, n)
+        with np.errstate(all="ignore"):
+            mid = low / 2.0 + high / 2.0
+        close = np.where(pick == 0, low, np.where(pick == 1, high, np.where(np.isnan(mid), 0.0, mid)))
+        return close, low, high
+    close = np.cumsum(rng.normal(0.0, 1.0, n))
+    close -= close[n // 2]                                       # zero in the middle: both signs occur
+    low, high = close - rng.exponential(0.5, n), close + rng.exponential(0.5, n)
+    if n >= 100:
+        low[40], high[n - 41] = -math.inf, math.inf
+    return close, low, high
+
+
+def nan_canonical(a):
+    """a with every NaN replaced by the canonical quiet NaN (what the hashes of large outputs are taken over)."""
+    a = np.array(a, dtype=np.float64)
+    a[np.isnan(a)] = np.nan
+    return a
+
+
 def ohlc_walk(n, seed, step=35, spread=30, hold=0.0):
     """-> (close, low, high) on a 0.01 grid in integer arithmetic: a walk and non-negative distances below and above it.  With
     probability `hold` a bar repeats the close and has low == high == close."""

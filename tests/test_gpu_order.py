@@ -1,7 +1,8 @@
 """The windowed order statistics on the MI355X -- comp_burst_ratio, stoch_k, roc, pct_change (csrc/fmk_order.hip) -- bit-equal
 (np.array_equal, equal_nan=True) to the untouched reference's recorded outputs (tests/golden/order_stats.npz) and to the plain
 restatement of tests/_order_ref.py.  There is no tolerance: a median, a minimum and a maximum are selections, and what follows them
-is one or two IEEE operations in the reference's order."""
+is one or two IEEE operations in the reference's order.  Signed and infinite values, planted elements, NaN-saturated spans and the
+second trip of the grid-stride loops: tests/test_gpu_order_edges.py."""
 import ctypes as C
 
 import numpy as np
@@ -9,7 +10,7 @@ import pytest
 
 from tests import _counts
 from tests import _order_ref as H
-from tests.test_order_host import MANIFEST, OK_CASES, REFUSED, case_input, expected, product
+from tests.test_order_host import MANIFEST, OK_CASES, REFUSED, VALUE_CLASS_CASES, case_input, expected, product
 
 pytestmark = pytest.mark.gpu
 
@@ -30,15 +31,24 @@ def equal(got, want, what):
     assert np.array_equal(got, want, equal_nan=True), (what, len(bad), bad[:5], got[bad[:3]], want[bad[:3]])
 
 
-def dev_call(fn, inputs, arg, ctx=None):
-    """The `_dev` entry of `fn` on resident copies of the inputs -> host array."""
+def equal_bits(got, want, what):
+    """equal(), and where both are zero they have the same sign (burst ratio, roc and pct_change: the reference decides it)."""
+    equal(got, want, what)
+    got, want = np.asarray(got), np.asarray(want)
+    bad = np.nonzero((got == 0) & (want == 0) & (np.signbit(got) != np.signbit(want)))[0]
+    assert len(bad) == 0, (what, "the sign of a zero", len(bad), bad[:5], got[bad[:3]], want[bad[:3]])
+
+
+def dev_call(fn, inputs, arg, ctx=None, prefill=None):
+    """The `_dev` entry of `fn` on resident copies of the inputs -> host array.  prefill: what the output buffer holds before the
+    call, so that an element the kernels do not write shows."""
     from finmlkit_amd import _ffi
     from finmlkit_amd._ffi import DeviceArray
     ctx = ctx or _ffi.default_context()
     ins = inputs if isinstance(inputs, tuple) else (inputs,)
     n = len(ins[0])
     dev = [DeviceArray.from_host(ctx, np.ascontiguousarray(a, dtype=np.float64)) for a in ins]
-    out = DeviceArray(ctx, n, np.float64)
+    out = DeviceArray(ctx, n, np.float64) if prefill is None else DeviceArray.from_host(ctx, np.full(n, prefill, np.float64))
     ctx.call(ENTRY[fn] + "_dev", *(d.p for d in dev), C.c_int64(n), C.c_int64(arg), out.p)
     return out.to_host()
 
@@ -53,8 +63,18 @@ def series():
     return made
 
 
+@pytest.fixture(scope="module")
+def long_series():
+    """The same kinds of series for the windows of two slabs and more."""
+    n = 13_000
+    made = (H.tie_sizes(n, 711), H.grid_walk(n, 712)) + H.ohlc_walk(n, 713)
+    for a in made:
+        a.setflags(write=False)
+    return made
+
+
 # ---------------------------------------------------------------------------------------------- the recorded cases
-@pytest.mark.parametrize("name", OK_CASES)
+@pytest.mark.parametrize("name", [k for k in OK_CASES if k not in VALUE_CLASS_CASES])      # those: tests/test_gpu_order_edges.py
 def test_fixture_replay(name):
     c, ins = MANIFEST[name], case_input(name)
     equal(H.call(c["fn"], ins, c["arg"], mod=product()), expected(name), name + " (python)")
@@ -100,9 +120,14 @@ BURST_WINDOWS = [(w, TILE) for w in (1, 2, 3, 63, 64, 65, TILE - 1, TILE, TILE +
 BURST_WINDOWS += [(w, WALK_TILE) for w in (SORT_WINDOW_MAX + 1, SORT_WINDOW_MAX + 2, 3687, 3688, ONE_SLAB_WINDOW, ONE_SLAB_WINDOW + 1)]
 
 
+# three slabs (the middle one lies wholly inside every lane's window), and a full tile's span of exactly two slabs and one more
+LONG_WINDOWS = (2 * SLAB - WALK_TILE + 1, 2 * SLAB - WALK_TILE + 2, 8500, 8501)
+BURST_WINDOWS += [(w, WALK_TILE) for w in LONG_WINDOWS]
+
+
 @pytest.mark.parametrize("window,tile", BURST_WINDOWS)
-def test_burst_ratio_geometry(series, window, tile):
-    ties, walk = series[:2]
+def test_burst_ratio_geometry(series, long_series, window, tile):
+    ties, walk = (long_series if window in LONG_WINDOWS else series)[:2]
     P = product()
     compared = 0
     for n in _lengths(window, tile):
@@ -110,18 +135,19 @@ def test_burst_ratio_geometry(series, window, tile):
             x = full[len(full) - n:]                             # the last n elements: another phase of the series at every size
             want = H.comp_burst_ratio(x, window)
             assert np.isfinite(want[window - 1:]).all()
-            equal(P.comp_burst_ratio(x, window), want, f"burst {name} n={n} w={window}")
+            equal_bits(P.comp_burst_ratio(x, window), want, f"burst {name} n={n} w={window}")
             compared += n
     _counts.record(f"order/geometry/burst_w{window}", outputs_compared=compared)
 
 
 # %K: the same edges for the walk kernel's tile and slab
 STOCH_LENGTHS = (1, 2, 3, 63, 64, 65, WALK_TILE - 1, WALK_TILE, WALK_TILE + 1, ONE_SLAB_WINDOW, ONE_SLAB_WINDOW + 1, SLAB + 1)
+STOCH_LENGTHS += LONG_WINDOWS[:3] + (12289,)                     # two slabs exactly, one element more, three slabs, four
 
 
 @pytest.mark.parametrize("length", STOCH_LENGTHS)
-def test_stoch_k_geometry(series, length):
-    close, low, high = series[2:]
+def test_stoch_k_geometry(series, long_series, length):
+    close, low, high = (long_series if length > SLAB + 1 else series)[2:]
     P = product()
     compared = 0
     for n in _lengths(length, WALK_TILE):

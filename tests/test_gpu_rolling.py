@@ -100,6 +100,9 @@ for _w in (ONE_SLAB_WINDOW - 1, ONE_SLAB_WINDOW, ONE_SLAB_WINDOW + 1, SLAB - 1, 
     GEOMETRY += _outputs(_w, (TILE + 1,))                      # where a second slab begins; a window of one slab +-1
 GEOMETRY += _outputs(4915, (5, 2 * TILE + 1))                  # a window of 1.2 slabs
 GEOMETRY += [(20_001, 65), (20_001, TILE + 1), (64, 65), (1, 1)]
+# a full tile's span of exactly two slabs and of one element more; three slabs (the middle one lies wholly inside every window); four
+for _w in (2 * SLAB - TILE + 1, 2 * SLAB - TILE + 2, 8500, 12289):
+    GEOMETRY += _outputs(_w, (TILE + 1,))
 
 
 @pytest.mark.parametrize("n,window", GEOMETRY)
@@ -120,6 +123,26 @@ def test_geometry(series, n, window):
     if n >= window + 8 and window >= 63:
         assert np.isfinite(want[window + 3:]).all(), (n, window)
     _counts.record(f"rolling/geometry/n{n}_w{window}", outputs_compared=3 * n + len(xr), windows=max(0, n - window + 1))
+
+
+PLANT_WINDOW = 8500                  # three slabs: a span of 8499 + TILE = 9523 elements for the first tile
+
+
+@pytest.mark.parametrize("p", (0, BLOCK - 1, BLOCK, TILE - 1, TILE, SLAB - 1, SLAB, SLAB + BLOCK - 1, 2 * SLAB - 1, 2 * SLAB,
+                               PLANT_WINDOW - 1 + TILE - 1))
+def test_sma_sees_a_planted_element_in_exactly_its_windows(p):
+    """Ones with one 3.0 at span position p of the first tile, two tiles of outputs: the sums are exact integers, 8502 for a window
+    that holds the 3.0 and 8500 for any other; a read skipped or made twice gives another integer."""
+    window, n = PLANT_WINDOW, PLANT_WINDOW - 1 + 2 * TILE
+    x = np.ones(n)
+    x[p] = 3.0
+    t = np.arange(n)
+    holds = (t >= p) & (t < p + window)
+    closed = np.where(t < window - 1, np.nan, (1.0 / window) * np.where(holds, window + 2.0, float(window)))
+    want = H.sma(x, window)
+    assert np.array_equal(want, closed, equal_nan=True) and 0 < holds[window - 1:].sum()
+    equal(product().sma(x, window), want, f"sma, 3.0 planted at {p}")
+    _counts.record(f"rolling/planted/sma_p{p}", outputs_compared=n)
 
 
 def test_nan_runs_across_a_tile_edge(series):

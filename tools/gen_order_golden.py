@@ -2,13 +2,19 @@
 """Writes tests/golden/order_stats.npz + order_stats.json: outputs of the REFERENCE's windowed order statistics -- comp_burst_ratio
 and pct_change (feature/core/utils.py), roc and stoch_k (feature/core/momentum.py) -- on seeded series that the tests regenerate
 (tests/_order_ref.py: grid walks, a tie-heavy size series drawn from 8 levels, all-distinct values, OHLC walks; integer arithmetic),
-on series with NaN runs, +-inf, zeros and negative values, on a zero median, on the edge lengths, on the calls of the reference's
+on signed full-mantissa series with zeros of both signs, subnormals, +-inf and DBL_MAX at every window at which the kernels change
+path (signed_sizes, alternating_sizes, signed_ohlc_walk), on series with NaN runs, +-inf, zeros and negative values, on a zero median, on the edge lengths, on the calls of the reference's
 own tests, and the refused arguments.  Build container only: imports the reference in pure-Python mode through oracle/shim, like
 tools/gen_rolling_golden.py; no GPU, nothing of the product.
 
 No sum, log or exp occurs in these functions, so the truth is the UNTOUCHED reference: nothing is substituted in its `np`.  A case
-is refused unless the reference and both forms of tests/_order_ref.py agree in every element, NaN positions included.  stoch_k
-cases hold no NaN in low / high (the reference is path-dependent there; the project's rule is tested against the restatement).
+is refused unless the reference and both forms of tests/_order_ref.py agree in every element, NaN positions included, and for
+burst ratio, roc and pct_change in the sign of every zero (np.signbit).  %K stays on `==`: np.min / np.max over a window that holds
+-0.0 and 0.0 has no defined winner, the reference's running min() / max() another one, and only the sign of a zero result can
+differ.  stoch_k cases hold no NaN in low / high (the reference is path-dependent there; the project's rule is tested against the
+restatement).  Cases of more than 2100 elements record `output_sha256` (over the output's bytes, every NaN made the canonical quiet
+NaN) instead of the output: the host test recomputes it from the vector form, which gates the restatement on the reference at full
+size.  The scalar form is slow and left out of the gate above a window of 4000.
     python tools/gen_order_golden.py [reference checkout]
 """
 import json
@@ -40,7 +46,14 @@ class Reference:
     stoch_k = staticmethod(lambda c, lo, hi, n: RMO.stoch_k(c, lo, hi, n))
 
 
-GENERATORS = {"grid_walk": H.grid_walk, "tie_sizes": H.tie_sizes, "distinct_sizes": H.distinct_sizes, "ohlc_walk": H.ohlc_walk}
+GENERATORS = {"grid_walk": H.grid_walk, "tie_sizes": H.tie_sizes, "distinct_sizes": H.distinct_sizes, "ohlc_walk": H.ohlc_walk,
+              "signed_sizes": H.signed_sizes, "alternating_sizes": H.alternating_sizes, "signed_ohlc_walk": H.signed_ohlc_walk}
+STORED_MAX = 2100                      # longer cases record the hash of their output, not the output
+SCALAR_MAX = 4000                      # the scalar form of the restatement is gated up to this window
+SORT_TILE, SORT_WINDOW_MAX, WALK_TILE = 1024, 3073, 256     # csrc/fmk_order.hip: ORD_TILE, ORD_SORT_WINDOW_MAX, ORD_WALK_TILE
+# alternating_sizes: the seed per even window at which a quarter of the medians and more is positive and a quarter and more is not
+# (tests/test_order_host.py asserts the shares); odd windows alternate at any seed
+ALT_SEEDS = {20: 1, 3072: 1, 3074: 80, 3842: 82, 8500: 76}
 
 
 def case(fn, inputs, arg, gen=None, args=None):
@@ -74,6 +87,23 @@ def series_cases():
         out[f"walk.stoch_l{length}"] = seeded("stoch", length, "ohlc_walk", n, 580 + k, 35, 30, 0.0)
     for k, length in enumerate((1, 2, 5, 14)):              # flat stretches: hi == lo gives NaN
         out[f"held.stoch_l{length}"] = seeded("stoch", length, "ohlc_walk", n, 590 + k, 2, 1, 0.9)
+    return out
+
+
+def value_class_cases():
+    """Negative, zero, subnormal, infinite and DBL_MAX values through every path of the kernels: the sorted span at both its key
+    widths' ends (windows 20 / 21, and 3072 / 3073 at 4096 entries), the bisection over one, two and three slabs."""
+    out = {}
+    for k, w in enumerate((20, 21, 3072, 3073, 3074, 3075, 3842, 8500, 8501, 12289)):
+        n = w - 1 + (SORT_TILE if w <= SORT_WINDOW_MAX else WALK_TILE) + 1       # a full tile and a tile of one output
+        out[f"signed.burst_w{w}"] = seeded("burst", w, "signed_sizes", n, 640 + k)
+        out[f"alt.burst_w{w}"] = seeded("burst", w, "alternating_sizes", n, ALT_SEEDS.get(w, 5))
+    for k, length in enumerate((14, 4097, 8500, 12289)):
+        out[f"signed.stoch_l{length}"] = seeded("stoch", length, "signed_ohlc_walk", length - 1 + WALK_TILE + 1, 660 + k)
+    out["hostile.stoch_l14"] = seeded("stoch", 14, "signed_ohlc_walk", 14 - 1 + 2 * WALK_TILE + 1, 21, True)
+    for p in (0, 1, 300):
+        out[f"signed.roc_p{p}"] = seeded("roc", p, "signed_sizes", 2000, 670)
+        out[f"signed.pct_p{p}"] = seeded("pct", p, "signed_sizes", 2000, 670)
     return out
 
 
@@ -155,14 +185,20 @@ def run(mod, c, **kw):
         return ("raises", type(e).__name__, str(e))
 
 
-def differs(a, b):
-    return int((~((a == b) | (np.isnan(a) & np.isnan(b)))).sum()) if a.shape == b.shape else -1
+def differs(a, b, signs=False):
+    """The elements in which a and b differ (NaN equals NaN); signs: a zero of the other sign differs as well."""
+    if a.shape != b.shape:
+        return -1
+    bad = ~((a == b) | (np.isnan(a) & np.isnan(b)))
+    if signs:
+        bad |= (a == b) & (np.signbit(a) != np.signbit(b))
+    return int(bad.sum())
 
 
 def main():
     out, manifest = {}, {}
     cases = {}
-    for group in (series_cases, odd_cases, length_cases, reference_test_calls, refused_calls):
+    for group in (series_cases, value_class_cases, odd_cases, length_cases, reference_test_calls, refused_calls):
         cases.update(group())
     for name, c in cases.items():
         ins = c["inputs"] if c["fn"] == "stoch" else (c["inputs"],)
@@ -173,7 +209,8 @@ def main():
         else:
             for k, a in enumerate(ins):
                 out[f"{name}.in{k}"] = a
-        own = [run(None, c, form=form) for form in ("scalar", "vector")]
+        forms = ("scalar", "vector") if c["arg"] <= SCALAR_MAX else ("vector",)
+        own = [run(None, c, form=form) for form in forms]
         ref = run(Reference, c)
         if name.startswith("refused."):
             if not all(o[0] == "raises" and o[1] == "ValueError" and o[1:] == own[0][1:] for o in own):
@@ -185,15 +222,19 @@ def main():
             continue
         if ref[0] != "ok":
             raise SystemExit(f"{name}: the reference raises {ref[1:]} -- case refused")
-        for form, o in zip(("scalar", "vector"), own):
-            if o[0] != "ok" or differs(ref[1], o[1]) != 0:
-                raise SystemExit(f"{name}: reference and helper ({form}) disagree ({o[0]}, {differs(ref[1], o[1]) if o[0] == 'ok' else o[1:]})"
+        signs = c["fn"] != "stoch"
+        for form, o in zip(forms, own):
+            if o[0] != "ok" or differs(ref[1], o[1], signs) != 0:
+                raise SystemExit(f"{name}: reference and helper ({form}) disagree ({o[0]}, {differs(ref[1], o[1], signs) if o[0] == 'ok' else o[1:]})"
                                  " -- case refused")
-        out[name + ".out"] = ref[1]
+        if len(ref[1]) <= STORED_MAX:
+            out[name + ".out"] = ref[1]
+        else:
+            entry["output_sha256"] = H.sha256(H.nan_canonical(ref[1]))
         entry.update(finite=int(np.isfinite(ref[1]).sum()), nan=int(np.isnan(ref[1]).sum()))
         manifest[name] = entry
     for k in sorted(manifest):
-        print(k, {a: b for a, b in manifest[k].items() if a != "input_sha256"})
+        print(k, {a: b for a, b in manifest[k].items() if not a.endswith("_sha256")})
     gold = os.path.join(ROOT, "tests", "golden")
     np.savez_compressed(os.path.join(gold, "order_stats.npz"), **out)
     with open(os.path.join(gold, "order_stats.json"), "w") as fh:
