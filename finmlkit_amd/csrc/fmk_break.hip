@@ -13,6 +13,8 @@
 // sqrt(k) are wave-uniform for every t (rolling and developing alike; lanes with a shorter window join late).  The span
 // [base(t0), t1 - 1) of the tile is staged in LDS in slabs of at most BRK_SLAB_MAX elements -- d2 for the pass that sums S, then y
 // for the pass over the pairs; a lane takes from each slab the part of its own range that lies in it, in ascending order.
+// Not the walk of fmk_window.h, which the fixed-window features share: here k runs downwards over per-lane ranges of different
+// length (developing windows), and the wave's bounds are max / min reductions over its lanes.
 #include <limits.h>
 #include <stdlib.h>
 
@@ -186,9 +188,8 @@ int brk_run(fmk_ctx *ctx, const double *d_x, int64_t n, int64_t window, int64_t 
     void *work;
     FMK_TRY(fmk_alloc(ctx, (size_t)(2 * n + 2 * nk) * sizeof(double), &work));
     double *y = (double *)work, *d2 = y + n, *sqk = d2 + n, *crit = sqk + nk;
-    int64_t blocks = fmk_ceil_div(n, 256);
-    if (blocks > (int64_t)ctx->n_cu * 16) blocks = (int64_t)ctx->n_cu * 16;
-    k_brk_log<<<(unsigned)blocks, 256, 0, ctx->stream>>>(d_x, n, y, &mail->nonpos);
+    const unsigned blocks = fmk_grid_blocks(ctx, n);
+    k_brk_log<<<blocks, 256, 0, ctx->stream>>>(d_x, n, y, &mail->nonpos);
     hipError_t le = hipGetLastError();
     int rc = le != hipSuccess ? fmk_set_error(ctx, FMK_E_HIP, "cusum_test: %s", hipGetErrorString(le)) : FMK_OK;
     if (rc == FMK_OK && rolling) {
@@ -197,7 +198,7 @@ int brk_run(fmk_ctx *ctx, const double *d_x, int64_t n, int64_t window, int64_t 
         if (rc == FMK_OK && nonpos) rc = fmk_set_error(ctx, FMK_E_ARG, "All close prices must be positive.");
     }
     if (rc == FMK_OK) {
-        k_brk_prep<<<(unsigned)blocks, 256, 0, ctx->stream>>>(y, n, d2, sqk, crit, nk, d_up, d_down, d_cup, d_cdn,
+        k_brk_prep<<<blocks, 256, 0, ctx->stream>>>(y, n, d2, sqk, crit, nk, d_up, d_down, d_cup, d_cdn,
                                                             compute ? (warmup < n ? warmup : n) : n);
         le = hipGetLastError();
         if (le != hipSuccess) rc = fmk_set_error(ctx, FMK_E_HIP, "cusum_test: %s", hipGetErrorString(le));

@@ -207,6 +207,43 @@ int fmk_long_bar_list(fmk_ctx *ctx, const int64_t *d_close_idx, int64_t nb, int6
 
 static inline int64_t fmk_ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
 
+// the workgroups of a 256-lane grid-stride kernel over n elements: at most 16 per CU, at least one
+static inline unsigned fmk_grid_blocks(const fmk_ctx *ctx, int64_t n)
+{
+    int64_t blocks = fmk_ceil_div(n, 256);
+    if (blocks > (int64_t)ctx->n_cu * 16) blocks = (int64_t)ctx->n_cu * 16;
+    return (unsigned)(blocks > 0 ? blocks : 1);
+}
+// NaN in d_out[0 .. min(window - 1, n)): the outputs before the first full window (fmk_rolling.hip)
+int fmk_nan_head(fmk_ctx *ctx, double *d_out, int64_t n, int64_t window);
+
+// What the series entries (fmk_rolling.hip, fmk_order.hip) refuse before any pointer is looked at and before a device is needed;
+// the host-pointer flavours (fmk_host.hip) ask the argument rules before any upload.  what: the name the _dev entry puts in front.
+static inline int fmk_series_check(fmk_ctx *ctx, const char *what, int64_t n)
+{
+    if (n < 0 || n >= ((int64_t)1 << 31)) return fmk_set_error(ctx, FMK_E_ARG, "%s: the series must hold fewer than 2^31 elements.", what);
+    return FMK_OK;
+}
+static inline int fmk_rule_least(fmk_ctx *ctx, int64_t arg, int64_t least, const char *message)
+{
+    return arg < least ? fmk_set_error(ctx, FMK_E_ARG, "%s", message) : FMK_OK;
+}
+static inline int fmk_rule_window(fmk_ctx *ctx, const char *what, int64_t window)
+{
+    if (what && window < 1) return fmk_set_error(ctx, FMK_E_ARG, "%s: window must be at least 1.", what);
+    return fmk_rule_least(ctx, window, 1, "window must be at least 1.");
+}
+static inline int fmk_rule_zscore(fmk_ctx *ctx, int64_t window, int64_t ddof)
+{
+    return ddof >= window ? fmk_set_error(ctx, FMK_E_ARG, "comp_zscore: window - ddof must be positive.") : FMK_OK;
+}
+static inline int fmk_rule_roc(fmk_ctx *ctx, int64_t period) { return fmk_rule_least(ctx, period, 0, "roc: period must not be negative."); }
+static inline int fmk_rule_pct_change(fmk_ctx *ctx, int64_t periods)
+{
+    return fmk_rule_least(ctx, periods, 0, "pct_change: periods must not be negative.");
+}
+static inline int fmk_rule_stoch_k(fmk_ctx *ctx, int64_t length) { return fmk_rule_least(ctx, length, 1, "stoch_k: length must be at least 1."); }
+
 // One excursion of a call onto the context's auxiliary stream (fmk_api.hip), the only way there.  Rules:
 //  - one fork per context at a time: fork() while another FmkSide of the context is open is an error;
 //  - the context scratch belongs to the context's stream: fmk_scratch inside run() is an error;

@@ -56,6 +56,20 @@ int down(fmk_ctx *ctx, T *host, const T *dev, int64_t count)
     return fmk_d2h(ctx, host, dev, sizeof(T) * (size_t)count);
 }
 
+// the rolling-window moments (fmk_rolling.hip) and order statistics (fmk_order.hip): one series up, dev(d_x, d_out), one series
+// down.  rule: the entry's argument rule (fmk_common.h), asked before anything is uploaded
+template <typename Dev>
+int series_host(fmk_ctx *ctx, int rule, const double *x, int64_t n, double *out, Dev dev)
+{
+    FMK_TRY(rule);
+    DevBag bag(ctx);
+    double *d_x, *d_o;
+    FMK_TRY(bag.up(x, n, &d_x));
+    FMK_TRY(bag.out(n, &d_o));
+    FMK_TRY(dev(d_x, d_o));
+    return down(ctx, out, (const double *)d_o, n);
+}
+
 }  // namespace
 
 extern "C" {
@@ -543,76 +557,55 @@ int fmk_cusum_test_developing(fmk_ctx *ctx, const double *x, int64_t n, int64_t 
     return cusum_test_host(ctx, x, n, -1, warmup_period, up, dn, crit_up, crit_down);
 }
 
-// the rolling-window moments (fmk_rolling.hip): one series up, one down.  which: 0 sma, 1 zscore, 2 rolling variance, 3 variance ratio
-static int rolling_host(fmk_ctx *ctx, int which, const double *x, int64_t n, int64_t window, int64_t ddof, int64_t extra, double *out)
-{
-    if (window < 1) return fmk_set_error(ctx, FMK_E_ARG, "window must be at least 1.");
-    if (which == 1 && ddof >= window) return fmk_set_error(ctx, FMK_E_ARG, "comp_zscore: window - ddof must be positive.");
-    DevBag bag(ctx);
-    double *d_x, *d_o;
-    FMK_TRY(bag.up(x, n, &d_x));
-    FMK_TRY(bag.out(n, &d_o));
-    if (which == 0) FMK_TRY(fmk_sma_dev(ctx, d_x, n, window, d_o));
-    else if (which == 1) FMK_TRY(fmk_zscore_dev(ctx, d_x, n, window, ddof, d_o));
-    else if (which == 2) FMK_TRY(fmk_rolling_variance_dev(ctx, d_x, n, window, ddof, extra, d_o));
-    else FMK_TRY(fmk_variance_ratio_1_4_dev(ctx, d_x, n, window, ddof, (int)extra, d_o));
-    return down(ctx, out, (const double *)d_o, n);
-}
-
+// the rolling-window moments (fmk_rolling.hip) and order statistics (fmk_order.hip) through series_host
 int fmk_sma(fmk_ctx *ctx, const double *x, int64_t n, int64_t window, double *out)
 {
-    return rolling_host(ctx, 0, x, n, window, 0, 0, out);
+    return series_host(ctx, fmk_rule_window(ctx, nullptr, window), x, n, out,
+                       [=](const double *d_x, double *d_o) { return fmk_sma_dev(ctx, d_x, n, window, d_o); });
 }
 
 int fmk_zscore(fmk_ctx *ctx, const double *x, int64_t n, int64_t window, int64_t ddof, double *out)
 {
-    return rolling_host(ctx, 1, x, n, window, ddof, 0, out);
+    FMK_TRY(fmk_rule_window(ctx, nullptr, window));
+    return series_host(ctx, fmk_rule_zscore(ctx, window, ddof), x, n, out,
+                       [=](const double *d_x, double *d_o) { return fmk_zscore_dev(ctx, d_x, n, window, ddof, d_o); });
 }
 
 int fmk_rolling_variance(fmk_ctx *ctx, const double *x, int64_t n, int64_t window, int64_t ddof, int64_t min_periods, double *out)
 {
-    return rolling_host(ctx, 2, x, n, window, ddof, min_periods, out);
+    return series_host(ctx, fmk_rule_window(ctx, nullptr, window), x, n, out, [=](const double *d_x, double *d_o) {
+        return fmk_rolling_variance_dev(ctx, d_x, n, window, ddof, min_periods, d_o);
+    });
 }
 
 int fmk_variance_ratio_1_4(fmk_ctx *ctx, const double *price, int64_t n, int64_t window, int64_t ddof, int is_log, double *out)
 {
-    return rolling_host(ctx, 3, price, n, window, ddof, is_log != 0, out);
-}
-
-// the windowed order statistics (fmk_order.hip): one series up (three for %K), one down.  which: 0 burst ratio, 1 roc, 2 pct_change
-static int order_host(fmk_ctx *ctx, int which, const double *x, int64_t n, int64_t arg, double *out)
-{
-    if (which == 0 && arg < 1) return fmk_set_error(ctx, FMK_E_ARG, "window must be at least 1.");
-    if (which == 1 && arg < 0) return fmk_set_error(ctx, FMK_E_ARG, "roc: period must not be negative.");
-    if (which == 2 && arg < 0) return fmk_set_error(ctx, FMK_E_ARG, "pct_change: periods must not be negative.");
-    DevBag bag(ctx);
-    double *d_x, *d_o;
-    FMK_TRY(bag.up(x, n, &d_x));
-    FMK_TRY(bag.out(n, &d_o));
-    if (which == 0) FMK_TRY(fmk_burst_ratio_dev(ctx, d_x, n, arg, d_o));
-    else if (which == 1) FMK_TRY(fmk_roc_dev(ctx, d_x, n, arg, d_o));
-    else FMK_TRY(fmk_pct_change_dev(ctx, d_x, n, arg, d_o));
-    return down(ctx, out, (const double *)d_o, n);
+    return series_host(ctx, fmk_rule_window(ctx, nullptr, window), price, n, out, [=](const double *d_x, double *d_o) {
+        return fmk_variance_ratio_1_4_dev(ctx, d_x, n, window, ddof, is_log != 0, d_o);
+    });
 }
 
 int fmk_burst_ratio(fmk_ctx *ctx, const double *x, int64_t n, int64_t window, double *out)
 {
-    return order_host(ctx, 0, x, n, window, out);
+    return series_host(ctx, fmk_rule_window(ctx, nullptr, window), x, n, out,
+                       [=](const double *d_x, double *d_o) { return fmk_burst_ratio_dev(ctx, d_x, n, window, d_o); });
 }
 
 int fmk_roc(fmk_ctx *ctx, const double *x, int64_t n, int64_t period, double *out)
 {
-    return order_host(ctx, 1, x, n, period, out);
+    return series_host(ctx, fmk_rule_roc(ctx, period), x, n, out,
+                       [=](const double *d_x, double *d_o) { return fmk_roc_dev(ctx, d_x, n, period, d_o); });
 }
 
 int fmk_pct_change(fmk_ctx *ctx, const double *x, int64_t n, int64_t periods, double *out)
 {
-    return order_host(ctx, 2, x, n, periods, out);
+    return series_host(ctx, fmk_rule_pct_change(ctx, periods), x, n, out,
+                       [=](const double *d_x, double *d_o) { return fmk_pct_change_dev(ctx, d_x, n, periods, d_o); });
 }
 
 int fmk_stoch_k(fmk_ctx *ctx, const double *close, const double *low, const double *high, int64_t n, int64_t length, double *out)
 {
-    if (length < 1) return fmk_set_error(ctx, FMK_E_ARG, "stoch_k: length must be at least 1.");
+    FMK_TRY(fmk_rule_stoch_k(ctx, length));
     DevBag bag(ctx);
     double *d_c, *d_l, *d_h, *d_o;
     FMK_TRY(bag.up(close, n, &d_c));

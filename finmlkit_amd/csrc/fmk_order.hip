@@ -19,12 +19,13 @@
 // sort first, so a window holds a NaN iff one of the first entries (those with key 0) lies in it.
 // Longer windows (k_burst_walk, correct for every window <= n): a workgroup owns ORD_WALK_TILE outputs, one per lane; the key of
 // rank window / 2 is built bit by bit from the top, each bit by one count of the window's keys below the candidate; the counts walk
-// the window in lockstep over LDS slabs as fmk_rolling.hip does.  One more walk gives the largest key below it (even windows).
-// Rolling minimum / maximum (k_stoch): the same lockstep walk, over `low` and then over `high`.
+// the window by the lockstep walk of fmk_window.h, one output per lane.  One more walk gives the largest key below it (even windows).
+// Rolling minimum / maximum (k_stoch): the same walk, over `low` and then over `high`.
 #include <limits.h>
 
 #include "fmk_common.h"
 #include "fmk_median.h"
+#include "fmk_window.h"
 
 #define ORD_BLOCK 256                                    // lanes per workgroup
 #define ORD_OPL 4                                        // sorted path: outputs per lane
@@ -32,7 +33,6 @@
 #define ORD_SPAN_MAX 4096                                // sorted path: entries in LDS (8 B key + 2 B position: 40 KiB, four workgroups per CU)
 #define ORD_SORT_WINDOW_MAX (ORD_SPAN_MAX - ORD_TILE + 1)   // the longest window whose full tile fits
 #define ORD_WALK_TILE ORD_BLOCK                          // walk kernels: outputs per workgroup, one per lane
-#define ORD_SLAB 4096                                    // walk kernels: LDS elements per staging (32 KiB)
 
 namespace {
 
@@ -44,11 +44,6 @@ __device__ __forceinline__ okey_t ord_key(double v)
 {
     const okey_t k = OK64::tokey((okey_t)__double_as_longlong(v));
     return v == v ? k : 0;
-}
-
-__global__ __launch_bounds__(256) void k_ord_nan(double *out, int64_t n)
-{
-    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) out[i] = NAN;
 }
 
 // ---------------------------------------------------------------------------------------------- rolling median, sorted span
@@ -161,46 +156,6 @@ __global__ __launch_bounds__(ORD_BLOCK) void k_burst_sorted(BurstArgs a)
     }
 }
 
-// ---------------------------------------------------------------------------------------------- the lockstep walk of one window per lane
-// A workgroup owns ORD_WALK_TILE outputs; lane l's window is the span elements l .. l + window - 1 of the tile's span of `span`
-// elements, which load(i) gives as 64-bit words.  All lanes walk the position q inside their windows upwards in lockstep (a wave
-// reads 64 consecutive LDS words per step); the span is staged in slabs of `slab` words, from each slab a lane takes the part of its
-// window that lies in it.  stage == false: the (single) slab is in LDS already.  Every lane of the workgroup comes here.
-template <typename Load, typename Take>
-__device__ __forceinline__ void ord_walk(uint64_t *lds, int64_t span, int64_t window, int slab, bool stage, Load load, Take take)
-{
-    const int tid = threadIdx.x;
-    for (int64_t s0 = 0; s0 < span; s0 += slab) {
-        const int len = (int)(span - s0 < (int64_t)slab ? span - s0 : (int64_t)slab);
-        if (stage) {
-            __syncthreads();                             // the readers of the previous slab are done
-            for (int i = tid; i < len; i += ORD_BLOCK) lds[i] = load(s0 + i);
-            __syncthreads();
-        }
-        // the positions q for which the element l + q of some lane l lies in the slab
-        const int64_t qa = s0 - (ORD_BLOCK - 1) > 0 ? s0 - (ORD_BLOCK - 1) : 0;
-        const int64_t qb = window - 1 < s0 + len - 1 ? window - 1 : s0 + len - 1;
-        if (qa > qb) continue;
-        // [fa, fb]: the element of every lane lies in the slab, no lane needs a check
-        const int64_t fa = qa > s0 ? qa : s0;
-        int64_t fb = qb < s0 + len - ORD_BLOCK ? qb : s0 + len - ORD_BLOCK;
-        if (fb < fa) fb = fa - 1;
-        const int64_t hb = fa - 1 < qb ? fa - 1 : qb;
-        for (int64_t q = qa; q <= hb; ++q) {
-            const int64_t i = q - s0 + tid;
-            if ((uint64_t)i < (uint64_t)len) take(lds[i]);
-        }
-        const uint64_t *row = lds + tid;
-        const int ia = (int)(fa - s0), ib = (int)(fb - s0);
-#pragma unroll 4
-        for (int i = ia; i <= ib; ++i) take(row[i]);
-        for (int64_t q = fb + 1; q <= qb; ++q) {
-            const int64_t i = q - s0 + tid;
-            if ((uint64_t)i < (uint64_t)len) take(lds[i]);
-        }
-    }
-}
-
 // ---------------------------------------------------------------------------------------------- rolling median, any window
 __global__ __launch_bounds__(ORD_BLOCK) void k_burst_walk(BurstArgs a)
 {
@@ -214,20 +169,20 @@ __global__ __launch_bounds__(ORD_BLOCK) void k_burst_walk(BurstArgs a)
     const int64_t k2 = a.window >> 1, k1 = (a.window - 1) >> 1;
 
     okey_t mn = OK64::MAXK;                              // the smallest key: 0 iff the window holds a NaN
-    ord_walk(ord_lds, span, a.window, a.slab, true, load, [&](okey_t k) { mn = k < mn ? k : mn; });
+    fmk_window_walk<ORD_BLOCK, 1>(ord_lds, span, a.window, a.slab, true, load, [&](int, okey_t k) { mn = k < mn ? k : mn; });
     // v2: the key of rank k2 = the largest v with count(key < v) <= k2, built from the top bit down
     okey_t v2 = 0;
     for (int b = 63; b >= 0; --b) {
         const okey_t cand = v2 | ((okey_t)1 << b);
         int64_t c = 0;
-        ord_walk(ord_lds, span, a.window, a.slab, restage, load, [&](okey_t k) { c += k < cand ? 1 : 0; });
+        fmk_window_walk<ORD_BLOCK, 1>(ord_lds, span, a.window, a.slab, restage, load, [&](int, okey_t k) { c += k < cand ? 1 : 0; });
         v2 = c <= k2 ? cand : v2;
     }
     okey_t v1 = v2;
     if (k1 != k2) {                                      // even window: rank k2 - 1 is v2 again when more than k1 keys lie below...
         int64_t c = 0;
         okey_t below = 0;                                // the largest key < v2
-        ord_walk(ord_lds, span, a.window, a.slab, restage, load, [&](okey_t k) {
+        fmk_window_walk<ORD_BLOCK, 1>(ord_lds, span, a.window, a.slab, restage, load, [&](int, okey_t k) {
             const bool lt = k < v2;
             c += lt ? 1 : 0;
             below = lt && k > below ? k : below;
@@ -255,25 +210,17 @@ struct StochArgs {
 
 __global__ __launch_bounds__(ORD_BLOCK) void k_stoch(StochArgs a)
 {
-    extern __shared__ uint64_t ord_words[];
+    extern __shared__ double ord_f64[];
     const int64_t t0 = a.length - 1 + (int64_t)blockIdx.x * ORD_WALK_TILE;
     const int64_t t1 = t0 + ORD_WALK_TILE < a.n ? t0 + ORD_WALK_TILE : a.n;
     const int64_t lo0 = t0 - (a.length - 1), span = t1 - lo0;
     const double *low = a.low, *high = a.high;
     double lo = INFINITY, hi = -INFINITY;
     bool nan = false;
-    ord_walk(ord_words, span, a.length, a.slab, true, [low, lo0](int64_t i) { return (uint64_t)__double_as_longlong(low[lo0 + i]); },
-             [&](uint64_t u) {
-                 const double v = __longlong_as_double((long long)u);
-                 nan = nan || v != v;
-                 lo = v < lo ? v : lo;
-             });
-    ord_walk(ord_words, span, a.length, a.slab, true, [high, lo0](int64_t i) { return (uint64_t)__double_as_longlong(high[lo0 + i]); },
-             [&](uint64_t u) {
-                 const double v = __longlong_as_double((long long)u);
-                 nan = nan || v != v;
-                 hi = v > hi ? v : hi;
-             });
+    fmk_window_walk<ORD_BLOCK, 1>(ord_f64, span, a.length, a.slab, true, [low, lo0](int64_t i) { return low[lo0 + i]; },
+                                  [&](int, double v) { nan = nan || v != v; lo = v < lo ? v : lo; });
+    fmk_window_walk<ORD_BLOCK, 1>(ord_f64, span, a.length, a.slab, true, [high, lo0](int64_t i) { return high[lo0 + i]; },
+                                  [&](int, double v) { nan = nan || v != v; hi = v > hi ? v : hi; });
     const int64_t t = t0 + threadIdx.x;
     if (t >= t1) return;
     double o = NAN;
@@ -296,39 +243,15 @@ __global__ __launch_bounds__(256) void k_ord_lag(const double *__restrict__ x, i
     }
 }
 
-unsigned ord_blocks(fmk_ctx *ctx, int64_t n)
-{
-    int64_t blocks = fmk_ceil_div(n, 256);
-    if (blocks > (int64_t)ctx->n_cu * 16) blocks = (int64_t)ctx->n_cu * 16;
-    return (unsigned)(blocks > 0 ? blocks : 1);
-}
-
-// the checks every entry makes before a device is needed and before any pointer is looked at
-int ord_check(fmk_ctx *ctx, const char *what, int64_t n, int64_t arg, int64_t least, const char *arg_message)
-{
-    if (arg < least) return fmk_set_error(ctx, FMK_E_ARG, "%s", arg_message);
-    if (n < 0 || n >= ((int64_t)1 << 31)) return fmk_set_error(ctx, FMK_E_ARG, "%s: the series must hold fewer than 2^31 elements.", what);
-    return FMK_OK;
-}
-
-int ord_nan_head(fmk_ctx *ctx, double *d_out, int64_t n, int64_t window)
-{
-    const int64_t n_nan = window - 1 < n ? window - 1 : n;
-    if (n_nan > 0) {
-        k_ord_nan<<<ord_blocks(ctx, n_nan), 256, 0, ctx->stream>>>(d_out, n_nan);
-        FMK_LAUNCH_CHECK(ctx);
-    }
-    return FMK_OK;
-}
-
 }  // namespace
 
 extern "C" int fmk_burst_ratio_dev(fmk_ctx *ctx, const double *d_x, int64_t n, int64_t window, double *d_out)
 {
-    FMK_TRY(ord_check(ctx, "comp_burst_ratio", n, window, 1, "window must be at least 1."));
+    FMK_TRY(fmk_rule_window(ctx, nullptr, window));
+    FMK_TRY(fmk_series_check(ctx, "comp_burst_ratio", n));
     FMK_HIP(ctx, hipSetDevice(ctx->device));
     if (n == 0) return FMK_OK;
-    FMK_TRY(ord_nan_head(ctx, d_out, n, window));
+    FMK_TRY(fmk_nan_head(ctx, d_out, n, window));
     if (window > n) return FMK_OK;
     const int64_t outputs = n - (window - 1);
     BurstArgs a;
@@ -343,8 +266,7 @@ extern "C" int fmk_burst_ratio_dev(fmk_ctx *ctx, const double *d_x, int64_t n, i
         if (window & 1) k_burst_sorted<false><<<tiles, ORD_BLOCK, lds, ctx->stream>>>(a);
         else k_burst_sorted<true><<<tiles, ORD_BLOCK, lds, ctx->stream>>>(a);
     } else {
-        const int64_t span = window - 1 + ORD_WALK_TILE;
-        a.slab = (int)(span < ORD_SLAB ? span : ORD_SLAB);
+        a.slab = fmk_slab(window, ORD_WALK_TILE);
         k_burst_walk<<<(unsigned)fmk_ceil_div(outputs, ORD_WALK_TILE), ORD_BLOCK, (size_t)a.slab * sizeof(okey_t), ctx->stream>>>(a);
     }
     FMK_LAUNCH_CHECK(ctx);
@@ -354,36 +276,39 @@ extern "C" int fmk_burst_ratio_dev(fmk_ctx *ctx, const double *d_x, int64_t n, i
 extern "C" int fmk_stoch_k_dev(fmk_ctx *ctx, const double *d_close, const double *d_low, const double *d_high, int64_t n, int64_t length,
                                double *d_out)
 {
-    FMK_TRY(ord_check(ctx, "stoch_k", n, length, 1, "stoch_k: length must be at least 1."));
+    FMK_TRY(fmk_rule_stoch_k(ctx, length));
+    FMK_TRY(fmk_series_check(ctx, "stoch_k", n));
     FMK_HIP(ctx, hipSetDevice(ctx->device));
     if (n == 0) return FMK_OK;
-    FMK_TRY(ord_nan_head(ctx, d_out, n, length));
+    FMK_TRY(fmk_nan_head(ctx, d_out, n, length));
     if (length > n) return FMK_OK;
-    const int64_t outputs = n - (length - 1), span = length - 1 + ORD_WALK_TILE;
+    const int64_t outputs = n - (length - 1);
     StochArgs a;
     a.close = d_close; a.low = d_low; a.high = d_high; a.out = d_out; a.n = n; a.length = length;
-    a.slab = (int)(span < ORD_SLAB ? span : ORD_SLAB);
-    k_stoch<<<(unsigned)fmk_ceil_div(outputs, ORD_WALK_TILE), ORD_BLOCK, (size_t)a.slab * sizeof(uint64_t), ctx->stream>>>(a);
+    a.slab = fmk_slab(length, ORD_WALK_TILE);
+    k_stoch<<<(unsigned)fmk_ceil_div(outputs, ORD_WALK_TILE), ORD_BLOCK, (size_t)a.slab * sizeof(double), ctx->stream>>>(a);
     FMK_LAUNCH_CHECK(ctx);
     return FMK_OK;
 }
 
 extern "C" int fmk_roc_dev(fmk_ctx *ctx, const double *d_x, int64_t n, int64_t period, double *d_out)
 {
-    FMK_TRY(ord_check(ctx, "roc", n, period, 0, "roc: period must not be negative."));
+    FMK_TRY(fmk_rule_roc(ctx, period));
+    FMK_TRY(fmk_series_check(ctx, "roc", n));
     FMK_HIP(ctx, hipSetDevice(ctx->device));
     if (n == 0) return FMK_OK;
-    k_ord_lag<true><<<ord_blocks(ctx, n), 256, 0, ctx->stream>>>(d_x, n, period, d_out);
+    k_ord_lag<true><<<fmk_grid_blocks(ctx, n), 256, 0, ctx->stream>>>(d_x, n, period, d_out);
     FMK_LAUNCH_CHECK(ctx);
     return FMK_OK;
 }
 
 extern "C" int fmk_pct_change_dev(fmk_ctx *ctx, const double *d_x, int64_t n, int64_t periods, double *d_out)
 {
-    FMK_TRY(ord_check(ctx, "pct_change", n, periods, 0, "pct_change: periods must not be negative."));
+    FMK_TRY(fmk_rule_pct_change(ctx, periods));
+    FMK_TRY(fmk_series_check(ctx, "pct_change", n));
     FMK_HIP(ctx, hipSetDevice(ctx->device));
     if (n == 0) return FMK_OK;
-    k_ord_lag<false><<<ord_blocks(ctx, n), 256, 0, ctx->stream>>>(d_x, n, periods, d_out);
+    k_ord_lag<false><<<fmk_grid_blocks(ctx, n), 256, 0, ctx->stream>>>(d_x, n, periods, d_out);
     FMK_LAUNCH_CHECK(ctx);
     return FMK_OK;
 }

@@ -380,62 +380,53 @@ class DeviceTrades:
         return out
 
     # ------------------------------------------------------------------ rolling-window moments (csrc/fmk_rolling.hip)
-    def _rolling(self, name: str, y: DeviceArray, window: int, *extra) -> DeviceArray:
-        if int(window) < 1:
-            raise ValueError("window must be at least 1.")
-        if y.dtype != np.float64:
-            raise TypeError(f"{name}: the series must be float64, not {y.dtype}")
-        out = DeviceArray(self.ctx, y.n, np.float64)
-        if y.n:
-            self.ctx.call(name, y.p, c_i64(y.n), c_i64(int(window)), *extra, out.p)
-        return out
-
-    def sma(self, y: DeviceArray, window: int) -> DeviceArray:
-        """sma (feature/core/ma.py:46-62) of a resident float64 series."""
-        return self._rolling("fmk_sma_dev", y, window)
-
-    def zscore(self, y: DeviceArray, window: int, ddof: int = 0) -> DeviceArray:
-        """comp_zscore (feature/core/utils.py:67-90) of a resident float64 series; ValueError when window - ddof <= 0."""
-        if int(window) >= 1 and int(window) - int(ddof) <= 0:
-            raise ValueError("comp_zscore: window - ddof must be positive.")
-        return self._rolling("fmk_zscore_dev", y, window, c_i64(int(ddof)))
-
-    def rolling_variance(self, y: DeviceArray, window: int, ddof: int = 1, min_periods: int = 1) -> DeviceArray:
-        """rolling_variance_nb (feature/core/volatility.py:440-478) of a resident float64 series."""
-        return self._rolling("fmk_rolling_variance_dev", y, window, c_i64(int(ddof)), c_i64(int(min_periods)))
-
-    def variance_ratio_1_4(self, window: int = 32, ddof: int = 0, ret_type: str = "log",
-                           series: Optional[DeviceArray] = None) -> DeviceArray:
-        """variance_ratio_1_4_core (feature/core/volatility.py:481-540) on a resident float64 series (default: the price column)."""
-        x = self.price if series is None else series
-        return self._rolling("fmk_variance_ratio_1_4_dev", x, window, c_i64(int(ddof)), C.c_int(ret_type == "log"))
-
-    # ------------------------------------------------------------------ windowed order statistics (csrc/fmk_order.hip)
     def _f64(self, name: str, *series) -> None:
         for y in series:
             if y.dtype != np.float64:
                 raise TypeError(f"{name}: the series must be float64, not {y.dtype}")
 
-    def burst_ratio(self, y: DeviceArray, window: int) -> DeviceArray:
-        """comp_burst_ratio (feature/core/utils.py:92-108) of a resident float64 series: y / its rolling median."""
-        return self._rolling("fmk_burst_ratio_dev", y, window)
-
-    def _lagged(self, name: str, y: DeviceArray, lag: int, message: str) -> DeviceArray:
-        if int(lag) < 0:
+    def _series(self, name: str, y: DeviceArray, arg: int, *extra, least: int = 1,
+                message: str = "window must be at least 1.") -> DeviceArray:
+        if int(arg) < least:
             raise ValueError(message)
         self._f64(name, y)
         out = DeviceArray(self.ctx, y.n, np.float64)
         if y.n:
-            self.ctx.call(name, y.p, c_i64(y.n), c_i64(int(lag)), out.p)
+            self.ctx.call(name, y.p, c_i64(y.n), c_i64(int(arg)), *extra, out.p)
         return out
+
+    def sma(self, y: DeviceArray, window: int) -> DeviceArray:
+        """sma (feature/core/ma.py:46-62) of a resident float64 series."""
+        return self._series("fmk_sma_dev", y, window)
+
+    def zscore(self, y: DeviceArray, window: int, ddof: int = 0) -> DeviceArray:
+        """comp_zscore (feature/core/utils.py:67-90) of a resident float64 series; ValueError when window - ddof <= 0."""
+        if int(window) >= 1 and int(window) - int(ddof) <= 0:
+            raise ValueError("comp_zscore: window - ddof must be positive.")
+        return self._series("fmk_zscore_dev", y, window, c_i64(int(ddof)))
+
+    def rolling_variance(self, y: DeviceArray, window: int, ddof: int = 1, min_periods: int = 1) -> DeviceArray:
+        """rolling_variance_nb (feature/core/volatility.py:440-478) of a resident float64 series."""
+        return self._series("fmk_rolling_variance_dev", y, window, c_i64(int(ddof)), c_i64(int(min_periods)))
+
+    def variance_ratio_1_4(self, window: int = 32, ddof: int = 0, ret_type: str = "log",
+                           series: Optional[DeviceArray] = None) -> DeviceArray:
+        """variance_ratio_1_4_core (feature/core/volatility.py:481-540) on a resident float64 series (default: the price column)."""
+        x = self.price if series is None else series
+        return self._series("fmk_variance_ratio_1_4_dev", x, window, c_i64(int(ddof)), C.c_int(ret_type == "log"))
+
+    # ------------------------------------------------------------------ windowed order statistics (csrc/fmk_order.hip)
+    def burst_ratio(self, y: DeviceArray, window: int) -> DeviceArray:
+        """comp_burst_ratio (feature/core/utils.py:92-108) of a resident float64 series: y / its rolling median."""
+        return self._series("fmk_burst_ratio_dev", y, window)
 
     def roc(self, y: DeviceArray, period: int) -> DeviceArray:
         """roc (feature/core/momentum.py:6-22) of a resident float64 series."""
-        return self._lagged("fmk_roc_dev", y, period, "roc: period must not be negative.")
+        return self._series("fmk_roc_dev", y, period, least=0, message="roc: period must not be negative.")
 
     def pct_change(self, y: DeviceArray, periods: int) -> DeviceArray:
         """pct_change (feature/core/utils.py:110-124) of a resident float64 series."""
-        return self._lagged("fmk_pct_change_dev", y, periods, "pct_change: periods must not be negative.")
+        return self._series("fmk_pct_change_dev", y, periods, least=0, message="pct_change: periods must not be negative.")
 
     def stoch_k(self, close: DeviceArray, low: DeviceArray, high: DeviceArray, length: int) -> DeviceArray:
         """stoch_k (feature/core/momentum.py:68-112) of three resident float64 series of one length."""

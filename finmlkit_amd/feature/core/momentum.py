@@ -7,7 +7,7 @@ from numpy.typing import NDArray
 
 from ... import _ffi
 from ..._ffi import c_i64, ptr
-from .utils import lag_call
+from .ma import series_call
 
 PERIOD_MESSAGE = "roc: period must not be negative."
 LENGTH_MESSAGE = "stoch_k: length must be at least 1."
@@ -17,7 +17,7 @@ SHAPE_MESSAGE = "stoch_k: close, low and high must have the same length."
 def roc(price: NDArray, period: int) -> NDArray:
     """Reference: finmlkit/feature/core/momentum.py:6-22: ((price[i] - price[i - period]) / price[i - period]) * 100, NaN before
     `period`; a zero divisor gives the IEEE result."""
-    return lag_call("fmk_roc", price, period, PERIOD_MESSAGE)
+    return series_call("fmk_roc", price, period, least=0, message=PERIOD_MESSAGE)
 
 
 def stoch_k(close: NDArray[np.float64], low: NDArray[np.float64], high: NDArray[np.float64], length: int) -> NDArray[np.float64]:

@@ -9,7 +9,7 @@ from numpy.typing import NDArray
 
 from ... import _ffi
 from ..._ffi import c_f64, c_i64, ptr
-from .ma import rolling_call
+from .ma import series_call
 
 PERIODS_MESSAGE = "pct_change: periods must not be negative."
 
@@ -34,27 +34,16 @@ def comp_zscore(x: NDArray[np.float64], window: int, ddof: int) -> NDArray[np.fl
     reference divides by zero or takes the root of a negative number there)."""
     if int(window) >= 1 and int(window) - int(ddof) <= 0:
         raise ValueError("comp_zscore: window - ddof must be positive.")
-    return rolling_call("fmk_zscore", x, window, c_i64(int(ddof)))
+    return series_call("fmk_zscore", x, window, c_i64(int(ddof)))
 
 
 def comp_burst_ratio(series: NDArray[np.float64], window: int) -> NDArray[np.float64]:
     """Reference: finmlkit/feature/core/utils.py:92-108: series[i] / np.median(the window ending at i) where that median is > 0,
     NaN elsewhere, where the window holds a NaN, and before the first full window (csrc/fmk_order.hip)."""
-    return rolling_call("fmk_burst_ratio", series, window)
-
-
-def lag_call(name: str, x, lag: int, message: str) -> NDArray[np.float64]:
-    """One of the lagged elementwise entries of csrc/fmk_order.hip on `x`; a negative lag is refused before a device is needed."""
-    if int(lag) < 0:
-        raise ValueError(message)
-    xx = np.ascontiguousarray(x, dtype=np.float64)
-    out = np.empty(len(xx), np.float64)
-    if len(xx):
-        _ffi.default_context().call(name, ptr(xx), c_i64(len(xx)), c_i64(int(lag)), ptr(out))
-    return out
+    return series_call("fmk_burst_ratio", series, window)
 
 
 def pct_change(x: NDArray[np.float64], periods: int) -> NDArray[np.float64]:
     """Reference: finmlkit/feature/core/utils.py:110-124: (x[t] - base) / base with base = x[t - periods] where base > 0, NaN
     elsewhere and before `periods`."""
-    return lag_call("fmk_pct_change", x, periods, PERIODS_MESSAGE)
+    return series_call("fmk_pct_change", x, periods, least=0, message=PERIODS_MESSAGE)

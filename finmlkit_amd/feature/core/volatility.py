@@ -14,7 +14,7 @@ from numpy.typing import NDArray
 
 from ... import _ffi
 from ..._ffi import c_f64, c_i64, ptr
-from .ma import rolling_call
+from .ma import series_call
 
 
 def _ewmst(timestamps, y, half_life, sigma_floor, mean0):
@@ -62,10 +62,10 @@ def realized_vol(r: NDArray[np.float64], window: int, is_sample: bool) -> NDArra
 def rolling_variance_nb(series: NDArray[np.float64], window: int, ddof: int = 1, min_periods: int = 1) -> NDArray[np.float64]:
     """Reference: finmlkit/feature/core/volatility.py:440-478: per window the count, sum and sum of squares of the non-NaN
     elements, max(0, (sum_sq / cnt - mean^2) * (cnt / (cnt - ddof))) when cnt >= min_periods and cnt > ddof, NaN otherwise."""
-    return rolling_call("fmk_rolling_variance", series, window, c_i64(int(ddof)), c_i64(int(min_periods)))
+    return series_call("fmk_rolling_variance", series, window, c_i64(int(ddof)), c_i64(int(min_periods)))
 
 
 def variance_ratio_1_4_core(price: NDArray[np.float64], window: int, ddof: int, ret_type: str) -> NDArray[np.float64]:
     """Reference: finmlkit/feature/core/volatility.py:481-540: var(1-step returns) / (var(4-step returns) / 4) over `window`;
     `ret_type` "log" takes log returns (the host's log), anything else simple returns."""
-    return rolling_call("fmk_variance_ratio_1_4", price, window, c_i64(int(ddof)), C.c_int(ret_type == "log"))
+    return series_call("fmk_variance_ratio_1_4", price, window, c_i64(int(ddof)), C.c_int(ret_type == "log"))

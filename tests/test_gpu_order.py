@@ -19,7 +19,7 @@ TILE = 1024                          # sorted path: outputs per workgroup (ORD_T
 SPAN_MAX = 4096                      # sorted path: entries in LDS (ORD_SPAN_MAX)
 SORT_WINDOW_MAX = SPAN_MAX - TILE + 1    # the largest window of the sorted path (ORD_SORT_WINDOW_MAX); the next takes the bisection
 WALK_TILE = BLOCK                    # walk kernels (bisection, %K): outputs per workgroup (ORD_WALK_TILE)
-SLAB = 4096                          # walk kernels: LDS elements per staging (ORD_SLAB)
+SLAB = 4096                          # walk kernels: LDS elements per staging (csrc/fmk_window.h: FMK_SLAB_MAX)
 ONE_SLAB_WINDOW = SLAB - WALK_TILE + 1   # walk kernels: the longest window whose full tile reads one slab
 ENTRY = {"burst": "fmk_burst_ratio", "stoch": "fmk_stoch_k", "roc": "fmk_roc", "pct": "fmk_pct_change"}
 

@@ -15,8 +15,8 @@ pytestmark = pytest.mark.gpu
 
 BLOCK = 256                          # lanes per workgroup (csrc/fmk_rolling.hip: ROLL_BLOCK)
 TILE = 1024                          # outputs per workgroup (ROLL_TILE = ROLL_BLOCK * ROLL_OPL)
-SLAB = 4096                          # LDS elements per staging (ROLL_SLAB_MAX)
-ONE_SLAB_WINDOW = SLAB - TILE + 1    # the longest window whose full tile reads one slab (window - 1 + ROLL_TILE <= ROLL_SLAB_MAX)
+SLAB = 4096                          # LDS elements per staging (csrc/fmk_window.h: FMK_SLAB_MAX)
+ONE_SLAB_WINDOW = SLAB - TILE + 1    # the longest window whose full tile reads one slab (window - 1 + ROLL_TILE <= FMK_SLAB_MAX)
 
 
 def equal(got, want, what):

@@ -185,3 +185,21 @@ def test_the_log_and_exp_tables_in_the_tree_are_the_hosts(tmp_path):
     strip = lambda t: [l for l in t.splitlines() if not l.startswith("//")]
     for name in ("fmk_logtab.h", "fmk_exptab.h"):
         assert strip(open(str(tmp_path / name)).read()) == strip(open(os.path.join(root, "finmlkit_amd", "csrc", name)).read()), name
+
+
+def test_window_walk_step_plan(tmp_path):
+    """The step plan of the lockstep window walk (csrc/fmk_window.h: fmk_walk_plan, plain C++ that the device walk calls) replayed on
+    the host by tools/walkplan_check.cpp: BLOCK 256, OPL 1 and 4, every wave, slabs of 64, 100, 256 and 1300 words, every window
+    1 .. 3 * slab + 2 and tiles of 1, 63, 64, 65, tile - 1 and tile outputs.  Every output takes every position of its window exactly
+    once, ascending; no unchecked step leaves the slab; a wave with no element in a slab takes no step."""
+    import os
+    import shutil
+    import subprocess
+    if not shutil.which("g++"):
+        pytest.skip("no g++")
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    exe = str(tmp_path / "walkplan_check")
+    subprocess.check_call(["g++", "-O2", "-std=c++17", os.path.join(root, "tools", "walkplan_check.cpp"), "-o", exe])
+    r = subprocess.run([exe], capture_output=True, text=True)
+    assert r.returncode == 0, r.stdout
+    assert "walk plans checked: 638200, failed checks: 0" in r.stdout

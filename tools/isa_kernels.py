@@ -6,7 +6,7 @@ import re, sys
 def kernels(path):
     src = open(path).read()
     out = {}
-    for m in re.finditer(r'^(_Z\w+):[^\n]*\n(.*?)^\s*s_endpgm', src, re.S | re.M):
+    for m in re.finditer(r'^(_Z\w+):[^\n]*\n(.*?)^\.Lfunc_end', src, re.S | re.M):
         ins = []
         for l in m.group(2).splitlines():
             t = l.split(';')[0].strip()
