@@ -19,6 +19,7 @@
 // float64 sums are combined in (lane-sequential, then tree) order; bars whose sums land within that reordering's
 // noise of a float32 rounding tie are redone in tick order (k_bar_dir_redo), so the float32 outputs are the
 // reference's bit for bit.
+#include "fmk_bars.h"
 #include "fmk_footprint.h"
 #include "fmk_f32tie.h"
 #include "fmk_median.h"
@@ -304,8 +305,8 @@ __device__ __forceinline__ void bf_dir_write(const FlowDirOut &o, int64_t b, int
     const double vmin = t.vmin, vmax = t.vmax, dmin = t.dmin, dmax = t.dmax;
     if (lane == 0 && tb + tsell == 0 && n_zero_div) atomicAdd(n_zero_div, 1ULL);   // reference: ZeroDivisionError (base.py:536)
     // The sums above are float64 in (lane, tree[, wave]) order, the reference's in tick order.  float32 outputs can only differ when
-    // a sum sits within the two orders' rounding noise of a float32 rounding boundary; those bars go on the redo list (redo[0]:
-    // count, redo[32...]: bar number | column mask << 48) and k_bar_dir_redo_par adds the flagged columns in tick order.
+    // a sum sits within the two orders' rounding noise of a float32 rounding boundary; those bars go on the redo list (a bar
+    // list, fmk_bars.h: bar number | column mask << 48) and k_bar_dir_redo_par adds the flagged columns in tick order.
     //   * one-signed sums (buy / sell volume and dollars, spread): recursive summation of len terms errs by at most (len - 1) u S
     //     (u = 2^-53, S the sum), the lane-sequential / tree / tile-carry order here by at most (len / 64 + len / 512 + 22) u S:
     //     together below 1.05 (len + 64) u S.
@@ -360,7 +361,7 @@ __device__ __forceinline__ void bf_dir_write(const FlowDirOut &o, int64_t b, int
         }
     }
     if (bf_force_redo != 0) mask = 0x7F;                               // (tests: every bar through the tick-order redo)
-    if (mask && lane == 0) redo[32 + atomicAdd(redo, 1ULL)] = (unsigned long long)b | ((unsigned long long)mask << 48);
+    if (mask && lane == 0) fmk_list_push(redo, (unsigned long long)b | ((unsigned long long)mask << 48));
     if (lane == 0) {
         o.ticks_buy[b] = tb; o.ticks_sell[b] = tsell;
         o.volume_buy[b] = (float)vb; o.volume_sell[b] = (float)vs;
@@ -405,10 +406,10 @@ __global__ __launch_bounds__(64 * WPB) void k_bar_dir(const double *__restrict__
     const AmtT *am = (const AmtT *)amount;
     const int64_t wave0 = (int64_t)blockIdx.x * WPB + wib;
     const int64_t nwaves = (int64_t)gridDim.x * WPB;
-    // `only` (list mode: [0] = count, [32...] = bar numbers): the bars k_bar_dir_lanes left to this schedule
-    const int64_t todo = only ? (int64_t)only[0] : nb;
+    // `only` (list mode): the bars k_bar_dir_lanes left to this schedule
+    const int64_t todo = fmk_list_count(only, nb);
     for (int64_t it = wave0; it < todo; it += nwaves) {
-        const int64_t b = only ? fmk_uniform((int64_t)only[32 + it]) : it;
+        const int64_t b = fmk_list_bar(only, it);
         const int64_t s = fmk_uniform(ci[b]);
         const int64_t e = fmk_uniform(ci[b + 1]);
         const int64_t start = s + 1;
@@ -579,7 +580,7 @@ __global__ __launch_bounds__(256) void k_bar_dir_redo(const double *__restrict__
     const int64_t count = (int64_t)redo[0];
     const int64_t nwaves = (int64_t)gridDim.x * 4;
     for (int64_t i = (int64_t)blockIdx.x * 4 + fmk_uniform((int)(threadIdx.x >> 6)); i < count; i += nwaves) {
-        const int64_t b = fmk_uniform((int64_t)(redo[32 + i] & 0xFFFFFFFFFFFFULL));
+        const int64_t b = fmk_uniform((int64_t)(fmk_list_entry(redo, i) & 0xFFFFFFFFFFFFULL));
         const int64_t s = fmk_uniform(ci[b]), e = fmk_uniform(ci[b + 1]);
         bf_dir_sequential<AmtT>(o, b, lane, s_rows[threadIdx.x >> 6], price, (const AmtT *)amount, side, s + 1, e, n);
     }
@@ -727,7 +728,7 @@ __global__ __launch_bounds__(64 * RS_WAVES) void k_bar_dir_redo_par(const double
     // item = column * count + list entry: the flagged columns of ONE bar land on different workgroups
     for (int64_t item = blockIdx.x; item < count * 7; item += gridDim.x) {
         const int row = (int)(item / count);
-        const unsigned long long entry = redo[32 + item % count];
+        const unsigned long long entry = (unsigned long long)fmk_list_entry(redo, item % count);
         if (!((entry >> (48 + row)) & 1)) continue;                      // this column is not near a float32 tie (block-uniform)
         const int64_t b = (int64_t)(entry & 0xFFFFFFFFFFFFULL);
         const int64_t start = ci[b] + 1, e_bar = ci[b + 1];
@@ -1294,10 +1295,9 @@ __global__ __launch_bounds__(64 * DL_WAVES) void k_bar_dir_lanes(const double *_
             unsigned long long base = 0;
             if (lane == 0) base = atomicAdd(long_list, (unsigned long long)__builtin_popcountll(lb));
             base = (unsigned long long)fmk_uniform((int64_t)base);
-            if (is_long) long_list[32 + base + __builtin_popcountll(lb & ((1ULL << lane) - 1))] = (unsigned long long)b;
+            if (is_long) long_list[FMK_BAR_LIST_HEAD + base + __builtin_popcountll(lb & ((1ULL << lane) - 1))] = (unsigned long long)b;
             if constexpr (OHLC) {
-                if (lane == 0 && __hip_atomic_load(oo.any_long, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0)
-                    __hip_atomic_store(oo.any_long, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                if (lane == 0) fmk_raise(oo.any_long);
             }
         }
         const bool active = has && len > 0 && !is_long;
@@ -1629,9 +1629,7 @@ __global__ __launch_bounds__(256, 4) void k_bar_ohlcv_dir(const double *__restri
                 bar.amount = amount; bar.start = start; bar.cnt = cnt; bar.lane = lane;
                 const double m = med_search<false, BF_MED_TILES * 8, false>(bar, s_buf[wib]);
                 if (lane == 0) oo.median[b] = m;
-            } else if (lane == 0 && __hip_atomic_load(saw_long, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0) {
-                __hip_atomic_store(saw_long, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // k_bar_median takes it
-            }
+            } else if (lane == 0) fmk_raise(saw_long);                   // k_bar_median takes it
         }
     }
 }
@@ -1642,7 +1640,7 @@ __global__ __launch_bounds__(256, 4) void k_bar_ohlcv_dir(const double *__restri
 // cfg 4 in one pass (fmk_fused.h): host side
 // ---------------------------------------------------------------------------------------
 struct FuState {                      // what the sizing call leaves for the fill call (ctx->fused)
-    void *block;                      // one allocation: staged rows [nb * FU_LV] x 4 arrays, L[nb], fp_list[nb + 32], the kernel's FuArgs
+    void *block;                      // one allocation: staged rows [nb * FU_LV] x 4 arrays, L[nb], fp_list[fmk_bar_list_words(nb)], the kernel's FuArgs
     FuStage stg;
     unsigned long long *fp_list;
     int64_t nb, n_fp;
@@ -1760,7 +1758,7 @@ static int bars_flow_fused(fmk_ctx *ctx, const double *d_price, const float *d_a
     FuState *st = (FuState *)calloc(1, sizeof(FuState));
     if (!st) return fmk_set_error(ctx, FMK_E_NOMEM, "calloc");
     const size_t rows = units ? (size_t)nb * FU_LV : 0;                 // (no staging without the histogram)
-    const size_t lbytes = ((size_t)nb * 4 + 255) & ~(size_t)255, fbytes = ((size_t)(nb + 32) * 8 + 255) & ~(size_t)255;
+    const size_t lbytes = ((size_t)nb * 4 + 255) & ~(size_t)255, fbytes = (fmk_bar_list_words(nb) * 8 + 255) & ~(size_t)255;
     int64_t blocks = fmk_ceil_div(nb, 4);
     {
         const int64_t cap = (int64_t)ctx->n_cu * 16;
@@ -1786,17 +1784,17 @@ static int bars_flow_fused(fmk_ctx *ctx, const double *d_price, const float *d_a
     // (any length: the chunk-record kernel).  On the bench tape 0.19 % of the bars are TRUE near-ties -- its prices and sizes lie on
     // grids that put running dollar sums exactly on float32 midpoints -- and the chunk-record kernel took 0.41 ms for those 1 591 short bars
     unsigned long long *redo;
-    rc = fmk_scratch(ctx, (size_t)(nb + 32) * 24, (void **)&redo);
+    rc = fmk_scratch(ctx, fmk_bar_list_words(nb) * 24, (void **)&redo);
     if (rc != FMK_OK) { fmk_fused_release(ctx); return rc; }
-    unsigned long long *dir_list = redo + nb + 32, *redo_fu = redo + 2 * (nb + 32);
+    unsigned long long *dir_list = redo + fmk_bar_list_words(nb), *redo_fu = redo + 2 * fmk_bar_list_words(nb);
     int *saw_long = ctx->d_mail->bf.fu_long;
     FuLists li{redo_fu, redo, dir_list, st->fp_list, saw_long, saw_long + 1};
     auto fail = [&](int code) { fmk_fused_release(ctx); return code; };
 #define FU_HIP(expr) do { const hipError_t e__ = (expr); if (e__ != hipSuccess) return fail(fmk_set_error(ctx, FMK_E_HIP, "%s failed: %s", #expr, hipGetErrorString(e__))); } while (0)
-    FU_HIP(hipMemsetAsync(redo, 0, 8, ctx->stream));
-    FU_HIP(hipMemsetAsync(redo_fu, 0, 8, ctx->stream));
-    FU_HIP(hipMemsetAsync(dir_list, 0, 8, ctx->stream));
-    FU_HIP(hipMemsetAsync(st->fp_list, 0, 8, ctx->stream));
+    FU_HIP(hipMemsetAsync(redo, 0, FMK_BAR_LIST_CLEAR, ctx->stream));
+    FU_HIP(hipMemsetAsync(redo_fu, 0, FMK_BAR_LIST_CLEAR, ctx->stream));
+    FU_HIP(hipMemsetAsync(dir_list, 0, FMK_BAR_LIST_CLEAR, ctx->stream));
+    FU_HIP(hipMemsetAsync(st->fp_list, 0, FMK_BAR_LIST_CLEAR, ctx->stream));
     FU_HIP(hipMemsetAsync(saw_long, 0, 2 * sizeof(int), ctx->stream));
     FuArgs h_args;
     h_args.amount = d_amount;
@@ -1952,8 +1950,8 @@ extern "C" int fmk_comp_bar_directional_dev(fmk_ctx *ctx, const double *d_price,
     if (blocks > cap) blocks = cap;
     if (blocks < 1) blocks = 1;
     unsigned long long *redo;
-    FMK_TRY(fmk_scratch(ctx, (size_t)(nb + 32) * 16, (void **)&redo));
-    FMK_HIP(ctx, hipMemsetAsync(redo, 0, 8, ctx->stream));
+    FMK_TRY(fmk_scratch(ctx, fmk_bar_list_words(nb) * 16, (void **)&redo));
+    FMK_HIP(ctx, hipMemsetAsync(redo, 0, FMK_BAR_LIST_CLEAR, ctx->stream));
     const unsigned rblocks = (unsigned)(blocks < 4096 ? blocks : 4096);
     // bars of more than BFW_MIN ticks: a workgroup per bar, from a list
     const int64_t skip_above = BFW_MIN;
@@ -1981,8 +1979,8 @@ extern "C" int fmk_comp_bar_directional_dev(fmk_ctx *ctx, const double *d_price,
     // ahead there too; before: 3.53), 12 000-tick bars: wave per bar
     const bool lanes_fit = nb >= (int64_t)ctx->n_cu * 64 * 4 && n / nb <= 2048;
     if (lanes_ok && lanes_mode != 0 && (lanes_fit || lanes_mode == 2)) {
-        unsigned long long *long_list = redo + nb + 32;
-        FMK_HIP(ctx, hipMemsetAsync(long_list, 0, 8, ctx->stream));
+        unsigned long long *long_list = redo + fmk_bar_list_words(nb);
+        FMK_HIP(ctx, hipMemsetAsync(long_list, 0, FMK_BAR_LIST_CLEAR, ctx->stream));
         int64_t lblocks = fmk_ceil_div(fmk_ceil_div(nb, 64), DL_WAVES);
         const int64_t lcap = (int64_t)ctx->n_cu * 40;
         if (lblocks > lcap) lblocks = lcap;
@@ -2135,11 +2133,11 @@ static int bars_flow_size(fmk_ctx *ctx, const double *d_price, const void *d_amo
             FMK_TRY(rc);
         } else sort_mode = 0;
         unsigned long long *redo;
-        FMK_TRY(fmk_scratch(ctx, (size_t)(nb + 32) * 16, (void **)&redo));
-        unsigned long long *long_list = redo + nb + 32;
+        FMK_TRY(fmk_scratch(ctx, fmk_bar_list_words(nb) * 16, (void **)&redo));
+        unsigned long long *long_list = redo + fmk_bar_list_words(nb);
         int *any_long = &ctx->d_mail->bf.any_long;
-        FMK_HIP(ctx, hipMemsetAsync(redo, 0, 8, ctx->stream));
-        FMK_HIP(ctx, hipMemsetAsync(long_list, 0, 8, ctx->stream));
+        FMK_HIP(ctx, hipMemsetAsync(redo, 0, FMK_BAR_LIST_CLEAR, ctx->stream));
+        FMK_HIP(ctx, hipMemsetAsync(long_list, 0, FMK_BAR_LIST_CLEAR, ctx->stream));
         FMK_HIP(ctx, hipMemsetAsync(any_long, 0, sizeof(int), ctx->stream));
         int64_t lblocks = fmk_ceil_div(fmk_ceil_div(nb, 64), DL_WAVES);
         const int64_t lcap = (int64_t)ctx->n_cu * 40;
@@ -2239,8 +2237,8 @@ static int bars_flow_size(fmk_ctx *ctx, const double *d_price, const void *d_amo
         if (blocks > cap) blocks = cap;
         if (blocks < 1) blocks = 1;
         unsigned long long *redo;
-        FMK_TRY(fmk_scratch(ctx, (size_t)(nb + 32) * 8, (void **)&redo));
-        FMK_HIP(ctx, hipMemsetAsync(redo, 0, 8, ctx->stream));
+        FMK_TRY(fmk_scratch(ctx, fmk_bar_list_words(nb) * 8, (void **)&redo));
+        FMK_HIP(ctx, hipMemsetAsync(redo, 0, FMK_BAR_LIST_CLEAR, ctx->stream));
         int *saw_long = &ctx->d_mail->bf.saw_long;
         FMK_HIP(ctx, hipMemsetAsync(saw_long, 0, sizeof(int), ctx->stream));
         if (d_median)

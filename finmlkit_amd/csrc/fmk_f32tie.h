@@ -2,7 +2,7 @@
 // dollars / spreads).  The kernels add in (lane, tree) order, the reference in tick order: the two float64 sums differ
 // by at most ~len * 2^-53 * sum|terms|, which changes the float32 result only when the sum sits that close to a
 // float32 rounding boundary.  Kernels test their per-bar sums with fmk_near_f32_tie and put the few bars that are
-// too close on a redo list (list[0]: count, list[32...]: bar numbers), which a second kernel walks in tick order.
+// too close on a redo list (a bar list, fmk_bars.h), which a second kernel walks in tick order.
 // Bound convention: callers pass eps * |sum| with eps = 2 * len * 2^-52; |sum| equals sum|terms| for the one-signed
 // terms of the domain (amounts >= 0, prices >= 0).
 #pragma once

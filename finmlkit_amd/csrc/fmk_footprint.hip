@@ -34,6 +34,7 @@
 // L<=128 (3 KB LDS/wave), <=512 (12 KB), <=2048 (48 KB, one wave per workgroup); bars wider than that (a fine
 // tick on a volatile hour: 10^4-10^5 levels) run the same code with the histogram in a per-wave slice of global
 // scratch instead of LDS (generic pointers; slow but unlimited up to 2^24 levels).
+#include "fmk_bars.h"
 #include "fmk_footprint.h"
 #include "fmk_median.h"
 #include "fmk_scan.h"
@@ -684,10 +685,10 @@ __global__ __launch_bounds__(256) void k_bar_footprints(const double *__restrict
     const double inv_tick = 1.0 / tick;
     int wq = FP_Q_UNKNOWN;        // quantum exponent the previous bar of this wave certified with
     int no_quantum = 0;           // bars in a row whose tick-ordered sweep found no usable quantum
-    // `only` (list mode: [0] = count, [32...] = bar numbers): the bars k_bar_footprints_lanes left to this schedule
-    const int64_t todo = only ? (int64_t)only[0] : nb;
+    // `only` (list mode): the bars k_bar_footprints_lanes left to this schedule
+    const int64_t todo = fmk_list_count(only, nb);
     for (int64_t it = wave0; it < todo; it += nwaves) {
-        const int64_t b = only ? fmk_uniform((int64_t)only[32 + it]) : it;
+        const int64_t b = fmk_list_bar(only, it);
         const int64_t base = fmk_uniform(off[b]);
         const int L = (int)fmk_uniform(off[b + 1] - base);
         if (L <= lmin || L > lmax) continue;          // handled by another launch (or L == 0)
@@ -695,8 +696,7 @@ __global__ __launch_bounds__(256) void k_bar_footprints(const double *__restrict
         const int64_t e = fmk_uniform(ci[b + 1]);
         if (e - s > skip_above && L <= skip_lmax) {                // a workgroup has taken this bar (k_bar_footprints_wide)
             if constexpr (MED) {                                       // ... and its median is the long-bar kernels'
-                if (lane == 0 && __hip_atomic_load(saw_long, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0)
-                    __hip_atomic_store(saw_long, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                if (lane == 0) fmk_raise(saw_long);
             }
             continue;
         }
@@ -758,8 +758,7 @@ __global__ __launch_bounds__(256) void k_bar_footprints(const double *__restrict
             __builtin_amdgcn_wave_barrier();
             double m = 0.0;
             if (n_t > FP_MED_MAX_TICKS) {
-                if (lane == 0 && __hip_atomic_load(saw_long, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0)
-                    __hip_atomic_store(saw_long, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                if (lane == 0) fmk_raise(saw_long);
                 med.have = medp ? med.have : 0;
                 continue;
             } else if (n_t > 0) {
@@ -1091,7 +1090,7 @@ __global__ __launch_bounds__(64 * FPW_WAVES) void k_bar_footprints_wide(const do
             wq = FP_Q_UNKNOWN;
             if (!parallel_ok) {
                 // float64 amounts (f32 element += f64 value) / no lane-ordered LDS atomics: the wave-per-bar kernel takes the bar
-                if (threadIdx.x == 0) defer[32 + atomicAdd(defer, 1ULL)] = (unsigned long long)b;
+                if (threadIdx.x == 0) fmk_list_push(defer, (unsigned long long)b);
                 continue;
             }
             if constexpr (!AF64) {
@@ -1370,7 +1369,7 @@ __global__ __launch_bounds__(64 * FL_WAVES) void k_bar_footprints_lanes(const do
     }
 }
 
-// list of the bars k_bar_footprints_lanes left over: rest[0] = count (from the scan's total), rest[32 + pos[g] + k] = the k-th
+// list of the bars k_bar_footprints_lanes left over: rest[0] = count (from the scan's total), rest[FMK_BAR_LIST_HEAD + pos[g] + k] = the k-th
 // set bit of group g
 __global__ __launch_bounds__(256) void k_fl_compact(const unsigned long long *__restrict__ grp_mask,
                                                     const int64_t *__restrict__ pos, int64_t groups,
@@ -1380,7 +1379,7 @@ __global__ __launch_bounds__(256) void k_fl_compact(const unsigned long long *__
     if (g == 0) rest[0] = (unsigned long long)pos[groups];
     if (g >= groups) return;
     unsigned long long m = grp_mask[g];
-    int64_t at = 32 + pos[g];
+    int64_t at = FMK_BAR_LIST_HEAD + pos[g];
     while (m) {
         const int bit = __builtin_ctzll(m);
         rest[at++] = (unsigned long long)(g * 64 + bit);
@@ -1562,7 +1561,7 @@ int fmk_footprints_fill_classes(fmk_ctx *ctx, const double *d_price, const void 
             const int64_t groups = fmk_ceil_div(nb, 64);
             unsigned long long *grp_mask = nullptr;
             int64_t *grp_cnt = nullptr;
-            int arc = fmk_alloc(ctx, (size_t)(nb + 32) * 8, (void **)&rest);
+            int arc = fmk_alloc(ctx, fmk_bar_list_words(nb) * 8, (void **)&rest);
             if (arc == FMK_OK) arc = fmk_alloc(ctx, (size_t)groups * 8, (void **)&grp_mask);
             if (arc == FMK_OK) arc = fmk_alloc(ctx, (size_t)(groups + 1) * 8, (void **)&grp_cnt);
             if (arc != FMK_OK) {
@@ -1608,9 +1607,9 @@ int fmk_footprints_fill_classes(fmk_ctx *ctx, const double *d_price, const void 
             // scratch of the tick-ordered path: the bars' amounts sorted by (key, tick), in the slots of the bar's own tick range;
             // the list of the bars handed back to the wave-per-bar kernel (at most n_ticks / FPW_MIN of them)
             if (rc == FMK_OK && !amount_is_f64) (void)fmk_alloc(ctx, (size_t)(n_ticks + 64) * 4, (void **)&wide_sorted);   // (none: those bars are deferred)
-            if (rc == FMK_OK) rc = fmk_alloc(ctx, (size_t)(n_ticks / FPW_MIN + 2 + 32) * 8, (void **)&wide_defer);
+            if (rc == FMK_OK) rc = fmk_alloc(ctx, fmk_bar_list_words(n_ticks / FPW_MIN + 2) * 8, (void **)&wide_defer);
             if (rc == FMK_OK) {
-                const hipError_t me = hipMemsetAsync(wide_defer, 0, 8, ctx->stream);
+                const hipError_t me = hipMemsetAsync(wide_defer, 0, FMK_BAR_LIST_CLEAR, ctx->stream);
                 if (me != hipSuccess) rc = fmk_set_error(ctx, FMK_E_HIP, "hipMemsetAsync: %s", hipGetErrorString(me));
             }
             if (rc == FMK_OK) {

@@ -42,7 +42,7 @@ struct FuStage {             // level rows of the bars the fused kernel finished
     int *bc, *sc;
     int *L;                  // [nb]: levels staged for the bar, -1: not staged (the bar is on fp_list)
 };
-struct FuLists {             // [0] = count, entries from [32]
+struct FuLists {             // bar lists (fmk_bars.h)
     unsigned long long *redo;        // bar | column mask << 48: float32 ties of bars of one tile (k_bar_dir_redo: a wave per bar)
     unsigned long long *redo_long;   // ... of longer bars (k_bar_dir's own redo list: the chunk-record kernel)
     unsigned long long *dir_list;    // bars whose order flow k_bar_dir computes
@@ -556,7 +556,7 @@ __device__ __forceinline__ void fu_finish(const double *__restrict__ price, int6
     // ---- comp_bar_directional_features (base.py:409-546)
     const bool dir_ok = vol_ok && lo_w > 0.0 && first == first && td_w < INFINITY;      // (a NaN / inf price anywhere: not this class)
     if (!dir_ok) {
-        if (lane == 0) li.dir_list[32 + atomicAdd(li.dir_list, 1ULL)] = (unsigned long long)b;
+        if (lane == 0) fmk_list_push(li.dir_list, (unsigned long long)b);
     } else {
         // every tick is a buy or a sell: counts and volumes from the totals and the signed totals (exact)
         const int64_t tb = (cnt + st_w) >> 1, tsell = (cnt - st_w) >> 1;
@@ -596,7 +596,7 @@ __device__ __forceinline__ void fu_finish(const double *__restrict__ price, int6
             if (mask) {
                 // (bars of one tile: the wave-per-bar redo; longer ones: k_bar_dir's chunk-record kernel)
                 unsigned long long *rl = cnt <= FU_MAXT ? li.redo : li.redo_long;
-                rl[32 + atomicAdd(rl, 1ULL)] = (unsigned long long)b | ((unsigned long long)mask << 48);
+                fmk_list_push(rl, (unsigned long long)b | ((unsigned long long)mask << 48));
             }
             if (pend) {
                 unsigned long long *ps_ = pend->slot;
@@ -665,7 +665,7 @@ __device__ __forceinline__ void fu_finish(const double *__restrict__ price, int6
             if (lane == 0) {
                 if (pend) { pend->slot[24] = 0ULL; pend->slot[27] = 0xFFFFFFFFULL; }
                 else stg.L[b] = -1;
-                li.fp_list[32 + atomicAdd(li.fp_list, 1ULL)] = (unsigned long long)b;
+                fmk_list_push(li.fp_list, (unsigned long long)b);
             }
             if (pend) pvalid |= 1u << 22;
         }
@@ -779,13 +779,12 @@ __global__ __launch_bounds__(256, FU_WAVES) void k_fu_bars(const double *__restr
                     oo.open[b] = pz; oo.high[b] = pz; oo.low[b] = pz; oo.close[b] = pz;
                     oo.vol[b] = 0.f; oo.vwap[b] = 0.0; oo.trades[b] = 0;
                     if (MEDIAN) oo.median[b] = 0.0;
-                    li.dir_list[32 + atomicAdd(li.dir_list, 1ULL)] = (unsigned long long)b;
+                    fmk_list_push(li.dir_list, (unsigned long long)b);
                     if (UNITS) {
                         cargs->stg.L[b] = -1;
-                        li.fp_list[32 + atomicAdd(li.fp_list, 1ULL)] = (unsigned long long)b;
+                        fmk_list_push(li.fp_list, (unsigned long long)b);
                     }
-                } else if (__hip_atomic_load(li.saw_long, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0)
-                    __hip_atomic_store(li.saw_long, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);      // k_fu_long, fmk_median_launch
+                } else fmk_raise(li.saw_long);                          // k_fu_long, fmk_median_launch
             }
             continue;
         }
@@ -861,12 +860,11 @@ __global__ __launch_bounds__(256, FU_WAVES) void k_fu_long(const double *__restr
             if (cnt > FU_LONGEST) {
                 if (lane == 0) {
                     const auto &li = cargs->li;
-                    if (__hip_atomic_load(li.saw_huge, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0)
-                        __hip_atomic_store(li.saw_huge, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    li.dir_list[32 + atomicAdd(li.dir_list, 1ULL)] = (unsigned long long)b;
+                    fmk_raise(li.saw_huge);
+                    fmk_list_push(li.dir_list, (unsigned long long)b);
                     if (UNITS) {
                         cargs->stg.L[b] = -1;
-                        li.fp_list[32 + atomicAdd(li.fp_list, 1ULL)] = (unsigned long long)b;
+                        fmk_list_push(li.fp_list, (unsigned long long)b);
                     }
                 }
                 continue;

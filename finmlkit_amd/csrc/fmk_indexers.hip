@@ -7,6 +7,7 @@
 #include <math.h>
 #include <stdlib.h>
 
+#include "fmk_bars.h"
 #include "fmk_common.h"
 
 // ---------------------------------------------------------------------------------------
@@ -184,8 +185,7 @@ __global__ __launch_bounds__(256) void k_time_bar_index_stage(const int64_t *__r
         if (live && k + 1 < ne) {
             const int64_t nx = (threadIdx.x + 1 < 256 && k + 1 < k1) ? sidx[threadIdx.x + 1]
                                                                       : tb_index_of(ts, n, coarse, m, e0 + (k + 1) * d, secant);
-            if (nx - me > long_min && __hip_atomic_load(saw_long, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0)
-                __hip_atomic_store(saw_long, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            if (nx - me > long_min) fmk_raise(saw_long);
         }
     }
 }

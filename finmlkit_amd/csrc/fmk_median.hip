@@ -17,6 +17,7 @@
 // registers; `min_cnt` lets this kernel process only the longer bars in that case.
 //
 // Traffic: amount column once (4 or 8 B/tick) + 8 B/bar.
+#include "fmk_bars.h"
 #include "fmk_median.h"
 
 // Bars beyond the register classes (more than 2048 float32 / 1536 float64 ticks: 2-minute bars and up on the bench tape).  The first
@@ -24,7 +25,6 @@
 // bars, 0.31 s at hourly bars, 13.7 s at daily bars (580 waves on the whole chip).  Now a WORKGROUP takes such a bar and
 // selects the two middle ranks by radix: BITS / 8 passes over the bar, 256-bin histograms of the current digit in LDS for the
 // keys that share the prefix found so far (one histogram while both ranks still share it), a block scan picks the digit.
-// The bars are found like in k_bar_median's leftover pass: 64 close indices per coalesced load.
 #define ML_MIN(F64) ((F64) ? 64 * 24 : 64 * 32)
 #define ML_THREADS 1024                  // threads per bar beyond ML_MID_MAX ticks (bins 0..255 of the scans are the first 256)
 #define ML_MID_MAX 8192
@@ -50,7 +50,7 @@ __global__ __launch_bounds__(THREADS) void k_bar_median_long(const void *__restr
     }
 }
 
-// bars of more than min_cnt ticks -> list (one thread per bar, one atomic per wave)
+// bars of more than min_cnt ticks -> list (one thread per bar, one atomic per wave; entries from [1]: not the bar list of fmk_bars.h)
 __global__ __launch_bounds__(256) void k_long_bar_list(const int64_t *__restrict__ ci, int64_t nb, int64_t min_cnt, int64_t max_cnt,
                                                        const int *__restrict__ go, int64_t *__restrict__ list, int64_t cap)
 {
@@ -177,24 +177,7 @@ __global__ __launch_bounds__(256) void k_bar_median(const void *__restrict__ amo
         }
         if (lane == 0) o_median[b] = m;
     };
-    if (min_cnt > 0) {
-        // the leftover pass of a small-bar kernel: 64 bars per step, one coalesced load of their close indices, then only the
-        // bars it left (longer than min_cnt) get the wave -- walking the bars one by one cost a dependent load per bar, 2.3 ms
-        // per 2.5e7 bars of which a few per cent were long
-        const int64_t ngroups = (nb + 63) >> 6;
-        for (int64_t g = wave0; g < ngroups; g += nwaves) {
-            const int64_t bl = g * 64 + lane;
-            int64_t s_l = 0, e_l = 0;
-            if (bl < nb) { s_l = ci[bl]; e_l = ci[bl + 1]; }
-            unsigned long long todo = __builtin_amdgcn_ballot_w64(bl < nb && e_l - s_l > min_cnt);
-            while (todo) {
-                const int bit = fmk_uniform((int)__builtin_ctzll(todo));
-                todo &= todo - 1;
-                do_bar(g * 64 + bit, fmk_readlane(s_l, bit), fmk_readlane(e_l, bit));
-            }
-        }
-        return;
-    }
+    if (min_cnt > 0) { fmk_for_long_bars(ci, nb, min_cnt, wave0, nwaves, lane, do_bar); return; }   // only the bars a small-bar kernel left
     for (int64_t b = wave0; b < nb; b += nwaves) do_bar(b, fmk_uniform(ci[b]), fmk_uniform(ci[b + 1]));
 }
 

@@ -32,6 +32,7 @@
 
 #include <utility>
 
+#include "fmk_bars.h"
 #include "fmk_common.h"
 #include "fmk_dpp.h"
 #include "fmk_f32tie.h"
@@ -89,7 +90,7 @@ __device__ __forceinline__ void ohlcv_finish(const OhlcvOut &o, int64_t b, const
         // matters in the last bits; bars that close to a float32 tie are redone in tick order by k_bar_vol_redo.
         if constexpr (AF64) {
             if (o.vol_redo && fmk_near_f32_tie(tv, fmk_f32tie_eps(e - start + 1) * fabs(tv)))
-                o.vol_redo[32 + atomicAdd(o.vol_redo, 1ULL)] = (unsigned long long)b;
+                fmk_list_push(o.vol_redo, (unsigned long long)b);
         }
     }
 }
@@ -106,7 +107,7 @@ __global__ __launch_bounds__(256) void k_bar_vol_redo(const double *__restrict__
     const int64_t count = (int64_t)redo[0];
     const int64_t nwaves = (int64_t)gridDim.x * 4;
     for (int64_t i = (int64_t)blockIdx.x * 4 + wib; i < count; i += nwaves) {
-        const int64_t b = fmk_uniform((int64_t)redo[32 + i]);
+        const int64_t b = fmk_uniform(fmk_list_entry(redo, i));
         const int64_t start = fmk_uniform(ci[b]) + 1, e = fmk_uniform(ci[b + 1]);
         double tv = 0.0;
         double v = start + lane <= e ? amount[start + lane] : 0.0;
@@ -446,23 +447,7 @@ __global__ __launch_bounds__(256) void k_bar_ohlcv(const double *__restrict__ pr
         }
         ohlcv_finish<AF64>(o, b, price, start, e, hi, lo, tv, td, lane);
     };
-    if (min_cnt > 0) {
-        // the leftover pass of a small-bar kernel: 64 bars per step, one coalesced load of their close indices, then only the
-        // bars it left (longer than min_cnt) get the wave (walking the bars one by one cost a dependent load per bar)
-        const int64_t ngroups = (nb + 63) >> 6;
-        for (int64_t g = wave0; g < ngroups; g += nwaves) {
-            const int64_t bl = g * 64 + lane;
-            int64_t s_l = 0, e_l = 0;
-            if (bl < nb) { s_l = ci[bl]; e_l = ci[bl + 1]; }
-            unsigned long long todo = __builtin_amdgcn_ballot_w64(bl < nb && e_l - s_l > min_cnt);
-            while (todo) {
-                const int bit = fmk_uniform((int)__builtin_ctzll(todo));
-                todo &= todo - 1;
-                do_bar(g * 64 + bit, fmk_readlane(s_l, bit), fmk_readlane(e_l, bit));
-            }
-        }
-        return;
-    }
+    if (min_cnt > 0) { fmk_for_long_bars(ci, nb, min_cnt, wave0, nwaves, lane, do_bar); return; }   // only the bars a small-bar kernel left
     for (int64_t b = wave0; b < nb; b += nwaves) do_bar(b, fmk_uniform(ci[b]), fmk_uniform(ci[b + 1]));
 }
 
@@ -547,12 +532,10 @@ __global__ __launch_bounds__(256, (MAXNCH <= 4 ? 8 : MAXNCH <= 10 ? 6 : 4)) void
         const int64_t e = fmk_uniform(ci[b + 1]);
         const int64_t cnt = e - s;
         if (cnt > 64 * MAXNCH) {                             // long bar: left to the generic kernels
-            // The flag only ever becomes 1: look first (shared reads do not serialise), store if still clear.  An
-            // atomicOr per long bar serialises on the one address (measured: 100 000 long bars -> 1.13 ms in this
-            // otherwise idle kernel, 11 ns each).  No state is kept across bars: a wave-uniform "already raised" bit
-            // made the register allocator park scalars in VGPR lanes throughout the small_bar bodies.
-            if (lane == 0 && __hip_atomic_load(saw_long, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0)
-                __hip_atomic_store(saw_long, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            // fmk_raise, not an atomicOr per long bar: that serialises on the one address (measured: 100 000 long bars ->
+            // 1.13 ms in this otherwise idle kernel, 11 ns each).  No state is kept across bars: a wave-uniform "already
+            // raised" bit made the register allocator park scalars in VGPR lanes throughout the small_bar bodies.
+            if (lane == 0) fmk_raise(saw_long);
             continue;
         }
         if (cnt <= 0) {
@@ -668,8 +651,7 @@ __global__ __launch_bounds__(256) void k_bar_median_small(const float *__restric
         const int64_t e = fmk_uniform(ci[b + 1]);
         const int64_t cnt = e - s;
         if (cnt > 64 * FMK_SMALL_NCH) {
-            if (lane == 0 && __hip_atomic_load(saw_long, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0)
-                __hip_atomic_store(saw_long, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            if (lane == 0) fmk_raise(saw_long);
             continue;
         }
         if (cnt <= 0) { if (lane == 0) o_median[b] = 0.0; continue; }     // base.py:352-361
@@ -708,54 +690,9 @@ int fmk_median_small_launch(fmk_ctx *ctx, const float *d_amount, const int64_t *
 // ~1: a wave takes the next <= 64 whole bars whose ticks fit its LDS tile; the tile is filled with coalesced loads (the bars
 // are one contiguous tick range); then lane l walks bar l's ticks in the tile -- max / min / sum(vol) / sum(price*vol) are
 // plain sequential register updates IN THE REFERENCE'S TICK ORDER (base.py:377-391: vwap comes out bit-identical, not just
-// within 1e-9) -- and sorts the bar's keys with a fixed compare-exchange network on its own registers (all lanes in
-// lockstep, two instructions per exchange, no cross-lane traffic at all).  Outputs are written coalesced, one bar per lane.
+// within 1e-9) -- and sorts the bar's keys with fmk_lane_sort on its own registers (all lanes in lockstep, two
+// instructions per exchange, no cross-lane traffic at all).  Outputs are written coalesced, one bar per lane.
 // Bars longer than 64 ticks are left to the generic kernels (flag `saw_long`).
-
-// bitonic sorting network on N registers of ONE lane; every index is a template constant, so the keys stay in VGPRs
-template <int I, int J, int K, int N>
-__device__ __forceinline__ void lb_ce(uint32_t (&r)[N])
-{
-    constexpr int l = I ^ J;
-    if constexpr (l > I) {
-        const uint32_t a = r[I], b = r[l];
-        const uint32_t mn = a < b ? a : b, mx = a < b ? b : a;
-        if constexpr ((I & K) == 0) { r[I] = mn; r[l] = mx; }
-        else { r[I] = mx; r[l] = mn; }
-    }
-}
-template <int J, int K, int N, int... I>
-__device__ __forceinline__ void lb_stage(uint32_t (&r)[N], std::integer_sequence<int, I...>)
-{
-    (lb_ce<I, J, K, N>(r), ...);
-}
-template <int J, int K, int N>
-__device__ __forceinline__ void lb_js(uint32_t (&r)[N])
-{
-    lb_stage<J, K, N>(r, std::make_integer_sequence<int, N>{});
-    if constexpr (J > 1) lb_js<J / 2, K, N>(r);
-}
-template <int K, int N>
-__device__ __forceinline__ void lb_ks(uint32_t (&r)[N])
-{
-    lb_js<K / 2, K, N>(r);
-    if constexpr (K < N) lb_ks<K * 2, N>(r);
-}
-template <int N>
-__device__ __forceinline__ void lb_sort(uint32_t (&r)[N]) { lb_ks<2, N>(r); }
-
-template <int N, int... I>
-__device__ __forceinline__ uint32_t lb_pick_seq(const uint32_t (&r)[N], int idx, std::integer_sequence<int, I...>)
-{
-    uint32_t v = r[0];
-    ((v = idx == I ? r[I] : v), ...);
-    return v;
-}
-template <int N>
-__device__ __forceinline__ uint32_t lb_pick(const uint32_t (&r)[N], int idx)
-{
-    return lb_pick_seq<N>(r, idx, std::make_integer_sequence<int, N>{});
-}
 
 // Block K (ticks 8K .. 8K+7) of a lane's bar: high / low, the eight tick slots' contribution to the two sums and the median
 // keys.  The sums are the balanced binary tree over the N tick slots in tick order (0.0 beyond the bar) -- the combining order
@@ -833,9 +770,9 @@ __device__ __forceinline__ void lb_bar(const double *tp, const uint32_t *ta, int
     const int Lmax = fmk_dpp_reduce(L, 0, FmkOpMax());               // wave-uniform: the longest bar of the wave
     lb_block<MEDIAN, N, 0, (MEDIAN ? N : 1)>(tp, ta, off, L, Lmax, zero_at, hi, lo, lv, ld, tv, td, r);
     if constexpr (MEDIAN) {
-        lb_sort<N>(r);
-        const uint32_t v1 = lb_pick<N>(r, (L - 1) >> 1), v2 = lb_pick<N>(r, L >> 1);
-        const uint32_t kmx = lb_pick<N>(r, L > 0 ? L - 1 : 0), kmn = r[0];
+        fmk_lane_sort<N>(r);
+        const uint32_t v1 = fmk_lane_pick<N>(r, (L - 1) >> 1), v2 = fmk_lane_pick<N>(r, L >> 1);
+        const uint32_t kmx = fmk_lane_pick<N>(r, L > 0 ? L - 1 : 0), kmn = r[0];
         if (kmn < MK::KEY_NEG_INF || kmx > MK::KEY_POS_INF) med = NAN;   // a NaN amount: np.median is NaN
         else med = (L & 1) ? MK::value(v1) : (MK::value(v1) + MK::value(v2)) / 2.0;
     }
@@ -860,11 +797,7 @@ __global__ __launch_bounds__(128) void k_bar_ohlcv_lanes(const double *__restric
     const int64_t nwaves = (int64_t)gridDim.x * 2;
     for (int64_t g = (int64_t)blockIdx.x * 2 + w; g < ngroups; g += nwaves) {
         const int64_t B0 = g * 64;
-        const int nbg = (int)(nb - B0 < 64 ? nb - B0 : 64);
-        __builtin_amdgcn_wave_barrier();
-        if (lane <= nbg) s_ci[w][lane] = ci[B0 + lane];
-        if (lane == 0 && nbg == 64) s_ci[w][64] = ci[B0 + 64];
-        __builtin_amdgcn_wave_barrier();
+        const int nbg = fmk_lane_group_load(s_ci[w], ci, nb, B0, lane);
         int bl = 0;
         while (bl < nbg) {
             const int64_t s0 = s_ci[w][bl];
@@ -874,8 +807,7 @@ __global__ __launch_bounds__(128) void k_bar_ohlcv_lanes(const double *__restric
             const int64_t s_l = valid ? s_ci[w][idx - 1] : 0;
             const int m = __popcll(__ballot(valid && e_l - s0 <= LB_TILE));     // closes ascend: a prefix of the lanes
             if (m == 0) {                                                        // one bar longer than the tile
-                if (lane == 0 && __hip_atomic_load(saw_long, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0)
-                    __hip_atomic_store(saw_long, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                if (lane == 0) fmk_raise(saw_long);
                 bl += 1;
                 continue;
             }
@@ -896,8 +828,7 @@ __global__ __launch_bounds__(128) void k_bar_ohlcv_lanes(const double *__restric
             const bool mine = owner && L > 0 && L <= 64;
             const int off = mine ? (int)(s_l - s0) : 0;
             const uint64_t longer = __ballot(owner && L > 64);                   // wave-long bars: generic kernels
-            if (longer && lane == 0 && __hip_atomic_load(saw_long, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0)
-                __hip_atomic_store(saw_long, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            if (longer && lane == 0) fmk_raise(saw_long);
             const int Lw = mine ? L : 0;
             const bool any_gt32 = __ballot(Lw > 32) != 0;
             const double first = ntick > 0 ? tp[off] : 0.0;
@@ -1207,8 +1138,7 @@ __global__ __launch_bounds__(64 * OHR_WAVES) void k_bar_ohlcv_rows(const double 
         const int64_t s_b = have ? ci[b] : 0, e_b = have ? ci[b + 1] : 0;
         const int64_t len_b = e_b - s_b;
         const bool is_long = have && len_b > LMAX;
-        if (__ballot(is_long) != 0 && lane == 0 && __hip_atomic_load(saw_long, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0)
-            __hip_atomic_store(saw_long, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (__ballot(is_long) != 0 && lane == 0) fmk_raise(saw_long);
         const bool mine = have && len_b >= 1 && len_b <= LMAX;
         if (have && len_b <= 0 && ri == 0) ohlcv_empty(o, b, price, e_b, n);          // base.py:352-361
         if (__ballot(mine) == 0) continue;
@@ -1736,8 +1666,8 @@ static int ohlcv_launch(fmk_ctx *ctx, const double *p, const void *a, const int6
         ci = tb->idx;
     }
     if (AF64) {   // redo list of near-tie volume sums (fmk_f32tie.h); nothing else here uses the context scratch
-        FMK_TRY(fmk_scratch(ctx, (size_t)(nb + 32) * 8, (void **)&o.vol_redo));
-        FMK_HIP(ctx, hipMemsetAsync(o.vol_redo, 0, 8, ctx->stream));
+        FMK_TRY(fmk_scratch(ctx, fmk_bar_list_words(nb) * 8, (void **)&o.vol_redo));
+        FMK_HIP(ctx, hipMemsetAsync(o.vol_redo, 0, FMK_BAR_LIST_CLEAR, ctx->stream));
     }
     if constexpr (!AF64)
         if (pl.kind == OHLCV_PIPELINED) return ohlcv_pipelined(ctx, pl, p, a, nb, n, o, tb);

@@ -16,6 +16,7 @@
 
 #include <utility>
 
+#include "fmk_bars.h"
 #include "fmk_median.h"
 #include "fmk_pairwise.h"
 #include "fmk_dpp.h"
@@ -136,10 +137,10 @@ __global__ __launch_bounds__(256, SMALL ? 4 : 1) void k_bar_trade_size(const voi
     const int64_t wave0 = (int64_t)blockIdx.x * wpb + wib;
     const int64_t nwaves = (int64_t)gridDim.x * wpb;
     K *buf = sbuf[wib];
-    // `only` (list mode: [0] = count, [32...] = bar numbers): the bars the lane-per-bar / row-per-bar schedules left to this one
-    const int64_t todo = only ? (int64_t)only[0] : nb;
+    // `only` (list mode): the bars the lane-per-bar / row-per-bar schedules left to this one
+    const int64_t todo = fmk_list_count(only, nb);
     for (int64_t it = wave0; it < todo; it += nwaves) {
-        const int64_t b = only ? fmk_uniform((int64_t)only[32 + it]) : it;
+        const int64_t b = fmk_list_bar(only, it);
         const int64_t s = fmk_uniform(ci[b]);
         const int64_t e_raw = fmk_uniform(ci[b + 1]);
         // The reference takes the bar as a SLICE, amounts[start:end + 1] (base.py:590): an end index past the array is
@@ -679,7 +680,7 @@ __device__ __forceinline__ bool tsm_one_wave5(int n)
     return same_depth && depth == 5 && nhi <= 95;
 }
 
-// `rest` (a list in k_bar_trade_size's format: [0] = count, [32 ...] = bar numbers): the bars neither this kernel nor the
+// `rest` (a bar list): the bars neither this kernel nor the
 // workgroup kernels (regular bars of TSM_MAX < ticks <= wg_hi) take
 template <int WAVES>
 __global__ __launch_bounds__(64 * WAVES, 4) void k_bar_trade_size_mid(const float *__restrict__ amount, const double *__restrict__ theta,
@@ -711,7 +712,7 @@ __global__ __launch_bounds__(64 * WAVES, 4) void k_bar_trade_size_mid(const floa
         const int64_t s = fmk_uniform(ci[b]), e = fmk_uniform(ci[b + 1]);
         const bool regular = s >= -1 && e <= n - 1;
         if (!(e - s > TSM_MIN && e - s <= TSM_MAX && regular)) {                                  // another launch's
-            if (lane == 0 && !(regular && e - s > TSM_MAX && e - s <= wg_hi)) rest[32 + atomicAdd(rest, 1ULL)] = (unsigned long long)b;
+            if (lane == 0 && !(regular && e - s > TSM_MAX && e - s <= wg_hi)) fmk_list_push(rest, (unsigned long long)b);
             continue;
         }
         const int cnt = (int)(e - s);
@@ -1142,51 +1143,13 @@ __global__ __launch_bounds__(64 * TSW_WAVES) void k_bar_trade_size_wide(const fl
 //     which one lane evaluates in NumPy's order; the same for sum((a / total)^2) (base.py:609);
 //   * block volume: float64 sum of the float32 sizes above the threshold (exact in any order; base.py:599-603 with the typed
 //     float64 accumulator);
-//   * np.percentile(., 95): the lane's keys through the fixed sorting network of fmk_ohlcv.hip's lane kernel (lb_sort), the two
+//   * np.percentile(., 95): the lane's keys through fmk_lane_sort, the two
 //     order statistics picked by index, NumPy's float32 lerp as in ts_percentile95.
 // Bars of more than 64 ticks, with irregular close indices (below -1 / beyond the column: Python slice semantics) or not fitting
 // the tile go on a list for the wave-per-bar kernel (list mode).
 // ---------------------------------------------------------------------------------------------------------------------
 #define TSL_TILE 2048
 #define TSL_WAVES 2
-
-// bitonic sorting network on N registers of ONE lane (every index a template constant: the keys stay in VGPRs)
-template <int I, int J, int K, int N>
-__device__ __forceinline__ void tsl_ce(uint32_t (&r)[N])
-{
-    constexpr int l = I ^ J;
-    if constexpr (l > I) {
-        const uint32_t a = r[I], b = r[l];
-        const uint32_t mn = a < b ? a : b, mx = a < b ? b : a;
-        if constexpr ((I & K) == 0) { r[I] = mn; r[l] = mx; }
-        else { r[I] = mx; r[l] = mn; }
-    }
-}
-template <int J, int K, int N, int... I>
-__device__ __forceinline__ void tsl_stage(uint32_t (&r)[N], std::integer_sequence<int, I...>) { (tsl_ce<I, J, K, N>(r), ...); }
-template <int J, int K, int N>
-__device__ __forceinline__ void tsl_js(uint32_t (&r)[N])
-{
-    tsl_stage<J, K, N>(r, std::make_integer_sequence<int, N>{});
-    if constexpr (J > 1) tsl_js<J / 2, K, N>(r);
-}
-template <int K, int N>
-__device__ __forceinline__ void tsl_ks(uint32_t (&r)[N])
-{
-    tsl_js<K / 2, K, N>(r);
-    if constexpr (K < N) tsl_ks<K * 2, N>(r);
-}
-template <int N>
-__device__ __forceinline__ void tsl_sort(uint32_t (&r)[N]) { tsl_ks<2, N>(r); }
-template <int N, int... I>
-__device__ __forceinline__ uint32_t tsl_pick_seq(const uint32_t (&r)[N], int idx, std::integer_sequence<int, I...>)
-{
-    uint32_t v = r[0];
-    ((v = idx == I ? r[I] : v), ...);
-    return v;
-}
-template <int N>
-__device__ __forceinline__ uint32_t tsl_pick(const uint32_t (&r)[N], int idx) { return tsl_pick_seq<N>(r, idx, std::make_integer_sequence<int, N>{}); }
 
 // NumPy's pairwise leaf of f(a[0..L)) for one lane, L <= N: blocks of eight elements, all lanes in lockstep up to the wave's
 // longest bar (Lmax, wave-uniform); `at(i)` gives element i of the lane's bar (LDS), idle slots are not touched
@@ -1250,13 +1213,13 @@ __device__ __forceinline__ void tsl_bar(const uint32_t *ta, int off, int L, doub
     const double sum = (double)tf;
     mean_rel = (float)log1p(mean / thr);
     // ---- np.percentile(., 95), every step in float32 (ts_percentile95)
-    tsl_sort<N>(r);
+    fmk_lane_sort<N>(r);
     const float vi = (float)(L - 1) * (95.0f / 100.0f);
     const int fl = (int)floorf(vi);
     const int k1 = fl < L - 1 ? fl : L - 1;
     const int k2 = k1 + 1 < L ? k1 + 1 : L - 1;
-    const uint32_t v1 = tsl_pick<N>(r, k1), v2 = tsl_pick<N>(r, k2);
-    const uint32_t kmx = tsl_pick<N>(r, L > 0 ? L - 1 : 0), kmn = r[0];
+    const uint32_t v1 = fmk_lane_pick<N>(r, k1), v2 = fmk_lane_pick<N>(r, k2);
+    const uint32_t kmx = fmk_lane_pick<N>(r, L > 0 ? L - 1 : 0), kmn = r[0];
     double p95;
     if (kmn < MK::KEY_NEG_INF || kmx > MK::KEY_POS_INF) p95 = NAN;     // a NaN size: np.percentile is NaN
     else {
@@ -1298,11 +1261,7 @@ __global__ __launch_bounds__(64 * TSL_WAVES) void k_bar_trade_size_lanes(const f
     const int64_t nwaves = (int64_t)gridDim.x * TSL_WAVES;
     for (int64_t g = (int64_t)blockIdx.x * TSL_WAVES + w; g < ngroups; g += nwaves) {
         const int64_t B0 = g * 64;
-        const int nbg = (int)(nb - B0 < 64 ? nb - B0 : 64);
-        __builtin_amdgcn_wave_barrier();
-        if (lane <= nbg) s_ci[w][lane] = ci[B0 + lane];
-        if (lane == 0 && nbg == 64) s_ci[w][64] = ci[B0 + 64];
-        __builtin_amdgcn_wave_barrier();
+        const int nbg = fmk_lane_group_load(s_ci[w], ci, nb, B0, lane);
         unsigned long long rest = 0;                                   // bars of this group left to the wave-per-bar kernel
         // a group whose close indices are not an ascending run inside the column goes to the wave kernel whole
         {
@@ -1427,7 +1386,7 @@ __global__ __launch_bounds__(64 * TSR_WAVES) void k_bar_trade_size_rows(const fl
     const float *fb = (const float *)ta;
     unsigned long long *left = s_left[w];
     int n_left = 0;                                                    // wave-uniform
-    // `only` (list mode: [0] = count, [32...] = bar numbers): the bars the lane-per-bar schedule left over
+    // `only` (list mode): the bars the lane-per-bar schedule left over
     const int64_t todo = only ? (int64_t)only[0] : nb;
     const int64_t niter = (todo + 3) >> 2;
     const int64_t nwaves = (int64_t)gridDim.x * TSR_WAVES;
@@ -1437,7 +1396,7 @@ __global__ __launch_bounds__(64 * TSR_WAVES) void k_bar_trade_size_rows(const fl
         if (lane == 0) base = atomicAdd(rest_out, (unsigned long long)n_left);
         base = (unsigned long long)fmk_uniform((int64_t)base);
         __builtin_amdgcn_wave_barrier();
-        if (lane < n_left) rest_out[32 + base + lane] = left[lane];
+        if (lane < n_left) rest_out[FMK_BAR_LIST_HEAD + base + lane] = left[lane];
         __builtin_amdgcn_wave_barrier();
         n_left = 0;
     };
@@ -1453,7 +1412,7 @@ __global__ __launch_bounds__(64 * TSR_WAVES) void k_bar_trade_size_rows(const fl
     for (int64_t it = (int64_t)blockIdx.x * TSR_WAVES + w; it < niter; it += nwaves) {
         const int64_t q = 4 * it + row;                                // four bars per wave, one per row of 16 lanes
         const bool have = q < todo;
-        const int64_t b = have ? (only ? (int64_t)only[32 + q] : q) : 0;
+        const int64_t b = have ? (only ? fmk_list_entry(only, q) : q) : 0;
         const int64_t s_b = have ? ci[b] : 0, e_b = have ? ci[b + 1] : 0;
         const bool regular = s_b >= -1 && e_b >= s_b && e_b <= n - 1;
         const int64_t len_b = e_b - s_b;
@@ -1615,7 +1574,7 @@ __global__ __launch_bounds__(64 * TSR_WAVES) void k_bar_trade_size_rows(const fl
     flush();
 }
 
-// list of the bars the lane kernel left over: rest[0] = count (from the scan's total), rest[32 + pos[g] + k] = the k-th set bit of group g
+// list of the bars the lane kernel left over: rest[0] = count (from the scan's total), rest[FMK_BAR_LIST_HEAD + pos[g] + k] = the k-th set bit of group g
 static __global__ __launch_bounds__(256) void k_tsl_compact(const unsigned long long *__restrict__ grp_mask,
                                                             const int64_t *__restrict__ pos, int64_t groups,
                                                             unsigned long long *__restrict__ rest)
@@ -1624,7 +1583,7 @@ static __global__ __launch_bounds__(256) void k_tsl_compact(const unsigned long 
     if (g == 0) rest[0] = (unsigned long long)pos[groups];
     if (g >= groups) return;
     unsigned long long m = grp_mask[g];
-    int64_t at = 32 + pos[g];
+    int64_t at = FMK_BAR_LIST_HEAD + pos[g];
     while (m) {
         const int bit = __builtin_ctzll(m);
         rest[at++] = (unsigned long long)(g * 64 + bit);
@@ -1665,12 +1624,12 @@ extern "C" int fmk_comp_bar_trade_size_dev(fmk_ctx *ctx, const void *d_amount, i
             const int64_t groups = fmk_ceil_div(nb, 64);
             unsigned long long *rest = nullptr, *rest2 = nullptr, *grp_mask = nullptr;
             int64_t *grp_cnt = nullptr;
-            int arc = fmk_alloc(ctx, (size_t)(nb + 32) * 8, (void **)&rest2);
-            if (arc == FMK_OK && use_lanes) arc = fmk_alloc(ctx, (size_t)(nb + 32) * 8, (void **)&rest);
+            int arc = fmk_alloc(ctx, fmk_bar_list_words(nb) * 8, (void **)&rest2);
+            if (arc == FMK_OK && use_lanes) arc = fmk_alloc(ctx, fmk_bar_list_words(nb) * 8, (void **)&rest);
             if (arc == FMK_OK && use_lanes) arc = fmk_alloc(ctx, (size_t)groups * 8, (void **)&grp_mask);
             if (arc == FMK_OK && use_lanes) arc = fmk_alloc(ctx, (size_t)(groups + 1) * 8, (void **)&grp_cnt);
             hipError_t le = hipSuccess;
-            if (arc == FMK_OK) le = hipMemsetAsync(rest2, 0, 8, ctx->stream);
+            if (arc == FMK_OK) le = hipMemsetAsync(rest2, 0, FMK_BAR_LIST_CLEAR, ctx->stream);
             if (arc == FMK_OK && le == hipSuccess && use_lanes) {
                 int64_t lb = fmk_ceil_div(groups, TSL_WAVES);
                 const int64_t lcap = (int64_t)ctx->n_cu * 32;
@@ -1766,8 +1725,8 @@ extern "C" int fmk_comp_bar_trade_size_dev(fmk_ctx *ctx, const void *d_amount, i
                                                                                    d_mean_size_rel, d_size_95_rel, d_pct_block, d_size_gini);
             k_bar_trade_size_wg<16><<<(unsigned)(ctx->n_cu * 2), 1024, 0, ctx->stream>>>(af, d_theta, d_close_idx, wg_lists[3], n, theta_mult,
                                                                                      d_mean_size_rel, d_size_95_rel, d_pct_block, d_size_gini);
-            rc = fmk_alloc(ctx, (size_t)(nb + 32) * 8, (void **)&rest);
-            if (rc == FMK_OK && hipMemsetAsync(rest, 0, 8, ctx->stream) != hipSuccess) rc = FMK_E_HIP;
+            rc = fmk_alloc(ctx, fmk_bar_list_words(nb) * 8, (void **)&rest);
+            if (rc == FMK_OK && hipMemsetAsync(rest, 0, FMK_BAR_LIST_CLEAR, ctx->stream) != hipSuccess) rc = FMK_E_HIP;
             if (rc == FMK_OK)
                 k_bar_trade_size_mid<4><<<(unsigned)blocks, 256, 0, ctx->stream>>>(af, d_theta, d_close_idx, nb, n, theta_mult,
                                                                                    d_mean_size_rel, d_size_95_rel, d_pct_block,

@@ -85,6 +85,49 @@ def test_a_bar_gets_the_same_bits_in_any_stream(orc):
         pos = hi
 
 
+def _packer_edge_streams():
+    """(name, bar lengths) of the three streams of test_lane_packer_edges; every stream starts at close index -1 and ends at n - 1,
+    and has a mean below 33 ticks per bar, so that comp_bar_ohlcv with the median takes the lane-per-bar schedule"""
+    rng = np.random.default_rng(31)
+    short = lambda k: rng.integers(3, 21, size=k)
+    a = np.full(64 * 3 + 1, 32)
+    b = np.concatenate([short(64), short(20), [1], short(10), [64], short(10), [65], short(10), [2049], short(10), short(128)])
+    c = np.concatenate([short(64), [0], short(63)])
+    return [("64 * 3 + 1 bars of 32 ticks", a), ("1 / 64 / 65 / 2049 ticks among short bars", b), ("a group that starts empty", c)]
+
+
+@pytest.mark.parametrize("which", [0, 1, 2])
+def test_lane_packer_edges(orc, monkeypatch, which):
+    """The edges of the lane-per-bar packer (k_bar_ohlcv_lanes with its 1 024-tick tile, k_bar_trade_size_lanes with its 2 048-tick
+    tile; csrc/fmk_bars.h) against the oracle, bit for bit (vwap as in _check):
+      0: 64 * 3 + 1 bars of exactly 32 ticks -- 64 bars fill the trade-size tile exactly, the OHLCV tile splits each group in two, the
+         last group holds one bar;
+      1: a group with a bar of 1, of 64, of 65 and of 2 049 ticks (the first length that does not fit the trade-size tile) between
+         60 short bars, groups of short bars around it;
+      2: a group whose first bar is empty and whose last close index is n - 1."""
+    from finmlkit_amd import engine
+    name, lens = _packer_edge_streams()[which]
+    ci = np.concatenate([[-1], np.cumsum(lens) - 1]).astype(np.int64)
+    n = int(ci[-1]) + 1
+    nb = len(ci) - 1
+    assert nb >= 64 and n // nb < 33 and ci[-1] == n - 1
+    if which == 1:
+        assert list(lens[84:64 + 64:11]) == [1, 64, 65, 2049]
+    if which == 2:
+        assert ci[64] == ci[65]
+    rng = np.random.default_rng(100 + which)
+    ts, px, _, sd = orc.synth(7, 0, n)
+    am = rng.lognormal(-1, 1.2, n).astype(np.float32)
+    t = engine.DeviceTrades.from_numpy(ts, px, am, sd)
+    _check(orc, t, engine, px, am, ci, name)
+    monkeypatch.setenv("FMK_TS_LANES", "2")                              # the lane-per-bar schedule whatever the number of bars
+    theta = np.full(nb, float(np.median(am)))
+    want = orc.comp_bar_trade_size_features(am, theta, ci, 5.0)
+    got = t.bar_trade_size(engine.DeviceArray.from_host(t.ctx, ci), theta, 5.0)
+    for k, w in zip(["mean_size_rel", "size_95_rel", "pct_block", "size_gini"], want):
+        np.testing.assert_array_equal(got[k], w, err_msg=f"{name}: {k}")
+
+
 @pytest.mark.parametrize("gscale", ["0", "0.3"])
 def test_wide_median_bracket_miss_takes_the_radix_select(orc, monkeypatch, gscale):
     """FMK_WIDE_MED_GSCALE shrinks the sample bracket of the one-pass wide kernel so that it misses for most bars: those go through

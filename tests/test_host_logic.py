@@ -203,3 +203,23 @@ def test_window_walk_step_plan(tmp_path):
     r = subprocess.run([exe], capture_output=True, text=True)
     assert r.returncode == 0, r.stdout
     assert "walk plans checked: 638200, failed checks: 0" in r.stdout
+
+
+def test_lane_sorting_network(tmp_path):
+    """The one-lane sorting network of csrc/fmk_bars.h (fmk_lane_sort / fmk_lane_pick, plain C++ that k_bar_ohlcv_lanes and
+    k_bar_trade_size_lanes run on a lane's registers) on the host by tools/lanesort_check.cpp, at the sizes the kernels instantiate.
+    N = 16: all 2^16 zero-one inputs (the zero-one principle: the network sorts any 16 keys).  N = 32 and 64: the 256 zero-one inputs
+    that repeat one 8-bit pattern per aligned block of 8, the N + 1 threshold patterns of each of 1 000 seeded permutations, 10 000
+    seeded key arrays with duplicates, 0, 0xFFFFFFFF (the padding key) and the infinity keys.  Every output equals std::sort of its
+    input and fmk_lane_pick(r, i) == r[i] for every i.  65 536 + (256 + 33 000 + 10 000) + (256 + 65 000 + 10 000) arrays."""
+    import os
+    import shutil
+    import subprocess
+    if not shutil.which("g++"):
+        pytest.skip("no g++")
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    exe = str(tmp_path / "lanesort_check")
+    subprocess.check_call(["g++", "-O2", "-std=c++17", os.path.join(root, "tools", "lanesort_check.cpp"), "-o", exe])
+    r = subprocess.run([exe], capture_output=True, text=True)
+    assert r.returncode == 0, r.stdout
+    assert "lane sorts checked: 184048, failed checks: 0" in r.stdout
