@@ -27,6 +27,7 @@
 #include "fmk_common.h"
 #include "fmk_log.h"
 #include "fmk_scan.h"
+#include "fmk_cusum_rule.h"
 
 #define CS_CHUNK 2048          // ticks per thread
 #define CS_THREADS 64
@@ -196,16 +197,13 @@ __global__ __launch_bounds__(FF_THREADS) void k_ff_apply(double *__restrict__ x,
 // ---------------------------------------------------------------------------------------
 // chunk simulation
 // ---------------------------------------------------------------------------------------
-struct CsState { double sp, sn; };
-
 // Per-tick inputs of the loop, computed ONCE and stored chunk-TRANSPOSED in blocks of 64 chunks -- element j of chunk k at
 // [((k >> 6) * CS_CHUNK + j) * 64 + (k & 63)] -- so that the one-thread-per-chunk simulation below streams 512 contiguous
 // bytes per wave, array and tick, one after the other:
-//   ret[t] = log(p_i / p_{i-1})                                             (logic.py:200)
-//   lam[t] = max(sigma_mult * sigma_i, sigma_floor), NaN inside a same-timestamp print block (logic.py:206-211):
-//            a NaN threshold can never be reached, which is exactly "this tick cannot close a bar"
-// for tick i = first + 1 + t, t = k * CS_CHUNK + j.  Tiles of 32 chunks x 64 ticks through LDS: every wave instruction of the
-// read side takes 512 contiguous bytes of a column, the write side fills 256-byte halves of adjacent rows.  (The first layout,
+// ret[t] and lam[t]: cs_input (fmk_cusum_rule.h) of tick i = first + 1 + t, t = k * CS_CHUNK + j.  The kernels of this file that must
+// keep their instruction order (k_cusum_prep, k_cusum_walk, k_cs1_pass) have cs_input and cs_tick written out, operation for
+// operation: a difference in one of them silently moves closes.  Tiles of 32 chunks x 64 ticks through LDS: every wave instruction of
+// the read side takes 512 contiguous bytes of a column, the write side fills 256-byte halves of adjacent rows.  (The first layout,
 // [j * chunks + k] with 64 x 32 tiles, read 256-byte pieces 16 KB apart and wrote rows 3.9 MB apart: 12.3 ms per 1e9 ticks.)
 #define CS_PREP_TK 32           // chunks per tile
 #define CS_PREP_TJ 64           // ticks per tile: 33.3 KB of LDS -> four workgroups per CU
@@ -231,7 +229,7 @@ __global__ __launch_bounds__(256) void k_cusum_prep(const int64_t *__restrict__ 
             double r = 0.0, lam = NAN;
             if (k0 + row < chunks && t < m) {
                 const int64_t i = first + 1 + t;
-                r = fmk_log_ratio(price[i], price[i - 1]);
+                r = fmk_log_ratio(price[i], price[i - 1]);               // cs_input, written out, operation for operation
                 const bool block = i + 1 < n && ts[i] == ts[i + 1];
                 const double sg = sigma[i];
                 nan_sigma |= sg != sg;
@@ -334,11 +332,6 @@ __global__ void k_cusum_first(int64_t *closes, int64_t first) { closes[0] = firs
 // it becomes right: the loop ends within `chunks` launches; a torn read of a neighbour that is being rewritten only
 // produces an input the next mark pass rejects.
 // ---------------------------------------------------------------------------------------
-__device__ __forceinline__ bool cs_same(CsState a, CsState b)
-{
-    return __double_as_longlong(a.sp) == __double_as_longlong(b.sp) && __double_as_longlong(a.sn) == __double_as_longlong(b.sn);
-}
-
 __global__ __launch_bounds__(256) void k_cusum_mark(const CsState *__restrict__ S, const CsState *__restrict__ last_in,
                                                     int64_t chunks, unsigned char *__restrict__ active,
                                                     int *__restrict__ list, unsigned long long *count)
@@ -349,14 +342,6 @@ __global__ __launch_bounds__(256) void k_cusum_mark(const CsState *__restrict__ 
     if (k > 0 && !cs_same(S[k - 1], last_in[k])) act = k == 1 || cs_same(S[k - 2], last_in[k - 1]);    // ... and k - 1 consistent
     active[k] = act ? 1 : 0;
     if (act) list[atomicAdd(count, 1ULL)] = (int)k;
-}
-
-__device__ __forceinline__ double cs_lane(double v, int src)
-{
-    const long long b = __double_as_longlong(v);
-    const unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)b, src);
-    const unsigned hi = (unsigned)__builtin_amdgcn_readlane((int)((unsigned long long)b >> 32), src);
-    return __longlong_as_double((long long)(((unsigned long long)hi << 32) | lo));
 }
 
 __global__ __launch_bounds__(256) void k_cusum_walk(const int64_t *__restrict__ ts, const double *__restrict__ price,
@@ -400,9 +385,6 @@ __global__ __launch_bounds__(256) void k_cusum_walk(const int64_t *__restrict__ 
             }
         };
         fetch(0, c_p, c_pm, c_sg, c_ts, c_tsn);
-#ifdef CS_TIMING
-        long long tA = 0, tB = 0, t0c = __builtin_readcyclecounter(), t1c;
-#endif
         for (int j0 = 0; j0 < len; j0 += 64 * G) {
             double n_p[G], n_pm[G], n_sg[G];
             int64_t n_ts[G], n_tsn[G];
@@ -413,7 +395,7 @@ __global__ __launch_bounds__(256) void k_cusum_walk(const int64_t *__restrict__ 
             for (int g = 0; g < G; ++g) {
                 const int jj = j0 + 64 * g + lane;
                 double r = 0.0, lam = NAN;
-                if (jj < len) {                                         // the expressions of k_cusum_prep
+                if (jj < len) {                                         // cs_input, written out, operation for operation
                     const int64_t i = first + 1 + t0 + jj;
                     r = fmk_log_ratio(c_p[g], c_pm[g]);
                     const bool block = i + 1 < n && c_ts[g] == c_tsn[g];
@@ -427,9 +409,6 @@ __global__ __launch_bounds__(256) void k_cusum_walk(const int64_t *__restrict__ 
                 c_p[g] = n_p[g]; c_pm[g] = n_pm[g]; c_sg[g] = n_sg[g]; c_ts[g] = n_ts[g]; c_tsn[g] = n_tsn[g];
             }
             __builtin_amdgcn_wave_barrier();
-#ifdef CS_TIMING
-            t1c = __builtin_readcyclecounter(); tA += t1c - t0c; t0c = t1c;
-#endif
             const int lim = len - j0 < 64 * G ? len - j0 : 64 * G;
             if (lane == 0) {
                 for (int q8 = 0; q8 < lim; q8 += 8) {
@@ -452,7 +431,7 @@ __global__ __launch_bounds__(256) void k_cusum_walk(const int64_t *__restrict__ 
                         }
                         if (__builtin_amdgcn_ballot_w64(any) == 0) { sp = p; sn = g2; continue; }
                     }
-                    for (int q = q8; q < q8 + nq; ++q) {                // the loop of k_cusum_chunks, as selects
+                    for (int q = q8; q < q8 + nq; ++q) {                // cs_tick, written out
                         const double ret = s_r[wib][q], lm = s_l[wib][q];
                         const double a = sp + ret, b = sn + ret;
                         sp = a > 0.0 ? a : 0.0;
@@ -466,13 +445,7 @@ __global__ __launch_bounds__(256) void k_cusum_walk(const int64_t *__restrict__ 
                 }
             }
             __builtin_amdgcn_wave_barrier();
-#ifdef CS_TIMING
-            t1c = __builtin_readcyclecounter(); tB += t1c - t0c; t0c = t1c;
-#endif
         }
-#ifdef CS_TIMING
-        if (lane == 0 && w == 0 && step == 0) printf("cusum walk, one chunk of %d ticks: compute r/lam %lld cycles, lane-0 walk %lld cycles\n", len, tA, tB);
-#endif
         sp = cs_lane(sp, 0); sn = cs_lane(sn, 0);
         if (lane == 0) {
             last_in[k] = in;
@@ -512,34 +485,19 @@ static int cs1_run(fmk_ctx *ctx, const int64_t *d_ts, const double *d_price, con
     *done = 0; *redo = false;
     const int64_t chunks = fmk_ceil_div(m, (int64_t)CS1_L);
     g_cs1_last[0] = 0; g_cs1_last[1] = 0; g_cs1_last[2] = 0; g_cs1_last[3] = chunks;
-    const size_t scan_bytes = (((size_t)fmk_ceil_div(chunks + 1, FMK_SCAN_TILE) + 1) * 8 + 255) & ~(size_t)255;
-    const size_t st_bytes = ((size_t)chunks * sizeof(CsState) + 255) & ~(size_t)255;
-    const size_t cnt_bytes = ((size_t)(chunks + 1) * 8 + 255) & ~(size_t)255;
-    const size_t c0_bytes = ((size_t)chunks * 4 + 255) & ~(size_t)255;
-    const size_t fix_bytes = ((size_t)chunks * sizeof(Cs1Fix) + 255) & ~(size_t)255;
-    const size_t row_bytes = ((size_t)chunks * CS1_L * 2 + 255) & ~(size_t)255;
-    void *scr;
-    FMK_TRY(fmk_scratch(ctx, scan_bytes + 5 * st_bytes + cnt_bytes + c0_bytes + fix_bytes + 2 * row_bytes, &scr));
-    char *base = (char *)scr + scan_bytes;
-    CsState *S = (CsState *)base, *S_read = (CsState *)(base + st_bytes), *last_in = (CsState *)(base + 2 * st_bytes);
-    CsState *S0 = (CsState *)(base + 3 * st_bytes), *E = (CsState *)(base + 4 * st_bytes);
-    int64_t *counts = (int64_t *)(base + 5 * st_bytes);
-    int *C0 = (int *)(base + 5 * st_bytes + cnt_bytes);
-    Cs1Fix *fix = (Cs1Fix *)(base + 5 * st_bytes + cnt_bytes + c0_bytes);
-    unsigned short *staged = (unsigned short *)(base + 5 * st_bytes + cnt_bytes + c0_bytes + fix_bytes);
-    unsigned short *patch = (unsigned short *)(base + 5 * st_bytes + cnt_bytes + c0_bytes + fix_bytes + row_bytes);
-    fmk_mail::Cusum::Round *d_round = &ctx->d_mail->cusum.round, r;
+    Cs1Work w;
+    FMK_TRY(cs1_work(ctx, chunks, &w));
+    fmk_mail::Cusum::Round *d_round = w.d_round, r;
     unsigned long long *d_changed = &d_round->changed, *d_pending = &d_round->pending, *d_nan = &d_round->nan;
     if (check_nan) FMK_HIP(ctx, hipMemsetAsync(d_nan, 0, 8, ctx->stream));
-    FMK_HIP(ctx, hipMemsetAsync(fix, 0, fix_bytes, ctx->stream));
     {
         const unsigned g = (unsigned)fmk_ceil_div(chunks, (int64_t)CS1_TK);
         unsigned long long *nf = check_nan ? d_nan : nullptr;
-        k_cs1_pass<<<g, 256, 0, ctx->stream>>>(d_ts, d_price, d_sigma, n, first, m, chunks, sigma_floor, sigma_mult, E, S0, C0, staged, nf);
+        k_cs1_pass<<<g, 256, 0, ctx->stream>>>(d_ts, d_price, d_sigma, n, first, m, chunks, sigma_floor, sigma_mult, w.E, w.S0, w.C0,
+                                               w.staged, nf);
         FMK_LAUNCH_CHECK(ctx);
     }
-    FMK_HIP(ctx, hipMemcpyAsync(S, S0, (size_t)chunks * sizeof(CsState), hipMemcpyDeviceToDevice, ctx->stream));
-    FMK_HIP(ctx, hipMemcpyAsync(last_in, E, (size_t)chunks * sizeof(CsState), hipMemcpyDeviceToDevice, ctx->stream));   // every record was made from E
+    FMK_TRY(cs1_after_pass(ctx, w));
     *rounds = 1;
     int limit = CS1_FIRST_LIMIT;
     int64_t launches = 0;
@@ -548,12 +506,12 @@ static int cs1_run(fmk_ctx *ctx, const int64_t *d_ts, const double *d_price, con
         if (r.nan != 0) { *redo = true; return FMK_OK; }
     }
     while (chunks > 1) {
-        FMK_HIP(ctx, hipMemcpyAsync(S_read, S, (size_t)chunks * sizeof(CsState), hipMemcpyDeviceToDevice, ctx->stream));
-        FMK_HIP(ctx, hipMemsetAsync(d_changed, 0, 8, ctx->stream));
+        FMK_TRY(cs1_round_begin(ctx, w));
+        FMK_HIP(ctx, hipMemsetAsync(d_changed, 0, 8, ctx->stream));         // (not the whole record: pass A's NaN flag stands)
         FMK_HIP(ctx, hipMemsetAsync(d_pending, 0, 8, ctx->stream));
         k_cs1_fix<<<(unsigned)fmk_ceil_div(chunks - 1, (int64_t)4), 256, 0, ctx->stream>>>(
-            d_ts, d_price, d_sigma, n, first, m, chunks, sigma_floor, sigma_mult, E, S0, S_read, S, last_in, fix, patch, limit,
-            d_changed, d_pending);
+            d_ts, d_price, d_sigma, n, first, m, chunks, sigma_floor, sigma_mult, w.E, w.S0, w.S_read, w.S, w.last_in, w.fix, w.patch,
+            limit, d_changed, d_pending);
         FMK_LAUNCH_CHECK(ctx);
         ++launches; ++*rounds;
         FMK_TRY(fmk_read_back(ctx, &r, d_round, sizeof r));
@@ -568,18 +526,8 @@ static int cs1_run(fmk_ctx *ctx, const int64_t *d_ts, const double *d_price, con
         if (changed == 0 && pending == 0) break;
         if (launches >= CS1_MAX_LAUNCHES) return FMK_OK;
     }
-    k_cs1_counts<<<(unsigned)fmk_ceil_div(chunks, (int64_t)256), 256, 0, ctx->stream>>>(C0, fix, chunks, counts);
-    FMK_LAUNCH_CHECK(ctx);
-    FMK_TRY(fmk_exclusive_scan_i64(ctx, counts, counts, chunks, true));
-    FMK_TRY(fmk_read_back(ctx, total, counts + chunks, 8));
-    if (d_out) {
-        if (capacity < *total + 1)
-            return fmk_set_error(ctx, FMK_E_CAPACITY, "cusum: %lld close indices, capacity %lld", (long long)(*total + 1),
-                                 (long long)capacity);
-        k_cs1_emit<<<(unsigned)fmk_ceil_div(chunks, (int64_t)4), 256, 0, ctx->stream>>>(C0, fix, staged, patch, chunks, first, counts,
-                                                                                      d_out + 1);
-        FMK_LAUNCH_CHECK(ctx);
-    }
+    // the opening entry d_out[0] is the caller's: total + 1 entries, the closes from d_out + 1
+    FMK_TRY(cs1_emit_all(ctx, w, chunks, first, d_out, 1, capacity, "cusum: %lld close indices, capacity %lld", total));
     g_cs1_last[0] = 1;
     *done = 1;
     return FMK_OK;

@@ -42,6 +42,7 @@
 #include "fmk_common.h"
 #include "fmk_log.h"
 #include "fmk_dpp.h"
+#include "fmk_cusum_rule.h"
 
 #define CC_CHUNK 2048
 #define CC_SUB 512                      // ticks a wave of k_cc_summary stages at a time
@@ -85,34 +86,6 @@ __device__ __forceinline__ CcSum cc_compose(const CcSum &l, const CcSum &r)
 }
 __device__ __forceinline__ double cc_shfl_down(double v, int d) { return __shfl_down(v, d, 64); }
 __device__ __forceinline__ double cc_shfl_up(double v, int d) { return __shfl_up(v, d, 64); }
-__device__ __forceinline__ double cc_bcast(double v, int src)
-{
-    const long long b = __double_as_longlong(v);
-    const unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)b, src);
-    const unsigned hi = (unsigned)__builtin_amdgcn_readlane((int)((unsigned long long)b >> 32), src);
-    return __longlong_as_double((long long)(((unsigned long long)hi << 32) | lo));
-}
-
-__device__ __forceinline__ int64_t cc_bcast_i64(int64_t v, int src)
-{
-    const unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)v, src);
-    const unsigned hi = (unsigned)__builtin_amdgcn_readlane((int)((unsigned long long)v >> 32), src);
-    return (int64_t)(((unsigned long long)hi << 32) | lo);
-}
-
-// r_i and lam_i of tick i = first + 1 + t: the expressions of k_cusum_prep (fmk_cusum.hip), NaN lam = "cannot close"
-__device__ __forceinline__ void cc_tick(double p, double pm, double sg, int64_t tsi, int64_t tsn, bool has_next,
-                                        double sigma_floor, double sigma_mult, double *r, double *lam)
-{
-    *r = fmk_log_ratio(p, pm);
-    double l = NAN;
-    if (!(has_next && tsi == tsn)) {
-        l = sigma_mult * sg;
-        l = sigma_floor > l ? sigma_floor : l;
-    }
-    *lam = l;
-}
-
 // ordered composition over the lanes on the DPP path (lane 63 ends up with lanes 0 .. 63 composed left to right; the order of
 // fmk_dpp_iscan).  The first version was a shuffle-down tree: 96 ds_bpermute per 512 ticks and their LDS round trips.
 template <int CTRL, int ROW_MASK>
@@ -187,8 +160,8 @@ __global__ __launch_bounds__(256) void k_cc_summary(const int64_t *__restrict__ 
                 double r = 0.0, lam = NAN;
                 if (tq + q < m) {
                     const int64_t i = i0 + q;
-                    cc_tick(p[q], q == 0 ? pm0 : p[q > 0 ? q - 1 : 0], sg[q], a[q], q == 7 ? an : a[q < 7 ? q + 1 : 7], i + 1 < n,
-                            sigma_floor, sigma_mult, &r, &lam);
+                    cs_input(p[q], q == 0 ? pm0 : p[q > 0 ? q - 1 : 0], sg[q], a[q], q == 7 ? an : a[q < 7 ? q + 1 : 7], i + 1 < n,
+                            sigma_floor, sigma_mult, r, lam);
                     bad |= !(fabs(r) < INFINITY);
                     nan_sigma |= sg[q] != sg[q];
                 }
@@ -254,7 +227,7 @@ __device__ __forceinline__ double cc_replay(const double *__restrict__ price, in
         const double r = fmk_log_ratio(price[i], price[i - 1]);
         const int cnt = (int)(t_to - base + 1 < 64 ? t_to - base + 1 : 64);
         for (int k = 0; k < cnt; ++k) {
-            const double rk = cc_bcast(r, k);
+            const double rk = cs_lane(r, k);
             s = positive ? fmax(0.0, s + rk) : fmin(0.0, s + rk);
         }
     }
@@ -335,7 +308,7 @@ __global__ __launch_bounds__(64 * CC_WALK_WAVES, 2) void k_cc_walk(const int64_t
         for (int g = 0; g < RW; ++g) {
             const int j = 64 * (wv + CC_WALK_WAVES * g) + lane;
             double r = 0.0, lam = NAN;
-            if (j < len) cc_tick(p[g], pm[g], sg[g], a[g], b[g], first + 1 + tq + j + 1 < n, sigma_floor, sigma_mult, &r, &lam);
+            if (j < len) cs_input(p[g], pm[g], sg[g], a[g], b[g], first + 1 + tq + j + 1 < n, sigma_floor, sigma_mult, r, lam);
             s_r[j + (j >> 3)] = r;
             s_l[j + (j >> 3)] = lam;
         }
@@ -400,7 +373,7 @@ __global__ __launch_bounds__(64 * CC_WALK_WAVES, 2) void k_cc_walk(const int64_t
             if (cb == 0) {
                 const int64_t left = chunk_limit - c;
                 const int last = left >= 64 ? 63 : (int)left - 1;
-                const double oB = cc_bcast(inc.B, last), oAp = cc_bcast(inc.Ap, last), oAn = cc_bcast(inc.An, last);
+                const double oB = cs_lane(inc.B, last), oAp = cs_lane(inc.Ap, last), oAn = cs_lane(inc.An, last);
                 sp = fmax(oAp, sp + oB); sn = fmin(oAn, sn + oB);
                 c = left >= 64 ? c + 64 : chunk_limit;                    // (the next launch resumes at `c`)
 #ifdef CC_TIMING
@@ -409,8 +382,8 @@ __global__ __launch_bounds__(64 * CC_WALK_WAVES, 2) void k_cc_walk(const int64_t
             } else {
                 const int f = __builtin_ctzll(cb);
                 k = c + f;
-                k_sp = cc_bcast(in_p, f); k_sn = cc_bcast(in_n, f);
-                U_k = cc_bcast(cur.U, f);
+                k_sp = cs_lane(in_p, f); k_sn = cs_lane(in_n, f);
+                U_k = cs_lane(cur.U, f);
             }
         }
         if (k < 0) { load_batch(c); CC_TICK(tG) continue; }
@@ -447,14 +420,14 @@ __global__ __launch_bounds__(64 * CC_WALK_WAVES, 2) void k_cc_walk(const int64_t
             const unsigned long long sc = __builtin_amdgcn_ballot_w64(scand);
             mag_p = sg_p; mag_n = sg_n;
             if (sc == 0) {                                                // the rest of the chunk passes without an event
-                const double oB = cc_bcast(sinc.B, CC_CHUNK / CC_SUB - 1), oAp = cc_bcast(sinc.Ap, CC_CHUNK / CC_SUB - 1);
-                const double oAn = cc_bcast(sinc.An, CC_CHUNK / CC_SUB - 1);
+                const double oB = cs_lane(sinc.B, CC_CHUNK / CC_SUB - 1), oAp = cs_lane(sinc.Ap, CC_CHUNK / CC_SUB - 1);
+                const double oAn = cs_lane(sinc.An, CC_CHUNK / CC_SUB - 1);
                 sp = fmax(oAp, sp + oB); sn = fmin(oAn, sn + oB);
                 break;
             }
             const int sf = __builtin_ctzll(sc);
-            sp = cc_bcast(si_p, sf); sn = cc_bcast(si_n, sf);
-            const double U_s = cc_bcast(sb.U, sf);
+            sp = cs_lane(si_p, sf); sn = cs_lane(si_n, sf);
+            const double U_s = cs_lane(sb.U, sf);
             if (visits >= visit_budget) { status = CC_ST_BUDGET; break; }
             ++visits;
             const int64_t ts0 = t0 + (int64_t)sf * CC_SUB;                // t of the sub-block's first tick
@@ -495,7 +468,7 @@ __global__ __launch_bounds__(64 * CC_WALK_WAVES, 2) void k_cc_walk(const int64_t
                 }
                 if (lane < dead) mask = 0;
                 const unsigned long long eb = __builtin_amdgcn_ballot_w64(mask != 0);
-                if (eb == 0) { sp = cc_bcast(ap, 63); sn = cc_bcast(an, 63); break; }
+                if (eb == 0) { sp = cs_lane(ap, 63); sn = cs_lane(an, 63); break; }
                 // (2b) the first such tick: the states there (wave-uniform trip count: no predicates)
                 const int fl = __builtin_ctzll(eb);
                 const int q0 = __builtin_ctz((unsigned)__builtin_amdgcn_readlane((int)mask, fl));
@@ -514,7 +487,7 @@ __global__ __launch_bounds__(64 * CC_WALK_WAVES, 2) void k_cc_walk(const int64_t
                     // (cc_replay), and `if s_pos >= lam ... elif s_neg <= -lam` is evaluated as written.  Tapes whose
                     // log-prices sit on a lattice meet round floors EXACTLY (the synthetic one: s = 2.0000000000054e-05
                     // against a floor of 2e-5, again and again); on others this is a once-in-1e11 event.
-                    const double lam_e = cc_bcast(lamq, fl);
+                    const double lam_e = cs_lane(lamq, fl);
                     const int64_t te = ts0 + j;
                     kind = 0;
                     if (do_p) {
@@ -537,8 +510,8 @@ __global__ __launch_bounds__(64 * CC_WALK_WAVES, 2) void k_cc_walk(const int64_t
                     }
                     ++n_out; ++visits;                                    // an event costs about as much as opening a sub-block
                 }
-                sp = kind == 1 ? 0.0 : cc_bcast(bp, fl);                  // states after that tick, the closing side reset
-                sn = kind == 2 ? 0.0 : cc_bcast(bn, fl);
+                sp = kind == 1 ? 0.0 : cs_lane(bp, fl);                  // states after that tick, the closing side reset
+                sn = kind == 2 ? 0.0 : cs_lane(bn, fl);
                 if (kind == 1) { reset_p = ts0 + j + 1; mag_p = 2.0 * U_s; }            // (first tick after the reset)
                 else if (kind == 2) { reset_n = ts0 + j + 1; mag_n = 2.0 * U_s; }
                 mag_p = fmax(mag_p, fabs(sp)); mag_n = fmax(mag_n, fabs(sn));

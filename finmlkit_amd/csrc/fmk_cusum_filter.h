@@ -1,6 +1,8 @@
 // fmk_cusum_filter.h -- the symmetric CUSUM event filter (finmlkit/sampling/filters.py:7-70) on gfx950.
-// Included by fmk_cusum.hip after fmk_cusum_onepass.h: CsState, cs_lane, cs_same, the CS1_* geometry, Cs1Fix and the counts / emit
-// kernels of the one-pass bar indexer are used as they are; the bar indexer's walking kernels are not touched.
+// Included by fmk_cusum.hip after fmk_cusum_onepass.h.  The rule below is cf_tick of fmk_cusum_rule.h (CsState, cs_same and cs_lane
+// live there too).  From fmk_cusum_onepass.h come the CS1_* geometry, the fix-up's lockstep walk (cs1_fix_body: k_cf_fix is that body
+// on the source CfSrc), Cs1Fix, the scratch layout Cs1Work, the counts / emit kernels and their host tail cs1_emit_all.  Pass A and the
+// re-walk are this file's own: sharing the walker's tile with k_cs1_pass reorders that kernel's listing.
 //
 // The rule, for i = 1 .. n-1 (tick i sits at offset t = i - 1 of the chunked stream, m = n - 1 ticks):
 //     ret   = log(x[i] / x[i-1])                     (fmk_log_ratio: the host's log of the rounded quotient)
@@ -18,7 +20,7 @@
 //                                     row, entry state E, exit state S0.  PER = false (constant threshold): x only, 8 B/tick, no
 //                                     threshold tile in LDS; PER = true: x and thr, 16 B/tick.
 //   fix-up  (k_cf_fix<PER>)         : a wave per chunk whose true entry state is not the one its record was made from: lane 0 walks from
-//                                     the true state, lane 1 from E, and they merge on bitwise-equal states (k_cs1_fix's lockstep).
+//                                     the true state, lane 1 from E, and they merge on bitwise-equal states (cs1_fix_body).
 //   re-walk (k_cf_pass<PER, true>)  : the loop of pass A without the warm-up, a LANE per chunk, from the exit state of the chunk before:
 //                                     the staging row, E and S0 are made anew from that entry state.  For tapes that do not forget
 //                                     within a chunk (wide thresholds), where a wave per chunk would walk every chunk over its whole
@@ -29,19 +31,6 @@
 #pragma once
 
 #define CF_MAX_FIX_LAUNCHES 24     // fix-up launches after which the default schedule goes over to the re-walk
-
-// one tick of the rule as selects -> 1 if tick is an event
-__device__ __forceinline__ unsigned cf_tick(double &sp, double &sn, double r, double l)
-{
-    const double a = sp + r, b = sn + r;
-    sp = a > 0.0 ? a : 0.0;                                              // max(0.0, s_pos + ret): NaN -> 0.0
-    sn = b < 0.0 ? b : 0.0;                                              // min(0.0, s_neg + ret)
-    const bool cn = sn < -l;                                             // the negative side first, strict
-    const bool cp = !cn && sp > l;
-    sn = cn ? 0.0 : sn;
-    sp = cp ? 0.0 : sp;
-    return (cn | cp) ? 1u : 0u;
-}
 
 // PER: one threshold per element (thr[i]); otherwise the constant thr[0].
 // REWALK = false: pass A.  Every chunk is walked from (0, 0), CS1_W ticks in front of it -> E, S0, C0, staged.
@@ -167,11 +156,30 @@ __global__ __launch_bounds__(256) void k_cf_pass(const double *__restrict__ x, c
     }
 }
 
-// One wave per chunk k >= 1, as k_cs1_fix: lane 0 walks from the true entry state S_read[k - 1], lane 1 from E[k] (the state the
-// chunk's staging row was made from), in lockstep over the same LDS rows; ret / thr are recomputed from the raw columns by the
-// expressions of k_cf_pass, so lane 1 IS that walk.  They are compared every 8 ticks; at the first boundary with equal states the
-// chunk is settled (lane 0's closes up to there in the patch row, the staging row's from there on, exit state S0[k]).  A chunk that
-// does not merge gets lane 0's exit state.  `limit`: ticks the walk may take before it gives the chunk up for this launch.
+// the filter's ticks for cs1_fix_body: tick t of the stream is element 1 + t of x (and of thr when there is one per element)
+template <bool PER>
+struct CfSrc {
+    const double *__restrict__ x, *__restrict__ thr;
+    int64_t n;
+    double lam;                                                          // the constant threshold, read once
+    __device__ __forceinline__ CfSrc(const double *x_, const double *thr_, int64_t n_) : x(x_), thr(thr_), n(n_), lam(PER ? 0.0 : thr_[0]) {}
+    struct Raw { double p, pm, th; };
+    static __device__ __forceinline__ Raw idle() { return Raw{1.0, 1.0, NAN}; }
+    __device__ __forceinline__ Raw load(int64_t t) const
+    {
+        int64_t i = 1 + t;
+        if (i > n - 1) i = n - 1;                                        // lanes past the chunk: any valid address
+        return Raw{x[i], x[i - 1], PER ? thr[i] : lam};
+    }
+    __device__ __forceinline__ void eval(const Raw &c, int64_t, double &r, double &l) const
+    {
+        r = fmk_log_ratio(c.p, c.pm);                                    // the expressions of k_cf_pass
+        l = c.th;
+    }
+    static __device__ __forceinline__ unsigned tick(double &sp, double &sn, double r, double l) { return cf_tick(sp, sn, r, l); }
+};
+
+// One wave per chunk k >= 1 whose true entry state S_read[k - 1] is not the one its staging row was made from (cs1_fix_body)
 template <bool PER>
 __global__ __launch_bounds__(256) void k_cf_fix(const double *__restrict__ x, const double *__restrict__ thr, int64_t n, int64_t m,
                                                 int64_t chunks, const CsState *__restrict__ E, const CsState *__restrict__ S0,
@@ -180,92 +188,7 @@ __global__ __launch_bounds__(256) void k_cf_fix(const double *__restrict__ x, co
                                                 unsigned short *__restrict__ patch, int limit, unsigned long long *changed,
                                                 unsigned long long *pending)
 {
-    __shared__ double s_r[4][64], s_l[4][64];
-    const int lane = fmk_lane();
-    const int wib = (int)(threadIdx.x >> 6);
-    const int64_t k = (int64_t)blockIdx.x * 4 + wib + 1;
-    if (k >= chunks) return;
-    const double lam = PER ? 0.0 : thr[0];
-    CsState in = S_read[k - 1];
-    in.sp = cs_lane(in.sp, 0); in.sn = cs_lane(in.sn, 0);               // one copy for the whole wave
-    {
-        CsState li = last_in[k];
-        li.sp = cs_lane(li.sp, 0); li.sn = cs_lane(li.sn, 0);
-        if (cs_same(li, in)) return;                                     // the record was made from exactly this entry state
-    }
-    CsState e = E[k];
-    e.sp = cs_lane(e.sp, 0); e.sn = cs_lane(e.sn, 0);
-    double sp = lane == 0 ? in.sp : e.sp, sn = lane == 0 ? in.sn : e.sn;
-    int cnt = 0;
-    const int64_t t0 = k * CS1_L;
-    const int len = (int)(m - t0 < CS1_L ? m - t0 : CS1_L);
-    unsigned short *my = patch + k * (int64_t)CS1_L;
-    bool merged = false, gave_up = false;
-    // raw inputs one group of 64 ticks ahead
-    double c_p, c_pm, c_th;
-    auto fetch = [&](int j0, double &p, double &pm, double &th) {
-        int64_t i = 1 + t0 + j0 + lane;
-        if (i > n - 1) i = n - 1;                                        // lanes past the chunk: any valid address
-        p = x[i]; pm = x[i - 1];
-        th = PER ? thr[i] : lam;
-    };
-    fetch(0, c_p, c_pm, c_th);
-    int j0 = 0;
-    for (; j0 < len; j0 += 64) {
-        if (j0 >= limit) { gave_up = true; break; }
-        double n_p = 1.0, n_pm = 1.0, n_th = NAN;
-        if (j0 + 64 < len) fetch(j0 + 64, n_p, n_pm, n_th);
-        {
-            const int jj = j0 + lane;
-            double r = 0.0, l = NAN;                                     // past the chunk's end: ticks that change nothing
-            if (jj < len) {
-                r = fmk_log_ratio(c_p, c_pm);
-                l = c_th;
-            }
-            s_r[wib][lane] = r;
-            s_l[wib][lane] = l;
-            c_p = n_p; c_pm = n_pm; c_th = n_th;
-        }
-        __builtin_amdgcn_wave_barrier();
-        const int lim = len - j0 < 64 ? len - j0 : 64;
-        int q8 = 0;
-        for (; q8 < lim; q8 += 8) {
-            double r8[8], l8[8];
-#pragma unroll
-            for (int q = 0; q < 8; ++q) { r8[q] = s_r[wib][q8 + q]; l8[q] = s_l[wib][q8 + q]; }
-            unsigned m8 = 0;
-#pragma unroll
-            for (int q = 0; q < 8; ++q) m8 |= cf_tick(sp, sn, r8[q], l8[q]) << q;
-            if (lane == 0) {
-                int at = cnt;
-                for (unsigned mm = m8; mm; mm &= mm - 1) my[at++] = (unsigned short)(j0 + q8 + __builtin_ctz(mm));
-            }
-            cnt += __builtin_popcount(m8);
-            const double tp = cs_lane(sp, 0), tn = cs_lane(sn, 0), ap = cs_lane(sp, 1), an = cs_lane(sn, 1);
-            if (__double_as_longlong(tp) == __double_as_longlong(ap) && __double_as_longlong(tn) == __double_as_longlong(an)) {
-                merged = true;
-                break;
-            }
-        }
-        __builtin_amdgcn_wave_barrier();
-        if (merged) break;
-    }
-    if (gave_up) {                                                       // not settled in this launch: the record stays as it was
-        if (lane == 0) atomicAdd(pending, 1ULL);
-        return;
-    }
-    const int cnt_t = __builtin_amdgcn_readlane(cnt, 0), cnt_a = __builtin_amdgcn_readlane(cnt, 1);
-    CsState out;
-    if (merged) out = S0[k];                                             // from the merge on the walk is the staging row's
-    else { out.sp = cs_lane(sp, 0); out.sn = cs_lane(sn, 0); }           // lane 0 reached the end of the chunk on its own
-    out.sp = cs_lane(out.sp, 0); out.sn = cs_lane(out.sn, 0);
-    if (lane == 0) {
-        fix[k].pfx_a = cnt_a; fix[k].pfx_t = cnt_t;                      // (no merge: lane 1 walked the whole chunk, cnt_a == C0[k])
-        last_in[k] = in;
-        const CsState was = S_read[k];
-        S[k] = out;
-        if (!cs_same(was, out)) atomicAdd(changed, 1ULL);
-    }
+    cs1_fix_body(CfSrc<PER>(x, thr, n), m, chunks, E, S0, S_read, S, last_in, fix, patch, limit, changed, pending);
 }
 
 static int64_t g_cf_last[4];            // last call: form that answered (0 one pass + fix-up, 1 re-walk), launches, pending after the first, chunks
@@ -291,43 +214,26 @@ static int cf_run(fmk_ctx *ctx, const double *d_x, int64_t n, const double *d_th
         else if (!strcmp(v, "fixed")) force = 2;
         else if (*v) return fmk_set_error(ctx, FMK_E_ARG, "FMK_CUSUM_FILTER_FORM must be onepass or fixed");
     }
-    // ---- scratch layout: [scan tile sums | states S, S_read, last_in, S0, E | counts | C0 | fix | staging rows | patch rows]
-    const size_t scan_bytes = (((size_t)fmk_ceil_div(chunks + 1, FMK_SCAN_TILE) + 1) * 8 + 255) & ~(size_t)255;
-    const size_t st_bytes = ((size_t)chunks * sizeof(CsState) + 255) & ~(size_t)255;
-    const size_t cnt_bytes = ((size_t)(chunks + 1) * 8 + 255) & ~(size_t)255;
-    const size_t c0_bytes = ((size_t)chunks * 4 + 255) & ~(size_t)255;
-    const size_t fix_bytes = ((size_t)chunks * sizeof(Cs1Fix) + 255) & ~(size_t)255;
-    const size_t row_bytes = ((size_t)chunks * CS1_L * 2 + 255) & ~(size_t)255;
-    void *scr;
-    FMK_TRY(fmk_scratch(ctx, scan_bytes + 5 * st_bytes + cnt_bytes + c0_bytes + fix_bytes + 2 * row_bytes, &scr));
-    char *base = (char *)scr + scan_bytes;
-    CsState *S = (CsState *)base, *S_read = (CsState *)(base + st_bytes), *last_in = (CsState *)(base + 2 * st_bytes);
-    CsState *S0 = (CsState *)(base + 3 * st_bytes), *E = (CsState *)(base + 4 * st_bytes);
-    int64_t *counts = (int64_t *)(base + 5 * st_bytes);
-    int *C0 = (int *)(base + 5 * st_bytes + cnt_bytes);
-    Cs1Fix *fix = (Cs1Fix *)(base + 5 * st_bytes + cnt_bytes + c0_bytes);
-    unsigned short *staged = (unsigned short *)(base + 5 * st_bytes + cnt_bytes + c0_bytes + fix_bytes);
-    unsigned short *patch = (unsigned short *)(base + 5 * st_bytes + cnt_bytes + c0_bytes + fix_bytes + row_bytes);
-    fmk_mail::Cusum::Round *d_round = &ctx->d_mail->cusum.round, r;
-    FMK_HIP(ctx, hipMemsetAsync(fix, 0, fix_bytes, ctx->stream));
+    Cs1Work w;
+    FMK_TRY(cs1_work(ctx, chunks, &w));
+    fmk_mail::Cusum::Round *d_round = w.d_round, r;
     const unsigned pass_grid = (unsigned)fmk_ceil_div(chunks, (int64_t)CS1_TK);
-    k_cf_pass<PER, false><<<pass_grid, 256, 0, ctx->stream>>>(d_x, d_thr, n, m, chunks, E, S0, C0, staged, nullptr, nullptr, nullptr,
-                                                            nullptr, nullptr);
+    k_cf_pass<PER, false><<<pass_grid, 256, 0, ctx->stream>>>(d_x, d_thr, n, m, chunks, w.E, w.S0, w.C0, w.staged, nullptr, nullptr,
+                                                            nullptr, nullptr, nullptr);
     FMK_LAUNCH_CHECK(ctx);
-    FMK_HIP(ctx, hipMemcpyAsync(S, S0, (size_t)chunks * sizeof(CsState), hipMemcpyDeviceToDevice, ctx->stream));
-    FMK_HIP(ctx, hipMemcpyAsync(last_in, E, (size_t)chunks * sizeof(CsState), hipMemcpyDeviceToDevice, ctx->stream));   // every record was made from E
+    FMK_TRY(cs1_after_pass(ctx, w));
     int64_t rounds = 1, launches = 0;
     int limit = CS1_FIRST_LIMIT;
     bool rewalk = force == 2;
     while (chunks > 1) {
-        FMK_HIP(ctx, hipMemcpyAsync(S_read, S, (size_t)chunks * sizeof(CsState), hipMemcpyDeviceToDevice, ctx->stream));
+        FMK_TRY(cs1_round_begin(ctx, w));
         FMK_HIP(ctx, hipMemsetAsync(d_round, 0, sizeof *d_round, ctx->stream));
         if (rewalk)
-            k_cf_pass<PER, true><<<pass_grid, 256, 0, ctx->stream>>>(d_x, d_thr, n, m, chunks, E, S0, C0, staged, S_read, S, last_in,
-                                                                   fix, &d_round->changed);
+            k_cf_pass<PER, true><<<pass_grid, 256, 0, ctx->stream>>>(d_x, d_thr, n, m, chunks, w.E, w.S0, w.C0, w.staged, w.S_read, w.S,
+                                                                   w.last_in, w.fix, &d_round->changed);
         else
             k_cf_fix<PER><<<(unsigned)fmk_ceil_div(chunks - 1, (int64_t)4), 256, 0, ctx->stream>>>(
-                d_x, d_thr, n, m, chunks, E, S0, S_read, S, last_in, fix, patch, limit, &d_round->changed, &d_round->pending);
+                d_x, d_thr, n, m, chunks, w.E, w.S0, w.S_read, w.S, w.last_in, w.fix, w.patch, limit, &d_round->changed, &d_round->pending);
         FMK_LAUNCH_CHECK(ctx);
         ++launches; ++rounds;
         FMK_TRY(fmk_read_back(ctx, &r, d_round, sizeof r));
@@ -341,22 +247,14 @@ static int cf_run(fmk_ctx *ctx, const double *d_x, int64_t n, const double *d_th
         if (!rewalk && force != 1 && ((launches == 1 && pending > chunks / 4 + 1) || launches >= CF_MAX_FIX_LAUNCHES)) rewalk = true;
     }
     g_cf_last[0] = rewalk ? 1 : 0;
-    k_cs1_counts<<<(unsigned)fmk_ceil_div(chunks, (int64_t)256), 256, 0, ctx->stream>>>(C0, fix, chunks, counts);
-    FMK_LAUNCH_CHECK(ctx);
-    FMK_TRY(fmk_exclusive_scan_i64(ctx, counts, counts, chunks, true));
-    int64_t total = 0;
-    FMK_TRY(fmk_read_back(ctx, &total, counts + chunks, 8));
-    if (n_out) *n_out = total;
-    if (n_rounds) *n_rounds = rounds;
-    if (d_out) {
-        if (capacity < total)
-            return fmk_set_error(ctx, FMK_E_CAPACITY, "cusum_filter: %lld event indices, capacity %lld", (long long)total,
-                                 (long long)capacity);
-        // tick t of chunk k is element 1 + k * CS1_L + t of the series (k_cs1_emit's `first` = 0)
-        k_cs1_emit<<<(unsigned)fmk_ceil_div(chunks, (int64_t)4), 256, 0, ctx->stream>>>(C0, fix, staged, patch, chunks, 0, counts, d_out);
-        FMK_LAUNCH_CHECK(ctx);
+    // tick t of chunk k is element 1 + k * CS1_L + t of the series (k_cs1_emit's `first` = 0); no opening entry
+    int64_t total = -1;
+    const int rc = cs1_emit_all(ctx, w, chunks, 0, d_out, 0, capacity, "cusum_filter: %lld event indices, capacity %lld", &total);
+    if (total >= 0) {                                                    // the count was read: also reported with "capacity" (the caller asks again)
+        if (n_out) *n_out = total;
+        if (n_rounds) *n_rounds = rounds;
     }
-    return FMK_OK;
+    return rc;
 }
 
 extern "C" int fmk_cusum_filter_dev(fmk_ctx *ctx, const double *d_x, int64_t n, const double *d_thr, int64_t n_thr, int64_t *d_out,

@@ -1,5 +1,7 @@
 // fmk_cusum_onepass.h -- the dense regime of _cusum_bar_indexer (finmlkit/bar/logic.py:152-221) in ONE pass over the columns.
-// Included by fmk_cusum.hip (CsState, cs_lane, CS_* and the expressions of k_cusum_prep live there).
+// Included by fmk_cusum.hip.  CsState, cs_same, cs_lane, the tick rule cs_tick and the loop inputs cs_input: fmk_cusum_rule.h.
+// The fix-up's lockstep walk (cs1_fix_body), the scratch layout (Cs1Work) and the counts -> scan -> emit tail (cs1_emit_all) are
+// shared with the event filter of fmk_cusum_filter.h, which supplies its own columns and its own tick rule.
 //
 // The fixed point of fmk_cusum.hip stores the loop inputs chunk-transposed (16 B/tick written, then read by every round and once more
 // by the pass that writes the closes): 88 GB for a 24 B/tick input at 1e9 ticks, 18.6 ms.  What makes that fixed point converge in two
@@ -37,22 +39,8 @@
 #define CS1_FIRST_LIMIT 512        // ticks a chunk may take to merge in the first fix-up launch
 #define CS1_PREFETCH 0             // 1: the next tile's loads are issued before the walk (measured: 7.2 against 6.8 ms -- 173 VGPRs, a spill at three waves)
 
-// ret / lam of tick i = first + 1 + t (the expressions of k_cusum_prep, operation for operation)
-__device__ __forceinline__ void cs1_inputs(const int64_t *__restrict__ ts, const double *__restrict__ price,
-                                           const double *__restrict__ sigma, int64_t n, int64_t i, double sigma_floor,
-                                           double sigma_mult, double &r, double &lam, bool &nan_sigma)
-{
-    r = fmk_log_ratio(price[i], price[i - 1]);
-    const bool block = i + 1 < n && ts[i] == ts[i + 1];
-    const double sg = sigma[i];
-    nan_sigma |= sg != sg;
-    lam = NAN;
-    if (!block) {
-        lam = sigma_mult * sg;
-        lam = sigma_floor > lam ? sigma_floor : lam;                     // max(lam, floor): a NaN lam stays NaN
-    }
-}
-
+// (k_cs1_pass keeps cs_input and cs_tick written out: called as functions they give the same values from a reordered tile block --
+//  2510 instead of 2538 instructions -- and this is the kernel whose time is on record; profiles/cusum_refactor_isa.txt.)
 __global__ __launch_bounds__(256) void k_cs1_pass(const int64_t *__restrict__ ts, const double *__restrict__ price,
                                                   const double *__restrict__ sigma, int64_t n, int64_t first, int64_t m,
                                                   int64_t chunks, double sigma_floor, double sigma_mult,
@@ -111,7 +99,7 @@ __global__ __launch_bounds__(256) void k_cs1_pass(const int64_t *__restrict__ ts
             const double pm = col == 0 ? __longlong_as_double((long long)halo[rr]) : up;
             const int64_t tsn = col == CS1_TJ - 1 ? (int64_t)halo[rr] : dn;
             double r = 0.0, lam = NAN;                                   // outside the stream: a tick that changes nothing
-            if ((okm >> rr) & 1u) {                                      // the expressions of k_cusum_prep, operation for operation
+            if ((okm >> rr) & 1u) {                                      // cs_input, written out, operation for operation
                 const int64_t i = first + 1 + (k0 + row) * CS1_L + j0 + col;
                 r = fmk_log_ratio(p[rr], pm);
                 const bool block = i + 1 < n && tsi[rr] == tsn;
@@ -138,7 +126,7 @@ __global__ __launch_bounds__(256) void k_cs1_pass(const int64_t *__restrict__ ts
 #pragma unroll
                 for (int q = 0; q < 8; ++q) { r8[q] = s_r[threadIdx.x][j8 + q]; l8[q] = s_l[threadIdx.x][j8 + q]; }
 #pragma unroll
-                for (int q = 0; q < 8; ++q) {
+                for (int q = 0; q < 8; ++q) {                            // cs_tick, written out (see the note above k_cs1_pass)
                     const double a = sp + r8[q], b = sn + r8[q];
                     sp = a > 0.0 ? a : 0.0;                              // max(0.0, s_pos + ret): NaN -> 0.0
                     sn = b < 0.0 ? b : 0.0;                              // min(0.0, s_neg + ret)
@@ -168,18 +156,22 @@ __global__ __launch_bounds__(256) void k_cs1_pass(const int64_t *__restrict__ ts
 // per-chunk record of the fix-up: how many of pass A's closes lie before the merge, how many closes the true walk has there
 struct Cs1Fix { int pfx_a, pfx_t; };
 
-// One wave per chunk k >= 1.  S_read: the exit states as they were before this launch (entry state of k = S_read[k - 1]);
-// S: the exit states this launch writes; last_in[k]: the entry state chunk k's record was made from (E[k] after pass A).
+// The fix-up of one chunk by one wave, for both users of the scheme.  Chunk k >= 1; S_read: the exit states as they were before this
+// launch (entry state of k = S_read[k - 1]); S: the exit states this launch writes; last_in[k]: the entry state chunk k's record was
+// made from (E[k] after pass A).
 //   limit   : ticks the walk may take before it gives the chunk up for this launch (`pending` counts those)
 //   changed : chunks whose exit state differs from S_read[k]
-__global__ __launch_bounds__(256) void k_cs1_fix(const int64_t *__restrict__ ts, const double *__restrict__ price,
-                                                 const double *__restrict__ sigma, int64_t n, int64_t first, int64_t m,
-                                                 int64_t chunks, double sigma_floor, double sigma_mult,
-                                                 const CsState *__restrict__ E, const CsState *__restrict__ S0,
-                                                 const CsState *__restrict__ S_read,
-                                                 CsState *__restrict__ S, CsState *__restrict__ last_in,
-                                                 Cs1Fix *__restrict__ fix, unsigned short *__restrict__ patch, int limit,
-                                                 unsigned long long *changed, unsigned long long *pending)
+// Src is where the ticks come from and what a tick does:
+//   Raw            : one lane's loads for one tick;  idle(): the value for a group that is not fetched
+//   load(t)        : the raw columns of tick t of the chunked stream (lanes past the stream's end read its last tick)
+//   eval(raw, t, r, lam) : return and threshold of that tick, by the expressions of pass A => the same bits => lane 1 IS pass A's walk
+//   tick(sp, sn, r, lam) : the rule -> 1 if the tick closes
+template <class Src>
+__device__ __forceinline__ void cs1_fix_body(const Src &src, int64_t m, int64_t chunks, const CsState *__restrict__ E,
+                                             const CsState *__restrict__ S0, const CsState *__restrict__ S_read,
+                                             CsState *__restrict__ S, CsState *__restrict__ last_in, Cs1Fix *__restrict__ fix,
+                                             unsigned short *__restrict__ patch, int limit, unsigned long long *changed,
+                                             unsigned long long *pending)
 {
     __shared__ double s_r[4][64], s_l[4][64];
     const int lane = fmk_lane();
@@ -203,35 +195,19 @@ __global__ __launch_bounds__(256) void k_cs1_fix(const int64_t *__restrict__ ts,
     const int len = (int)(m - t0 < CS1_L ? m - t0 : CS1_L);
     unsigned short *my = patch + k * (int64_t)CS1_L;
     bool merged = false, gave_up = false;
-    // raw inputs one group of 64 ticks ahead
-    double c_p, c_pm, c_sg; int64_t c_ts, c_tsn;
-    auto fetch = [&](int j0, double &p, double &pm, double &sg, int64_t &tsi, int64_t &tsn) {
-        int64_t i = first + 1 + t0 + j0 + lane;
-        if (i > n - 1) i = n - 1;                                        // lanes past the chunk: any valid address
-        p = price[i]; pm = price[i - 1]; sg = sigma[i]; tsi = ts[i];
-        tsn = ts[i + 1 < n ? i + 1 : i];
-    };
-    fetch(0, c_p, c_pm, c_sg, c_ts, c_tsn);
+    typename Src::Raw cur = src.load(t0 + lane);                         // raw inputs one group of 64 ticks ahead
     int j0 = 0;
     for (; j0 < len; j0 += 64) {
         if (j0 >= limit) { gave_up = true; break; }
-        double n_p = 1.0, n_pm = 1.0, n_sg = 0.0; int64_t n_ts = 0, n_tsn = 1;
-        if (j0 + 64 < len) fetch(j0 + 64, n_p, n_pm, n_sg, n_ts, n_tsn);
+        typename Src::Raw nxt = Src::idle();
+        if (j0 + 64 < len) nxt = src.load(t0 + j0 + 64 + lane);
         {
             const int jj = j0 + lane;
-            double r = 0.0, lam = NAN;
-            if (jj < len) {                                              // the expressions of k_cusum_prep / cs1_inputs
-                const int64_t i = first + 1 + t0 + jj;
-                r = fmk_log_ratio(c_p, c_pm);
-                const bool block = i + 1 < n && c_ts == c_tsn;
-                if (!block) {
-                    lam = sigma_mult * c_sg;
-                    lam = sigma_floor > lam ? sigma_floor : lam;
-                }
-            }
+            double r = 0.0, lam = NAN;                                   // past the chunk's end: ticks that change nothing
+            if (jj < len) src.eval(cur, t0 + jj, r, lam);
             s_r[wib][lane] = r;
             s_l[wib][lane] = lam;
-            c_p = n_p; c_pm = n_pm; c_sg = n_sg; c_ts = n_ts; c_tsn = n_tsn;
+            cur = nxt;
         }
         __builtin_amdgcn_wave_barrier();
         const int lim = len - j0 < 64 ? len - j0 : 64;
@@ -244,16 +220,7 @@ __global__ __launch_bounds__(256) void k_cs1_fix(const int64_t *__restrict__ ts,
             for (int q = 0; q < 8; ++q) { r8[q] = s_r[wib][q8 + q]; l8[q] = s_l[wib][q8 + q]; }
             unsigned m8 = 0;
 #pragma unroll
-            for (int q = 0; q < 8; ++q) {                                // the loop of k_cusum_chunks, as selects
-                const double a = sp + r8[q], b = sn + r8[q];
-                sp = a > 0.0 ? a : 0.0;
-                sn = b < 0.0 ? b : 0.0;
-                const bool cp = sp >= l8[q];
-                const bool cn = !cp && sn <= -l8[q];
-                m8 |= ((cp | cn) ? 1u : 0u) << q;
-                sp = cp ? 0.0 : sp;
-                sn = cn ? 0.0 : sn;
-            }
+            for (int q = 0; q < 8; ++q) m8 |= Src::tick(sp, sn, r8[q], l8[q]) << q;
             if (lane == 0) {
                 int at = cnt;
                 for (unsigned mm = m8; mm; mm &= mm - 1) my[at++] = (unsigned short)(j0 + q8 + __builtin_ctz(mm));
@@ -286,6 +253,40 @@ __global__ __launch_bounds__(256) void k_cs1_fix(const int64_t *__restrict__ ts,
     }
 }
 
+// the bar indexer's ticks: tick t of the stream is element first + 1 + t of ts / price / sigma
+struct Cs1BarSrc {
+    const int64_t *__restrict__ ts;
+    const double *__restrict__ price, *__restrict__ sigma;
+    int64_t n, first;
+    double sigma_floor, sigma_mult;
+    struct Raw { double p, pm, sg; int64_t ts, tsn; };
+    static __device__ __forceinline__ Raw idle() { return Raw{1.0, 1.0, 0.0, 0, 1}; }
+    __device__ __forceinline__ Raw load(int64_t t) const
+    {
+        int64_t i = first + 1 + t;
+        if (i > n - 1) i = n - 1;                                        // lanes past the chunk: any valid address
+        return Raw{price[i], price[i - 1], sigma[i], ts[i], ts[i + 1 < n ? i + 1 : i]};
+    }
+    __device__ __forceinline__ void eval(const Raw &c, int64_t t, double &r, double &lam) const
+    {
+        cs_input(c.p, c.pm, c.sg, c.ts, c.tsn, first + 1 + t + 1 < n, sigma_floor, sigma_mult, r, lam);
+    }
+    static __device__ __forceinline__ unsigned tick(double &sp, double &sn, double r, double lam) { return cs_tick(sp, sn, r, lam); }
+};
+
+__global__ __launch_bounds__(256) void k_cs1_fix(const int64_t *__restrict__ ts, const double *__restrict__ price,
+                                                 const double *__restrict__ sigma, int64_t n, int64_t first, int64_t m,
+                                                 int64_t chunks, double sigma_floor, double sigma_mult,
+                                                 const CsState *__restrict__ E, const CsState *__restrict__ S0,
+                                                 const CsState *__restrict__ S_read,
+                                                 CsState *__restrict__ S, CsState *__restrict__ last_in,
+                                                 Cs1Fix *__restrict__ fix, unsigned short *__restrict__ patch, int limit,
+                                                 unsigned long long *changed, unsigned long long *pending)
+{
+    cs1_fix_body(Cs1BarSrc{ts, price, sigma, n, first, sigma_floor, sigma_mult}, m, chunks, E, S0, S_read, S, last_in, fix, patch, limit,
+                 changed, pending);
+}
+
 __global__ __launch_bounds__(256) void k_cs1_counts(const int *__restrict__ C0, const Cs1Fix *__restrict__ fix, int64_t chunks,
                                                     int64_t *__restrict__ counts)
 {
@@ -309,4 +310,72 @@ __global__ __launch_bounds__(256) void k_cs1_emit(const int *__restrict__ C0, co
     const unsigned short *pp = patch + k * (int64_t)CS1_L, *ss = staged + k * (int64_t)CS1_L;
     for (int e = lane; e < pt; e += 64) dst[e] = base + pp[e];
     for (int e = lane; e < c0 - pa; e += 64) dst[pt + e] = base + ss[pa + e];
+}
+
+// ---- host side, for both users: the scratch of a call and what follows the fix-up
+struct Cs1Work {
+    CsState *S, *S_read, *last_in, *S0, *E;      // exit states (written / as read by a launch), entry state of each record, pass A's exit and entry states
+    int64_t *counts;                             // chunks + 1: closes per chunk, then their exclusive scan and the total
+    int *C0;                                     // closes pass A staged per chunk
+    Cs1Fix *fix;
+    unsigned short *staged, *patch;              // CS1_L slots per chunk each
+    fmk_mail::Cusum::Round *d_round;
+    size_t st_copy;                              // bytes of one state array
+};
+
+// [scan tile sums | states S, S_read, last_in, S0, E | counts | C0 | fix (zeroed) | staging rows | patch rows]
+static int cs1_work(fmk_ctx *ctx, int64_t chunks, Cs1Work *w)
+{
+    auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
+    const size_t scan_bytes = up(((size_t)fmk_ceil_div(chunks + 1, FMK_SCAN_TILE) + 1) * 8);
+    const size_t st_bytes = up((size_t)chunks * sizeof(CsState)), cnt_bytes = up((size_t)(chunks + 1) * 8);
+    const size_t c0_bytes = up((size_t)chunks * 4), fix_bytes = up((size_t)chunks * sizeof(Cs1Fix));
+    const size_t row_bytes = up((size_t)chunks * CS1_L * 2);
+    void *scr;
+    FMK_TRY(fmk_scratch(ctx, scan_bytes + 5 * st_bytes + cnt_bytes + c0_bytes + fix_bytes + 2 * row_bytes, &scr));
+    char *at = (char *)scr + scan_bytes;
+    auto take = [&at](size_t b) { char *p = at; at += b; return p; };
+    w->S = (CsState *)take(st_bytes); w->S_read = (CsState *)take(st_bytes); w->last_in = (CsState *)take(st_bytes);
+    w->S0 = (CsState *)take(st_bytes); w->E = (CsState *)take(st_bytes);
+    w->counts = (int64_t *)take(cnt_bytes);
+    w->C0 = (int *)take(c0_bytes);
+    w->fix = (Cs1Fix *)take(fix_bytes);
+    w->staged = (unsigned short *)take(row_bytes); w->patch = (unsigned short *)take(row_bytes);
+    w->d_round = &ctx->d_mail->cusum.round;
+    w->st_copy = (size_t)chunks * sizeof(CsState);
+    FMK_HIP(ctx, hipMemsetAsync(w->fix, 0, fix_bytes, ctx->stream));
+    return FMK_OK;
+}
+
+// after pass A: its exit states are the first S, and every record was made from E
+static int cs1_after_pass(fmk_ctx *ctx, const Cs1Work &w)
+{
+    FMK_HIP(ctx, hipMemcpyAsync(w.S, w.S0, w.st_copy, hipMemcpyDeviceToDevice, ctx->stream));
+    FMK_HIP(ctx, hipMemcpyAsync(w.last_in, w.E, w.st_copy, hipMemcpyDeviceToDevice, ctx->stream));
+    return FMK_OK;
+}
+
+// top of a round: the launch reads entry states from a copy made before it
+static int cs1_round_begin(fmk_ctx *ctx, const Cs1Work &w)
+{
+    FMK_HIP(ctx, hipMemcpyAsync(w.S_read, w.S, w.st_copy, hipMemcpyDeviceToDevice, ctx->stream));
+    return FMK_OK;
+}
+
+// counts -> exclusive scan -> *total; with an output array: total + lead entries must fit, the closes go to d_out + lead as tick
+// indices first + 1 + t.  `what` is the caller's capacity message (two %lld: needed, capacity).
+static int cs1_emit_all(fmk_ctx *ctx, const Cs1Work &w, int64_t chunks, int64_t first, int64_t *d_out, int64_t lead, int64_t capacity,
+                        const char *what, int64_t *total)
+{
+    k_cs1_counts<<<(unsigned)fmk_ceil_div(chunks, (int64_t)256), 256, 0, ctx->stream>>>(w.C0, w.fix, chunks, w.counts);
+    FMK_LAUNCH_CHECK(ctx);
+    FMK_TRY(fmk_exclusive_scan_i64(ctx, w.counts, w.counts, chunks, true));
+    FMK_TRY(fmk_read_back(ctx, total, w.counts + chunks, 8));
+    if (d_out) {
+        if (capacity < *total + lead) return fmk_set_error(ctx, FMK_E_CAPACITY, what, (long long)(*total + lead), (long long)capacity);
+        k_cs1_emit<<<(unsigned)fmk_ceil_div(chunks, (int64_t)4), 256, 0, ctx->stream>>>(w.C0, w.fix, w.staged, w.patch, chunks, first,
+                                                                                      w.counts, d_out + lead);
+        FMK_LAUNCH_CHECK(ctx);
+    }
+    return FMK_OK;
 }

@@ -317,6 +317,40 @@ def test_cusum_onepass_vs_oracle(orc, monkeypatch, n, vol, floor, same_ts, sigma
     assert _onepass()[0] == 0
 
 
+@pytest.mark.parametrize("n,same_ts,quiet", [
+    (1 + 80 * 4096, 0.0, ((10, 14), (25, 27))),                   # strictly increasing timestamps: no print blocks
+    (1 + 80 * 4096, 0.25, ((10, 14), (25, 27))),                  # print blocks, also across chunk edges
+    (1 + 79 * 4096 + 13, 0.0, ((10, 14), (25, 27), (78, 80)))])   # the last chunk has 13 ticks (no multiple of 8) and is walked
+def test_cusum_onepass_fixup_is_walked(orc, monkeypatch, n, same_ts, quiet):
+    """The lockstep walk of the fix-up (k_cs1_fix), which the dense tapes above never enter: their warm-up reaches every chunk
+    with the true state.  A close per ~100 ticks (floor 2e-3, sigma = floor / 4, multiplier 2) with quiet stretches of whole
+    chunks in which sigma = 1.0 (threshold 2.0: never reached, only the clamps forget): the chunks in and right after a stretch
+    start from a state the 512-tick warm-up from (0, 0) does not reproduce, so they are walked -- some merge inside the first
+    launch, some are given up at its limit (pending_first >= 1) and walked over their whole length in the second, some never
+    merge and pass a new exit state on; their patch rows are not empty.  pending_first <= chunks // 4 + 1 is the form's own
+    condition for answering."""
+    from finmlkit_amd.bar.logic import _cusum_bar_indexer
+    monkeypatch.setenv("FMK_CUSUM_CHAIN", "0")
+    floor = 2e-3
+    ts, px = _stream(orc, n, 21, vol=2e-4, same_ts=same_ts)
+    if same_ts == 0.0:
+        ts = ts[0] + np.arange(n, dtype=np.int64) * 1_000_000
+    sigma = np.full(n, floor / 4)
+    for a, b in quiet:                                            # chunk k holds the ticks 1 + 4096 k .. 4096 (k + 1)
+        sigma[1 + a * 4096: 1 + b * 4096] = 1.0
+    want = orc._cusum_bar_indexer(ts, px, sigma.copy(), floor, 2.0)
+    got = _cusum_bar_indexer(ts, px, sigma.copy(), floor, 2.0)
+    used, launches, pending, chunks = _onepass()
+    print(f"n {n}, same_ts {same_ts}: {len(want) - 1} closes, used {used}, fix-up launches {launches}, pending after the first "
+          f"{pending}, chunks {chunks}")
+    np.testing.assert_array_equal(got, want)
+    assert chunks == 80
+    assert used == 1 and launches >= 2 and 1 <= pending <= chunks // 4 + 1, (used, launches, pending, chunks)
+    monkeypatch.setenv("FMK_CUSUM_ONEPASS", "0")
+    np.testing.assert_array_equal(_cusum_bar_indexer(ts, px, sigma.copy(), floor, 2.0), want)
+    assert _onepass()[0] == 0
+
+
 def test_cusum_onepass_leaves_a_tape_that_does_not_forget(orc, monkeypatch):
     """Thresholds that are never reached on a quiet tape: the clamps alone do not bring the walk from (0, 0) and the true
     walk together within the warm-up plus the first fix-up launch, so the form gives the call to the fixed point."""
