@@ -243,6 +243,15 @@ static inline int fmk_rule_pct_change(fmk_ctx *ctx, int64_t periods)
     return fmk_rule_least(ctx, periods, 0, "pct_change: periods must not be negative.");
 }
 static inline int fmk_rule_stoch_k(fmk_ctx *ctx, int64_t length) { return fmk_rule_least(ctx, length, 1, "stoch_k: length must be at least 1."); }
+// the recursive indicators (fmk_recur.hip); ewma's message is the reference's
+static inline int fmk_rule_ewma(fmk_ctx *ctx, double span)
+{
+    return span >= 1.0 ? FMK_OK
+                       : fmk_set_error(ctx, FMK_E_ARG, "span size is less than or equal to 1. Please provide a span size greater than 1.");
+}
+static inline int fmk_rule_rsi_wilder(fmk_ctx *ctx, int64_t window) { return fmk_rule_least(ctx, window, 1, "rsi_wilder: window must be at least 1."); }
+static inline int fmk_rule_atr(fmk_ctx *ctx, int64_t window) { return fmk_rule_least(ctx, window, 0, "atr: window must not be negative."); }
+static inline int fmk_rule_adx(fmk_ctx *ctx, int64_t length) { return fmk_rule_least(ctx, length, 1, "adx_core: length must be at least 1."); }
 
 // One excursion of a call onto the context's auxiliary stream (fmk_api.hip), the only way there.  Rules:
 //  - one fork per context at a time: fork() while another FmkSide of the context is open is an error;

@@ -70,6 +70,21 @@ int series_host(fmk_ctx *ctx, int rule, const double *x, int64_t n, double *out,
     return down(ctx, out, (const double *)d_o, n);
 }
 
+// high, low and close up, dev(d_high, d_low, d_close, d_out), one series down
+template <typename Dev>
+int hlc_host(fmk_ctx *ctx, int rule, const double *high, const double *low, const double *close, int64_t n, double *out, Dev dev)
+{
+    FMK_TRY(rule);
+    DevBag bag(ctx);
+    double *d_h, *d_l, *d_c, *d_o;
+    FMK_TRY(bag.up(high, n, &d_h));
+    FMK_TRY(bag.up(low, n, &d_l));
+    FMK_TRY(bag.up(close, n, &d_c));
+    FMK_TRY(bag.out(n, &d_o));
+    FMK_TRY(dev(d_h, d_l, d_c, d_o));
+    return down(ctx, out, (const double *)d_o, n);
+}
+
 }  // namespace
 
 extern "C" {
@@ -614,6 +629,44 @@ int fmk_stoch_k(fmk_ctx *ctx, const double *close, const double *low, const doub
     FMK_TRY(bag.out(n, &d_o));
     FMK_TRY(fmk_stoch_k_dev(ctx, d_c, d_l, d_h, n, length, d_o));
     return down(ctx, out, (const double *)d_o, n);
+}
+
+// the recursive indicators (fmk_recur.hip)
+int fmk_ewma(fmk_ctx *ctx, const double *y, int64_t n, double span, double *out)
+{
+    FMK_TRY(fmk_rule_ewma(ctx, span));
+    return series_host(ctx, fmk_series_check(ctx, "ewma", n), y, n, out,
+                       [=](const double *d_x, double *d_o) { return fmk_ewma_dev(ctx, d_x, n, span, d_o); });
+}
+
+int fmk_rsi_wilder(fmk_ctx *ctx, const double *close, int64_t n, int64_t window, double *out)
+{
+    FMK_TRY(fmk_rule_rsi_wilder(ctx, window));
+    return series_host(ctx, fmk_series_check(ctx, "rsi_wilder", n), close, n, out,
+                       [=](const double *d_x, double *d_o) { return fmk_rsi_wilder_dev(ctx, d_x, n, window, d_o); });
+}
+
+int fmk_true_range(fmk_ctx *ctx, const double *high, const double *low, const double *close, int64_t n, double *out)
+{
+    return hlc_host(ctx, fmk_series_check(ctx, "true_range", n), high, low, close, n, out,
+                    [=](const double *h, const double *l, const double *c, double *o) { return fmk_true_range_dev(ctx, h, l, c, n, o); });
+}
+
+int fmk_atr(fmk_ctx *ctx, const double *high, const double *low, const double *close, int64_t n, int64_t window, int ema_based,
+            int normalize, double *out)
+{
+    FMK_TRY(fmk_rule_atr(ctx, window));
+    return hlc_host(ctx, fmk_series_check(ctx, "atr", n), high, low, close, n, out,
+                    [=](const double *h, const double *l, const double *c, double *o) {
+                        return fmk_atr_dev(ctx, h, l, c, n, window, ema_based, normalize, o);
+                    });
+}
+
+int fmk_adx(fmk_ctx *ctx, const double *high, const double *low, const double *close, int64_t n, int64_t length, double *out)
+{
+    FMK_TRY(fmk_rule_adx(ctx, length));
+    return hlc_host(ctx, fmk_series_check(ctx, "adx_core", n), high, low, close, n, out,
+                    [=](const double *h, const double *l, const double *c, double *o) { return fmk_adx_dev(ctx, h, l, c, n, length, o); });
 }
 
 }  // extern "C"

@@ -440,6 +440,49 @@ class DeviceTrades:
             self.ctx.call("fmk_stoch_k_dev", close.p, low.p, high.p, c_i64(close.n), c_i64(int(length)), out.p)
         return out
 
+    # ------------------------------------------------------------------ recursive indicators (csrc/fmk_recur.hip)
+    def ewma(self, y: DeviceArray, span) -> DeviceArray:
+        """ewma (feature/core/ma.py:6-43) of a resident float64 series."""
+        if not float(span) >= 1.0:
+            raise ValueError("span size is less than or equal to 1. Please provide a span size greater than 1.")
+        self._f64("fmk_ewma_dev", y)
+        out = DeviceArray(self.ctx, y.n, np.float64)
+        if y.n:
+            self.ctx.call("fmk_ewma_dev", y.p, c_i64(y.n), c_f64(float(span)), out.p)
+        return out
+
+    def rsi_wilder(self, close: DeviceArray, window: int) -> DeviceArray:
+        """rsi_wilder (feature/core/momentum.py:25-65) of a resident float64 series."""
+        return self._series("fmk_rsi_wilder_dev", close, window, message="rsi_wilder: window must be at least 1.")
+
+    def _hlc(self, name: str, message: str, high: DeviceArray, low: DeviceArray, close: DeviceArray, *args) -> DeviceArray:
+        self._f64(name, high, low, close)
+        if not high.n == low.n == close.n:
+            raise ValueError(message)
+        out = DeviceArray(self.ctx, high.n, np.float64)
+        if high.n:
+            self.ctx.call(name, high.p, low.p, close.p, c_i64(high.n), *args, out.p)
+        return out
+
+    def true_range(self, high: DeviceArray, low: DeviceArray, close: DeviceArray) -> DeviceArray:
+        """true_range (feature/core/volatility.py:222-253) of three resident float64 series of one length."""
+        return self._hlc("fmk_true_range_dev", "The length of high, low, and close prices must be the same.", high, low, close)
+
+    def atr(self, high: DeviceArray, low: DeviceArray, close: DeviceArray, window: int, ema_based: bool = False,
+            normalize: bool = False) -> DeviceArray:
+        """atr (feature/core/volatility.py:352-437) of three resident float64 series of one length."""
+        if int(window) < 0:
+            raise ValueError("atr: window must not be negative.")
+        return self._hlc("fmk_atr_dev", "The length of high, low, and close prices must be the same.", high, low, close,
+                         c_i64(int(window)), C.c_int(bool(ema_based)), C.c_int(bool(normalize)))
+
+    def adx(self, high: DeviceArray, low: DeviceArray, close: DeviceArray, length: int = 14) -> DeviceArray:
+        """adx_core (feature/core/trend.py:8-96) of three resident float64 series of one length."""
+        if int(length) < 1:
+            raise ValueError("adx_core: length must be at least 1.")
+        return self._hlc("fmk_adx_dev", "adx_core: high, low and close must have the same length.", high, low, close,
+                         c_i64(int(length)))
+
     # ------------------------------------------------------------------ event sampling
     def cusum_filter(self, threshold, series: Optional[DeviceArray] = None) -> DeviceArray:
         """cusum_filter (sampling/filters.py:7-70) on a resident float64 series (default: the price column) -> int64 event indices

@@ -1,13 +1,14 @@
-"""Drop-in for finmlkit/feature/core/ma.py::sma, computed on the MI355X (csrc/fmk_rolling.hip)."""
+"""Drop-in for finmlkit/feature/core/ma.py::sma (csrc/fmk_rolling.hip) and ::ewma (csrc/fmk_recur.hip), computed on the MI355X."""
 from __future__ import annotations
 
 import numpy as np
 from numpy.typing import NDArray
 
 from ... import _ffi
-from ..._ffi import c_i64, ptr
+from ..._ffi import c_f64, c_i64, ptr
 
 WINDOW_MESSAGE = "window must be at least 1."
+SPAN_MESSAGE = "span size is less than or equal to 1. Please provide a span size greater than 1."
 
 
 def series_call(name: str, x, arg: int, *extra, least: int = 1, message: str = WINDOW_MESSAGE) -> NDArray[np.float64]:
@@ -26,3 +27,18 @@ def sma(array: NDArray[np.float64], window: int) -> NDArray[np.float64]:
     """Reference: finmlkit/feature/core/ma.py:46-62: (1.0 / window) * (the window's sum, added left to right), NaN before the first
     full window."""
     return series_call("fmk_sma", array, window)
+
+
+def ewma(y: NDArray, span: int) -> NDArray[np.float64]:
+    """Reference: finmlkit/feature/core/ma.py:6-43: pandas' `ewm(span=span).mean()` with adjust=True, u = y[t] + (1 - alpha) * u and
+    v = 1 + (1 - alpha) * v with alpha = 2 / (span + 1), out = u / v; NaN from the first NaN of `y` on.  `span < 1` raises
+    ValueError with the reference's message.  An empty series gives an empty array (the reference raises IndexError there).
+    A device-wide scan: the outputs agree with the reference to a few units in the last place (1e-9 relative is the contract),
+    NaN positions exactly.  Infinite inputs are outside the contract."""
+    if not float(span) >= 1.0:
+        raise ValueError(SPAN_MESSAGE)
+    yy = np.ascontiguousarray(y, dtype=np.float64)
+    out = np.empty(len(yy), np.float64)
+    if len(yy):
+        _ffi.default_context().call("fmk_ewma", ptr(yy), c_i64(len(yy)), c_f64(float(span)), ptr(out))
+    return out

@@ -1,5 +1,5 @@
-"""Drop-in for finmlkit/feature/core/momentum.py::roc and ::stoch_k, computed on the MI355X (csrc/fmk_order.hip).  The other
-indicators of that module (rsi_wilder and the rest) are one serial chain over the whole series and out of scope."""
+"""Drop-in for finmlkit/feature/core/momentum.py::roc and ::stoch_k (csrc/fmk_order.hip) and ::rsi_wilder (a device-wide scan of
+Wilder's recurrence, csrc/fmk_recur.hip), computed on the MI355X."""
 from __future__ import annotations
 
 import numpy as np
@@ -11,6 +11,7 @@ from .ma import series_call
 
 PERIOD_MESSAGE = "roc: period must not be negative."
 LENGTH_MESSAGE = "stoch_k: length must be at least 1."
+RSI_WINDOW_MESSAGE = "rsi_wilder: window must be at least 1."
 SHAPE_MESSAGE = "stoch_k: close, low and high must have the same length."
 
 
@@ -33,3 +34,13 @@ def stoch_k(close: NDArray[np.float64], low: NDArray[np.float64], high: NDArray[
     if len(c):
         _ffi.default_context().call("fmk_stoch_k", ptr(c), ptr(lo), ptr(hi), c_i64(len(c)), c_i64(int(length)), ptr(out))
     return out
+
+
+def rsi_wilder(close: NDArray[np.float64], window: int) -> NDArray[np.float64]:
+    """Reference: finmlkit/feature/core/momentum.py:25-65: the gains and losses of close[1 .. window] averaged, then Wilder's
+    avg = ((window - 1) * avg + x) / window; 100 - 100 / (1 + gain / loss) where loss > 0, NaN otherwise, before `window`, and
+    everywhere when a difference of the first window is NaN (a later NaN difference counts as no gain and no loss).
+    `window < 1` raises ValueError (the reference divides by zero there).  A device-wide scan: the outputs agree with the
+    reference within 1e-7 absolute on the 0-100 scale, NaN positions exactly.  Outside the contract: infinite prices, and the exact
+    bar at which an average underflows to zero after thousands of bars without a loss (there the output turns NaN)."""
+    return series_call("fmk_rsi_wilder", close, window, message=RSI_WINDOW_MESSAGE)

@@ -2,8 +2,8 @@
 
 The estimators that run on the raw tick frame are on the hot path: `ewmst`,
 `ewmst_mean0`, `ewms` and `realized_vol`; `rolling_variance_nb` and `variance_ratio_1_4_core` (the reference's
-microstructure-noise detector) run on a resident series too (csrc/fmk_rolling.hip).  The other bar-level indicators
-of that module (Bollinger, Parkinson, ATR) are out of scope.
+microstructure-noise detector) run on a resident series too (csrc/fmk_rolling.hip), and so do `true_range` and `atr`
+(csrc/fmk_recur.hip).  The other bar-level indicators of that module (Bollinger, Parkinson) are out of scope.
 """
 from __future__ import annotations
 
@@ -69,3 +69,42 @@ def variance_ratio_1_4_core(price: NDArray[np.float64], window: int, ddof: int, 
     """Reference: finmlkit/feature/core/volatility.py:481-540: var(1-step returns) / (var(4-step returns) / 4) over `window`;
     `ret_type` "log" takes log returns (the host's log), anything else simple returns."""
     return series_call("fmk_variance_ratio_1_4", price, window, c_i64(int(ddof)), C.c_int(ret_type == "log"))
+
+
+HLC_MESSAGE = "The length of high, low, and close prices must be the same."
+ATR_WINDOW_MESSAGE = "atr: window must not be negative."
+
+
+def _hlc(high, low, close):
+    h, lo, c = (np.ascontiguousarray(a, dtype=np.float64) for a in (high, low, close))
+    if not (h.ndim == lo.ndim == c.ndim == 1 and len(h) == len(lo) == len(c)):
+        raise ValueError(HLC_MESSAGE)
+    return h, lo, c
+
+
+def true_range(high: NDArray, low: NDArray, close: NDArray) -> NDArray:
+    """Reference: finmlkit/feature/core/volatility.py:222-253: max(high - low, |high - close[i-1]|, |low - close[i-1]|), NaN where
+    one of the three inputs is; bar 0 is high - low.  The reference's bits."""
+    h, lo, c = _hlc(high, low, close)
+    out = np.empty(len(h), np.float64)
+    if len(h):
+        _ffi.default_context().call("fmk_true_range", ptr(h), ptr(lo), ptr(c), c_i64(len(h)), ptr(out))
+    return out
+
+
+def atr(high: NDArray[np.float64], low: NDArray[np.float64], close: NDArray[np.float64], window: int, ema_based: bool = False,
+        normalize: bool = False) -> NDArray[np.float64]:
+    """Reference: finmlkit/feature/core/volatility.py:352-437.  SMA mode: the mean of the non-NaN true ranges of the window, the
+    reference's bits (its NaN at bar 2 included).  EMA mode: the mean of the first window's non-NaN true ranges, then
+    ((window - 1) * atr + tr) / window, NaN for good from the first NaN true range on; a device-wide scan that agrees with the
+    reference to a few units in the last place (1e-9 relative is the contract), NaN positions exactly; infinite prices are
+    outside the contract there.  `normalize` divides by (high + low) / 2.0.  Window 0 gives NaN everywhere, as the reference;
+    a negative window raises ValueError."""
+    if int(window) < 0:
+        raise ValueError(ATR_WINDOW_MESSAGE)
+    h, lo, c = _hlc(high, low, close)
+    out = np.empty(len(h), np.float64)
+    if len(h):
+        _ffi.default_context().call("fmk_atr", ptr(h), ptr(lo), ptr(c), c_i64(len(h)), c_i64(int(window)), C.c_int(bool(ema_based)),
+                                    C.c_int(bool(normalize)), ptr(out))
+    return out

@@ -1,7 +1,8 @@
 """The tick-level transforms of the hot path: `ReturnT`, `EWMST`, `RealizedVolatility` (+ `Compose`), the rolling-window moments
 `SMA`, `ZScore` and `VarianceRatio14` (reference transforms.py:549-574, :335-359, :867-897), the windowed order statistics
 `BurstRatio`, `ROC`, `PctChange` and `StochK` (reference transforms.py:362-385, :155-177, :180-203, :276-305), and the
-structural-break transform `CUSUMTest` (reference transforms.py:631-708).
+structural-break transform `CUSUMTest` (reference transforms.py:631-708), and the recursive indicators `EWMA`, `RSIWilder`, `ATR`
+and `ADX` (reference transforms.py:577-602, :206-273, :711-751, :991-1030).
 
 Counterparts of finmlkit/feature/transforms.py:89-117 (ReturnT), :308-332 (EWMST) and the
 pipeline part of finmlkit/feature/kit.py:Compose (:630-720), enough to run the QuickStart flow
@@ -20,10 +21,11 @@ import pandas as pd
 from .. import _ffi
 from .._ffi import DeviceArray, c_f64, c_i64
 from .core.structural_break.cusum import cusum_test_rolling
-from .core.ma import sma
-from .core.momentum import LENGTH_MESSAGE, PERIOD_MESSAGE, roc, stoch_k
+from .core.ma import SPAN_MESSAGE, ewma, sma
+from .core.momentum import LENGTH_MESSAGE, PERIOD_MESSAGE, RSI_WINDOW_MESSAGE, roc, rsi_wilder, stoch_k
+from .core.trend import adx_core
 from .core.utils import PERIODS_MESSAGE, comp_burst_ratio, comp_lagged_returns, comp_zscore, pct_change
-from .core.volatility import ewmst, realized_vol, variance_ratio_1_4_core
+from .core.volatility import atr, ewmst, realized_vol, variance_ratio_1_4_core
 
 
 class SISOTransform:
@@ -213,6 +215,52 @@ class BurstRatio(_Rolling):
         self.window = window
 
 
+class EWMA(SISOTransform):
+    """Exponentially weighted moving average (reference transforms.py:577-602).  backend="pd" is pandas' own
+    `ewm(span=span).mean()`, as in the reference (it skips NaN where the kernel propagates it)."""
+
+    def __init__(self, span: int, input_col: str = None):
+        super().__init__(input_col, f"ewma{span}")
+        self.span = span
+
+    def _pd(self, x):
+        outp = x[self.requires[0]].ewm(span=self.span).mean()
+        outp.name = self.output_name
+        return outp
+
+    def __call__(self, x: pd.DataFrame, *, backend: str = "nb") -> pd.Series:
+        assert backend in ("pd", "nb", "hip"), "Backend must be 'pd', 'nb' or 'hip'."
+        self._validate_input(x)
+        return self._pd(x) if backend == "pd" else self._hip(x)
+
+    def _hip(self, x):
+        return self._prepare_output_nb(x.index, ewma(self._prepare_input_nb(x), self.span))
+
+    def _dev(self, ts, y):
+        if not float(self.span) >= 1.0:
+            raise ValueError(SPAN_MESSAGE)
+        out = DeviceArray(ts.ctx, y.n, np.float64)
+        if y.n:
+            ts.ctx.call("fmk_ewma_dev", y.p, c_i64(y.n), c_f64(float(self.span)), out.p)
+        return out
+
+
+class RSIWilder(_Rolling):
+    """Wilder's relative strength index (reference transforms.py:206-273).  Both backends are the kernel.  The reference's pandas
+    backend is an arithmetic of its own: it gives 100 where there is no loss, the Numba kernel and this one give NaN there."""
+    _host = staticmethod(rsi_wilder)
+    _entry = "fmk_rsi_wilder_dev"
+
+    def __init__(self, window: int = 14, input_col: str = "close"):
+        super().__init__(input_col, f"rsiw{window}")
+        self.window = window
+
+    def _dev(self, ts, y):
+        if int(self.window) < 1:
+            raise ValueError(RSI_WINDOW_MESSAGE)
+        return super()._dev(ts, y)
+
+
 class _Lagged(SISOTransform):
     """An elementwise function of x[t] and x[t - periods] (csrc/fmk_order.hip)."""
     _host = None
@@ -316,6 +364,45 @@ class StochK(MISOTransform):
         cols = self._prepare_input_nb(x)
         high, low, close = (np.asarray(cols[c], dtype=np.float64) for c in self.requires[:3])
         return self._prepare_output_nb(x.index, stoch_k(high, low, close, self.length))
+
+
+class ATR(MISOTransform):
+    """Average true range (reference transforms.py:711-751); the columns are (high, low, close) in that order.  Both backends are
+    the kernel, as the reference's `_pd` falls back to Numba."""
+
+    def __init__(self, window: int = 14, ema_based: bool = False, normalize: bool = False, input_cols=None):
+        if input_cols is None:
+            input_cols = ["high", "low", "close"]
+        output_name = f"atr{window}"
+        if ema_based:
+            output_name += "_ema"
+        if normalize:
+            output_name += "_norm"
+        super().__init__(input_cols, output_name)
+        self.window = window
+        self.ema_based = ema_based
+        self.normalize = normalize
+
+    def _hip(self, x):
+        cols = self._prepare_input_nb(x)
+        high, low, close = (np.asarray(cols[c], dtype=np.float64) for c in self.requires[:3])
+        return self._prepare_output_nb(x.index, atr(high, low, close, self.window, self.ema_based, self.normalize))
+
+
+class ADX(MISOTransform):
+    """Average directional index (reference transforms.py:991-1030); the columns are (high, low, close) in that order.  Both
+    backends are the kernel, as the reference's `_pd` falls back to Numba."""
+
+    def __init__(self, length: int = 14, input_cols=None):
+        if input_cols is None:
+            input_cols = ["high", "low", "close"]
+        super().__init__(input_cols, f"adx_{length}")
+        self.length = length
+
+    def _hip(self, x):
+        cols = self._prepare_input_nb(x)
+        high, low, close = (np.asarray(cols[c], dtype=np.float64) for c in self.requires[:3])
+        return self._prepare_output_nb(x.index, adx_core(high, low, close, self.length))
 
 
 class SIMOTransform:

@@ -443,6 +443,44 @@ int fmk_roc(fmk_ctx *ctx, const double *x, int64_t n, int64_t period, double *ou
 int fmk_pct_change_dev(fmk_ctx *ctx, const double *d_x, int64_t n, int64_t periods, double *d_out);
 int fmk_pct_change(fmk_ctx *ctx, const double *x, int64_t n, int64_t periods, double *out);
 
+/* ---- recursive indicators: finmlkit/feature/core/ma.py (ewma), momentum.py (rsi_wilder), volatility.py (true_range, atr),
+ * trend.py (adx_core) on float64 series of n elements -> one float64 array of n elements (csrc/fmk_recur.hip).
+ *   true_range: bar 0: high - low, NaN when one of them is; bar i: max(high - low, |high - close[i-1]|, |low - close[i-1]|), NaN
+ *             when high, low or close[i-1] is NaN.  The reference's bits.
+ *   atr:      window 0 or window > n: NaN everywhere.  SMA mode (ema_based == 0): NaN before window - 1, then the mean of the non-NaN
+ *             true ranges of the window, added left to right (NaN when there is none; NaN at bar 2 when its high, low and close are
+ *             all NaN).  The reference's bits.  EMA mode: NaN before window - 1, there the mean of the non-NaN true ranges so far,
+ *             then ((window - 1) * atr + tr) / window, NaN for good from the first NaN true range on.  normalize: divided by
+ *             (high + low) / 2.0 where that and the value are numbers and it is > 0.
+ *   ewma:     alpha = 2 / (span + 1), u = y + (1 - alpha) * u, v = 1 + (1 - alpha) * v from (y[0], 1), out = u / v.
+ *   rsi_wilder: NaN before `window` (everywhere when n <= window); the gains and losses of close[1 .. window] summed and divided by
+ *             window, then avg = ((window - 1) * avg + x) / window; out = 100 - 100 / (1 + gain / loss) where loss > 0, NaN
+ *             otherwise.  A NaN difference inside the first window gives NaN everywhere; later it counts as no gain and no loss.
+ *   adx:      true range (0 at bar 0, no NaN checks), +DM and -DM summed over bars 1 .. length, then s = s - s / length + x; the
+ *             directional indices and dx from them; adx[2 length - 1] = mean(dx[length .. 2 length)), then
+ *             (adx * (length - 1) + dx) / length.  0.0 before 2 length - 1 and everywhere when n < 2 length.
+ * The four recurrences run as a device-wide scan: every step is the reference's own expression, but the state that enters a
+ * thread's 8 elements is composed from per-tile aggregates, so the outputs from the seed index on agree with the reference to a few
+ * units in the last place of the running averages (1e-9 relative is the contract; for rsi_wilder and adx 1e-7 absolute on their
+ * 0 .. 100 scale), while NaN positions, the outputs before the seed and adx's exact zeros are the reference's.  The seeds are added
+ * in index order.  Not part of the contract: infinite inputs to the four recurrences, and the exact step at which an average
+ * underflows to zero.  Scratch: the context's scratch (one record per 2048 elements); adx takes n float64 from the context's pool.
+ * FMK_E_ARG, checked before a device is touched and before any pointer is looked at: span < 1, rsi_wilder window < 1, atr window < 0,
+ * length < 1, n >= 2^31. */
+int fmk_ewma_dev(fmk_ctx *ctx, const double *d_y, int64_t n, double span, double *d_out);
+int fmk_ewma(fmk_ctx *ctx, const double *y, int64_t n, double span, double *out);
+int fmk_rsi_wilder_dev(fmk_ctx *ctx, const double *d_close, int64_t n, int64_t window, double *d_out);
+int fmk_rsi_wilder(fmk_ctx *ctx, const double *close, int64_t n, int64_t window, double *out);
+int fmk_true_range_dev(fmk_ctx *ctx, const double *d_high, const double *d_low, const double *d_close, int64_t n, double *d_out);
+int fmk_true_range(fmk_ctx *ctx, const double *high, const double *low, const double *close, int64_t n, double *out);
+int fmk_atr_dev(fmk_ctx *ctx, const double *d_high, const double *d_low, const double *d_close, int64_t n, int64_t window,
+                int ema_based, int normalize, double *d_out);
+int fmk_atr(fmk_ctx *ctx, const double *high, const double *low, const double *close, int64_t n, int64_t window, int ema_based,
+            int normalize, double *out);
+int fmk_adx_dev(fmk_ctx *ctx, const double *d_high, const double *d_low, const double *d_close, int64_t n, int64_t length,
+                double *d_out);
+int fmk_adx(fmk_ctx *ctx, const double *high, const double *low, const double *close, int64_t n, int64_t length, double *out);
+
 /* ---- labels and sample weights on the tick tape: finmlkit/label/tbm.py, label/weights.py ------------------------
  * triple_barrier (tbm.py:11-158) on the raw tape.  Per event: label (side labels -1 / +1; meta labels 0 / 1 when d_side is given),
  * index of the first barrier touch, the return there and the max return / barrier ratio.  Labels, touch indices, returns and ratios
