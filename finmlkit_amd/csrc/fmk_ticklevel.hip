@@ -354,6 +354,7 @@ __device__ __forceinline__ double ew_sigma(double V, double V2, double Sy, doubl
         return ew_sqrt(var);
     } else if constexpr (MODE == 1) {
         double var = V > 0.0 ? ew_div(Syy, V, ew_rcp(V)) : NAN;     // volatility.py:127-133
+        if (isinf(Syy) && V > 0.0 && V < INFINITY) var = Syy;       // an infinite U over finite weights: ew_div's remainder step gives inf - inf
         if (var < 0.0) var = 0.0;
         double s = ew_sqrt(var);
         if (s < sigma_floor) s = sigma_floor;
@@ -513,7 +514,7 @@ __device__ __forceinline__ EwMap ew_thread_ticks(const int64_t *__restrict__ ts,
 template <int MODE, int THREADS = EW_THREADS>
 __device__ __forceinline__ void ew_thread_apply(double V, double V2, double Sy, double Syy, const double (&yl)[EW_ITEMS],
                                                 const double (&al)[EW_ITEMS], double sigma_floor, int64_t tile, int64_t n,
-                                                double *__restrict__ out)
+                                                double *__restrict__ out, double *fin = nullptr /* [4]: the state after the eight ticks */)
 {
     const int64_t i0 = tile * (THREADS * EW_ITEMS) + (int64_t)threadIdx.x * EW_ITEMS;
     const bool whole = ew_whole_tile(tile, n, THREADS * EW_ITEMS);
@@ -530,6 +531,7 @@ __device__ __forceinline__ void ew_thread_apply(double V, double V2, double Sy, 
     }
     if (MODE != 2 && i0 == 0) res[0] = NAN;
     ew_store8(out, i0, n, whole, res);
+    if (fin) { fin[0] = V; fin[1] = V2; fin[2] = Sy; fin[3] = Syy; }
 }
 
 template <int MODE>
@@ -599,13 +601,56 @@ __device__ __forceinline__ void ew_enter(const EwMap &ex, const double *__restri
     }
 }
 
+// ewmst after a restart.  A tick whose 1 - alpha is at most EW_RESTART_OM (a weekend gap: alpha exactly 1) leaves the state one sample, and
+// so does the start of the series.  While only ticks with a tiny alpha follow (gaps of 0 and 1 ns: alpha of 1e-10), var_raw = Syy / V - mean^2 and
+// denom = V - V2 / V are cancellation residues of 1e-10 x their operands and their quotient is a sigma of ordinary size: a state that differs
+// from the loop's in its last bit -- a composed one does -- moves it by 1e-16 / 1e-10, past the 1e-9 of the contract.  So those ticks are
+// STEPPED: a thread of k_ew_apply whose eight ticks hold a restart (or the first tick with a weight: it enters with V == 0 and has an alpha > 0;
+// a shard that enters with a state has none) leaves the state after its last tick in a record, and
+// k_ew_restart_walk, one lane per record, goes on from there in the reference's own order, rewriting the outputs, until the weights are those
+// of more than one sample (V^2 - V2 >= EW_WALK_DONE x V^2: the residues are then at least 1e-4 of their operands), the next restart, the end
+// of the series or EW_WALK_CAP ticks.  What enters a restart tick reaches the state behind it times 1 - alpha <= 1e-5, so its last bits do not.
+// Walks do not overlap: each ends at the next restart tick, whose own record starts behind it.  The limits (include/fmk.h): a call whose
+// threads hold more than EW_RESTART_RECORDS restarts is not walked at all (which records an overfull list holds would depend on the order of
+// the atomics; the count does not), and behind EW_WALK_CAP ticks of one walk (a run of that many ticks within nanoseconds of a restart) the
+// composed outputs stay.  A half life that is not positive and finite has no walk: V never becomes positive, every output is NaN.  The map-only
+// entry (fmk_ewmst_shard_map_dev) writes no outputs and needs none; the one-pass kernel behind FMK_EW_ONE_PASS has no walk.
+#define EW_RESTART_OM 1e-5
+#define EW_WALK_DONE 1e-4
+#define EW_WALK_CAP (1 << 16)
+#define EW_RESTART_RECORDS (1 << 16)
+struct EwRestart { int64_t next; double s[4]; };     // the first tick to step, and (V, V2, Sy, Syy) in front of it
+
+__global__ __launch_bounds__(256) void k_ew_restart_walk(const int64_t *__restrict__ ts, const double *__restrict__ y, int64_t n, EwHl h,
+                                                         double sigma_floor, const unsigned long long *__restrict__ count,
+                                                         const EwRestart *__restrict__ rec, double *__restrict__ out)
+{
+    const unsigned long long t = (unsigned long long)blockIdx.x * 256 + threadIdx.x;
+    const unsigned long long m = *count;
+    if (m > EW_RESTART_RECORDS || t >= m) return;
+    double V = rec[t].s[0], V2 = rec[t].s[1], Sy = rec[t].s[2], Syy = rec[t].s[3];
+    int64_t j = rec[t].next;                              // >= EW_ITEMS
+    for (int steps = 0; j < n && steps < EW_WALK_CAP; ++j, ++steps) {
+        const double dt = ew_div((double)(ts[j] - ts[j - 1]), 1e9, 1e-9);          // the bits of ew_alphas
+        const double x = h.r != 0.0 ? -ew_div(dt, h.hl, h.r) : -(dt / h.hl);
+        const double alpha = 1.0 - fmk_exp_host(x);
+        ew_step<0>(V, V2, Sy, Syy, alpha, y[j]);
+        out[j] = ew_sigma<0>(V, V2, Sy, Syy, sigma_floor);
+        if (alpha >= 1.0 - EW_RESTART_OM) break;          // the next restart: its own record goes on
+        if (V > 0.0 && V * V - V2 >= EW_WALK_DONE * (V * V)) break;
+    }
+}
+
 template <int MODE>
-// five waves per SIMD (96 VGPRs, no spill): 7.47 ms per 1e9 ticks; six (80 VGPRs, 8 spill instructions): 7.6; four: 7.46 (round 6)
+// five waves per SIMD (no spill; MODE 0 with the restart record: 90 VGPRs).  Round 6, before the record: 7.47 ms per 1e9 ticks; six waves (80 VGPRs,
+// 8 spill instructions): 7.6; four: 7.46.  With the record and the walk's launch: 0.913 against 0.903 ms per 1e8 ticks.
 __global__ __launch_bounds__(EW_THREADS, 5) void k_ew_apply(const int64_t *__restrict__ ts, const double *__restrict__ y,
                                                          int64_t n, EwHl half_life, double sigma_floor,
                                                          const EwMap *__restrict__ tile_pre,
                                                          const double *__restrict__ state_in,
-                                                         double *__restrict__ out)
+                                                         double *__restrict__ out,
+                                                         unsigned long long *__restrict__ restart_count = nullptr,
+                                                         EwRestart *__restrict__ restart_rec = nullptr)
 {
     __shared__ EwMap lds[4];
     double yl[EW_ITEMS], al[EW_ITEMS];
@@ -615,7 +660,24 @@ __global__ __launch_bounds__(EW_THREADS, 5) void k_ew_apply(const int64_t *__res
     ex = ew_compose(tile_pre[blockIdx.x], ex);
     double V, V2, Sy, Syy;
     ew_enter(ex, state_in, V, V2, Sy, Syy);
-    ew_thread_apply<MODE>(V, V2, Sy, Syy, yl, al, sigma_floor, blockIdx.x, n, out);
+    if constexpr (MODE == 0) {
+        double fin[4];
+        const bool unweighted = V == 0.0;                                     // no tick has had a weight yet (composing identities is exact)
+        ew_thread_apply<MODE>(V, V2, Sy, Syy, yl, al, sigma_floor, blockIdx.x, n, out, fin);
+        bool restart = false;
+#pragma unroll
+        for (int k = 0; k < EW_ITEMS; ++k)                                    // (ticks that are not there: alpha 0)
+            restart |= al[k] >= 1.0 - EW_RESTART_OM || (unweighted && al[k] > 0.0);
+        const int64_t next = ((int64_t)blockIdx.x * EW_THREADS + threadIdx.x + 1) * EW_ITEMS;
+        if (restart && restart_count && next < n) {
+            const unsigned long long slot = atomicAdd(restart_count, 1ULL);
+            if (slot < EW_RESTART_RECORDS) {
+                restart_rec[slot].next = next;
+                restart_rec[slot].s[0] = fin[0]; restart_rec[slot].s[1] = fin[1]; restart_rec[slot].s[2] = fin[2]; restart_rec[slot].s[3] = fin[3];
+            }
+        }
+    } else
+        ew_thread_apply<MODE>(V, V2, Sy, Syy, yl, al, sigma_floor, blockIdx.x, n, out);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -807,7 +869,8 @@ static int ew_run(fmk_ctx *ctx, const int64_t *d_ts, const double *d_y, int64_t 
         if (g <= 1) break;
     }
     void *scr;
-    // The one-pass kernel (16 + 8 B/tick instead of 2 x 16 + 8) is correct -- the same suite runs through it -- and SLOWER at every size
+    // The one-pass kernel (16 + 8 B/tick instead of 2 x 16 + 8) agrees with the two passes on the regular tape (test_ewmst_one_pass_kernel_matches_two_pass;
+    // it has no restart walk, k_ew_restart_walk, and is not run on the irregular tapes) and is SLOWER at every size
     // measured, every round: 25.9 vs 16.0 ms (round 2, one predecessor per round trip), 9.3 vs 9.7 (round 5, two-level look-back), 9.5 vs
     // 8.0 ms (round 6: the two passes lost more instructions than it did).  A workgroup's four waves sit out two dependent round trips
     // between its map phase and its apply phase, and at 112 .. 128 registers only four workgroups share a CU to cover for each other;
@@ -831,9 +894,15 @@ static int ew_run(fmk_ctx *ctx, const int64_t *d_ts, const double *d_y, int64_t 
         FMK_LAUNCH_CHECK(ctx);
         return FMK_OK;
     }
-    FMK_TRY(fmk_scratch(ctx, (size_t)(tiles + work_maps + 2) * sizeof(EwMap), &scr));
+    const size_t map_bytes = (size_t)(tiles + work_maps + 2) * sizeof(EwMap);
+    const int64_t threads = tiles * EW_THREADS;
+    const bool walk = MODE == 0 && !d_map_out && half_life > 0.0 && half_life < INFINITY;
+    const size_t records = walk ? (size_t)(threads < EW_RESTART_RECORDS ? threads : EW_RESTART_RECORDS) : 0;
+    FMK_TRY(fmk_scratch(ctx, map_bytes + 64 + records * sizeof(EwRestart), &scr));
     EwMap *tm = (EwMap *)scr;
     EwMap *work = tm + tiles;
+    unsigned long long *restart_count = (unsigned long long *)((char *)scr + map_bytes);      // map_bytes is a multiple of 16
+    EwRestart *restart_rec = (EwRestart *)((char *)scr + map_bytes + 64);
     // (round 4 tried leaving the alphas of the map pass in d_out for the apply pass: what exp saved the 8 GB of stores cost -- profiles/r04_ewmst.txt)
     k_ew_tile_maps<MODE><<<(unsigned)tiles, EW_THREADS, 0, ctx->stream>>>(d_ts, d_y, n, hl, tm);
     FMK_LAUNCH_CHECK(ctx);
@@ -843,6 +912,14 @@ static int ew_run(fmk_ctx *ctx, const int64_t *d_ts, const double *d_y, int64_t 
         return FMK_OK;
     }
     FMK_TRY(ew_scan_maps(ctx, tm, tiles, work));
+    if (records) {
+        FMK_HIP(ctx, hipMemsetAsync(restart_count, 0, 8, ctx->stream));
+        k_ew_apply<MODE><<<(unsigned)tiles, EW_THREADS, 0, ctx->stream>>>(d_ts, d_y, n, hl, sigma_floor, tm, d_state_in, d_out, restart_count, restart_rec);
+        FMK_LAUNCH_CHECK(ctx);
+        k_ew_restart_walk<<<(unsigned)fmk_ceil_div((int64_t)records, 256), 256, 0, ctx->stream>>>(d_ts, d_y, n, hl, sigma_floor, restart_count, restart_rec, d_out);
+        FMK_LAUNCH_CHECK(ctx);
+        return FMK_OK;
+    }
     k_ew_apply<MODE><<<(unsigned)tiles, EW_THREADS, 0, ctx->stream>>>(d_ts, d_y, n, hl, sigma_floor, tm, d_state_in, d_out);
     FMK_LAUNCH_CHECK(ctx);
     return FMK_OK;

@@ -278,7 +278,23 @@ int fmk_comp_lagged_returns_dev(fmk_ctx *ctx, const int64_t *d_ts, const double 
                                 int64_t n, double return_window_sec, int is_log, double *d_out);
 int fmk_comp_lagged_returns(fmk_ctx *ctx, const int64_t *ts, const double *close_, int64_t n,
                             double return_window_sec, int is_log, double *out);
-/* ewmst / ewmst_mean0 (core/volatility.py:139-219, 72-136). */
+/* ewmst / ewmst_mean0 (core/volatility.py:139-219, 72-136).  Every tick is the reference's own update and closing expression, but
+ * the state that enters a thread's 8 ticks is composed from per-tile affine maps: NaN positions, out[0], exact zeros and every
+ * output that is sigma_floor are the reference's; the rest is within 1e-9 relative, or 1e-11 x the series' typical sigma absolute.
+ * Any half life is taken as the reference takes it (zero, negative and non-finite ones included).  Not part of the contract: an
+ * infinite y.  The loop keeps an infinite state where a composed map whose decay product has underflowed to 0 gives 0 * inf = NaN.
+ * What holds there: the outputs before the first infinite element are unaffected; from it on ewmst is sigma_floor, as the
+ * reference's (a NaN and an infinite state give the same closing expression); ewmst_mean0 is inf or NaN from it on, and equals the
+ * reference's where no decay product up to the tick has underflowed.
+ * ewmst after a restart.  A tick with 1 - alpha <= 1e-5 (a weekend gap) leaves the state one sample, and so does the first tick
+ * that carries a weight.  While only gaps of nanoseconds follow, the closing expression is a quotient of two cancellation residues
+ * and only the loop's own state gives the loop's sigma, so those ticks are stepped in the reference's order (k_ew_restart_walk),
+ * from the end of the 8-tick group that holds the restart until the weights are those of more than one sample
+ * (V^2 - V2 >= 1e-4 V^2), the next restart or the end of the series.  Limits, behind which the composed state's outputs stay and
+ * the 1e-9 is not promised for such ticks: 65 536 ticks per walk (a run of that many ticks within nanoseconds of a restart), and
+ * 65 536 8-tick groups with a restart per call (a call with more is not walked at all; its result does not depend on the run).
+ * fmk_ewmst_shard_apply_dev walks too (a shard that enters with weights has no first tick of its own); the kernel behind
+ * FMK_EW_ONE_PASS does not. */
 int fmk_ewmst_dev(fmk_ctx *ctx, const int64_t *d_ts, const double *d_y, int64_t n,
                   double half_life, double sigma_floor, int mean0, double *d_out);
 int fmk_ewmst(fmk_ctx *ctx, const int64_t *ts, const double *y, int64_t n, double half_life,
