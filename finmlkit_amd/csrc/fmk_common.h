@@ -252,6 +252,20 @@ static inline int fmk_rule_ewma(fmk_ctx *ctx, double span)
 static inline int fmk_rule_rsi_wilder(fmk_ctx *ctx, int64_t window) { return fmk_rule_least(ctx, window, 1, "rsi_wilder: window must be at least 1."); }
 static inline int fmk_rule_atr(fmk_ctx *ctx, int64_t window) { return fmk_rule_least(ctx, window, 0, "atr: window must not be negative."); }
 static inline int fmk_rule_adx(fmk_ctx *ctx, int64_t length) { return fmk_rule_least(ctx, length, 1, "adx_core: length must be at least 1."); }
+// the running-sum indicators (fmk_runsum.hip)
+static inline int fmk_rule_bollinger(fmk_ctx *ctx, int64_t window)
+{
+    return fmk_rule_least(ctx, window, 1, "bollinger_percent_b: window must be at least 1.");
+}
+static inline int fmk_rule_vwap_distance(fmk_ctx *ctx, int64_t n_periods)
+{
+    return fmk_rule_least(ctx, n_periods, 1, "vwap_distance: n_periods must be at least 1.");
+}
+static inline int fmk_rule_flow_acceleration(fmk_ctx *ctx, int64_t recent_periods)
+{
+    return fmk_rule_least(ctx, recent_periods, 0, "comp_flow_acceleration: recent_periods must not be negative.");
+}
+static inline int fmk_rule_vpin(fmk_ctx *ctx, int64_t window) { return fmk_rule_least(ctx, window, 0, "vpin: window must not be negative."); }
 
 // One excursion of a call onto the context's auxiliary stream (fmk_api.hip), the only way there.  Rules:
 //  - one fork per context at a time: fork() while another FmkSide of the context is open is an error;

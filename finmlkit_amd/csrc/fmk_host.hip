@@ -85,6 +85,21 @@ int hlc_host(fmk_ctx *ctx, int rule, const double *high, const double *low, cons
     return down(ctx, out, (const double *)d_o, n);
 }
 
+// two series up, dev(d_a, d_b, d_out), one series of T down
+template <typename T, typename Dev>
+int pair_host(fmk_ctx *ctx, int rule, const double *a, const double *b, int64_t n, T *out, Dev dev)
+{
+    FMK_TRY(rule);
+    DevBag bag(ctx);
+    double *d_a, *d_b;
+    T *d_o;
+    FMK_TRY(bag.up(a, n, &d_a));
+    FMK_TRY(bag.up(b, n, &d_b));
+    FMK_TRY(bag.out(n, &d_o));
+    FMK_TRY(dev(d_a, d_b, d_o));
+    return down(ctx, out, (const T *)d_o, n);
+}
+
 }  // namespace
 
 extern "C" {
@@ -667,6 +682,42 @@ int fmk_adx(fmk_ctx *ctx, const double *high, const double *low, const double *c
     FMK_TRY(fmk_rule_adx(ctx, length));
     return hlc_host(ctx, fmk_series_check(ctx, "adx_core", n), high, low, close, n, out,
                     [=](const double *h, const double *l, const double *c, double *o) { return fmk_adx_dev(ctx, h, l, c, n, length, o); });
+}
+
+// the running-sum indicators (fmk_runsum.hip)
+int fmk_bollinger_percent_b(fmk_ctx *ctx, const double *close, int64_t n, int64_t window, double num_std, double *out)
+{
+    FMK_TRY(fmk_rule_bollinger(ctx, window));
+    return series_host(ctx, fmk_series_check(ctx, "bollinger_percent_b", n), close, n, out,
+                       [=](const double *d_x, double *d_o) { return fmk_bollinger_percent_b_dev(ctx, d_x, n, window, num_std, d_o); });
+}
+
+int fmk_vwap_distance(fmk_ctx *ctx, const double *close, const double *volume, int64_t n, int64_t n_periods, int is_log, double *out)
+{
+    FMK_TRY(fmk_rule_vwap_distance(ctx, n_periods));
+    return pair_host(ctx, fmk_series_check(ctx, "vwap_distance", n), close, volume, n, out,
+                     [=](const double *c, const double *v, double *o) { return fmk_vwap_distance_dev(ctx, c, v, n, n_periods, is_log, o); });
+}
+
+int fmk_flow_acceleration(fmk_ctx *ctx, const double *volumes, int64_t n, int64_t window, int64_t recent_periods, double *out)
+{
+    FMK_TRY(fmk_rule_flow_acceleration(ctx, recent_periods));
+    return series_host(ctx, fmk_series_check(ctx, "comp_flow_acceleration", n), volumes, n, out, [=](const double *d_x, double *d_o) {
+        return fmk_flow_acceleration_dev(ctx, d_x, n, window, recent_periods, d_o);
+    });
+}
+
+int fmk_vpin(fmk_ctx *ctx, const double *volume_buy, const double *volume_sell, int64_t n, int64_t window, float *out)
+{
+    FMK_TRY(fmk_rule_vpin(ctx, window));
+    return pair_host(ctx, fmk_series_check(ctx, "vpin", n), volume_buy, volume_sell, n, out,
+                     [=](const double *b, const double *s, float *o) { return fmk_vpin_dev(ctx, b, s, n, window, o); });
+}
+
+int fmk_parkinson_range(fmk_ctx *ctx, const double *high, const double *low, int64_t n, double *out)
+{
+    return pair_host(ctx, fmk_series_check(ctx, "parkinson_range", n), high, low, n, out,
+                     [=](const double *h, const double *l, double *o) { return fmk_parkinson_range_dev(ctx, h, l, n, o); });
 }
 
 }  // extern "C"

@@ -30,115 +30,13 @@
 
 #include "fmk_common.h"
 #include "fmk_dpp.h"
+#include "fmk_recur_core.h"
 #include "fmk_window.h"
 
-#define RC_THREADS 256
-#define RC_ITEMS 8                   // consecutive elements per thread: four 16-byte loads per series
-#define RC_TILE (RC_THREADS * RC_ITEMS)
-#define RC_AGG_UNIT RC_THREADS       // tile maps per trip of the aggregate scan
 #define ATR_OPL 4                    // SMA mode: outputs per lane of the window walk
 #define ATR_TILE (RC_THREADS * ATR_OPL)
 
 namespace {
-
-// s -> a * s + b[k] on channel k
-template <int K>
-struct RcMap {
-    double a;
-    double b[K];
-};
-
-template <int K>
-__device__ __forceinline__ RcMap<K> rc_identity()
-{
-    RcMap<K> m;
-    m.a = 1.0;
-#pragma unroll
-    for (int k = 0; k < K; ++k) m.b[k] = 0.0;
-    return m;
-}
-
-// f first, then g
-template <int K>
-__device__ __forceinline__ RcMap<K> rc_compose(const RcMap<K> &f, const RcMap<K> &g)
-{
-    RcMap<K> r;
-    r.a = g.a * f.a;
-#pragma unroll
-    for (int k = 0; k < K; ++k) r.b[k] = g.a * f.b[k] + g.b[k];
-    return r;
-}
-
-template <int CTRL, int ROW_MASK, int K>
-__device__ __forceinline__ RcMap<K> rc_dpp(const RcMap<K> &m)
-{
-    RcMap<K> r;
-    r.a = fmk_dpp<CTRL, ROW_MASK>(1.0, m.a);
-#pragma unroll
-    for (int k = 0; k < K; ++k) r.b[k] = fmk_dpp<CTRL, ROW_MASK>(0.0, m.b[k]);
-    return r;
-}
-
-// The maps of the workgroup's 256 threads in thread order: returns the composition of the threads before this one, *total = of all.
-// Lanes without a source compose with the identity, which is exact.  Two barriers: may be called again at once.
-template <int K>
-__device__ __forceinline__ RcMap<K> rc_block_exclusive(const RcMap<K> &mine, RcMap<K> *lds /* [4] */, RcMap<K> *total)
-{
-    const int lane = fmk_lane(), w = threadIdx.x >> 6;
-    RcMap<K> inc = mine;
-    inc = rc_compose(rc_dpp<FMK_DPP_ROW_SHR(1), 0xF>(inc), inc);
-    inc = rc_compose(rc_dpp<FMK_DPP_ROW_SHR(2), 0xF>(inc), inc);
-    inc = rc_compose(rc_dpp<FMK_DPP_ROW_SHR(4), 0xF>(inc), inc);
-    inc = rc_compose(rc_dpp<FMK_DPP_ROW_SHR(8), 0xF>(inc), inc);
-    inc = rc_compose(rc_dpp<FMK_DPP_ROW_BCAST15, 0xA>(inc), inc);
-    inc = rc_compose(rc_dpp<FMK_DPP_ROW_BCAST31, 0xC>(inc), inc);
-    if (lane == 63) lds[w] = inc;
-    __syncthreads();
-    RcMap<K> pre = rc_identity<K>();
-    for (int k = 0; k < w; ++k) pre = rc_compose(pre, lds[k]);
-    RcMap<K> tot = lds[0];
-#pragma unroll
-    for (int k = 1; k < RC_THREADS / 64; ++k) tot = rc_compose(tot, lds[k]);
-    *total = tot;
-    const RcMap<K> prev = rc_dpp<FMK_DPP_WAVE_SHR1, 0xF>(inc);      // lane 0: the identity
-    __syncthreads();
-    return rc_compose(pre, prev);
-}
-
-// ---- the thread's 8 consecutive elements.  whole: every element of the workgroup's tile exists and none of them is element 0
-// (uniform over the workgroup); the other tiles read element by element with range checks (0.0 for what is not there).
-typedef double rc_d2 __attribute__((ext_vector_type(2), aligned(8)));          // 16-byte accesses on an 8-byte alignment promise
-
-__device__ __forceinline__ bool rc_whole(int64_t tile, int64_t n) { return tile > 0 && (tile + 1) * RC_TILE <= n; }
-
-__device__ __forceinline__ void rc_load8(const double *__restrict__ src, int64_t i0, int64_t n, bool whole, double (&v)[RC_ITEMS])
-{
-    if (whole) {
-        const rc_d2 *q = (const rc_d2 *)(src + i0);
-#pragma unroll
-        for (int k = 0; k < RC_ITEMS / 2; ++k) { const rc_d2 t = q[k]; v[2 * k] = t.x; v[2 * k + 1] = t.y; }
-    } else {
-#pragma unroll
-        for (int k = 0; k < RC_ITEMS; ++k) v[k] = i0 + k < n ? src[i0 + k] : 0.0;
-    }
-}
-// src[i0 - 1]: the element in front of the thread's first (0.0 in front of element 0 and beyond the series)
-__device__ __forceinline__ double rc_prev(const double *__restrict__ src, int64_t i0, int64_t n)
-{
-    return (i0 >= 1 && i0 - 1 < n) ? src[i0 - 1] : 0.0;
-}
-__device__ __forceinline__ void rc_store8(double *__restrict__ dst, int64_t i0, int64_t n, bool whole, const double (&v)[RC_ITEMS])
-{
-    if (whole) {
-        rc_d2 *q = (rc_d2 *)(dst + i0);
-#pragma unroll
-        for (int k = 0; k < RC_ITEMS / 2; ++k) { rc_d2 t; t.x = v[2 * k]; t.y = v[2 * k + 1]; q[k] = t; }
-    } else {
-#pragma unroll
-        for (int k = 0; k < RC_ITEMS; ++k)
-            if (i0 + k < n) dst[i0 + k] = v[k];
-    }
-}
 
 // ---- the inputs of the recurrences, as the reference writes them
 // Python's max(a, b, c): the first of the largest, a NaN staying where it is first
@@ -331,163 +229,6 @@ struct RcAdxLast {
     __device__ __forceinline__ void fin(double (&s)[K], int64_t) const { s[0] = s[0] / L; }
 };
 
-// The seed value, by the whole workgroup: the terms of 256 elements at a time go to LDS, thread 0 adds them in index order.  Every
-// thread returns with the value in sv.
-template <class S>
-__device__ __forceinline__ void rc_seed(const S &sp, double (*stage)[RC_THREADS], double (&sv)[S::K])
-{
-    constexpr int K = S::K;
-    double s[K];
-    int64_t cnt = 0;
-#pragma unroll
-    for (int k = 0; k < K; ++k) s[k] = 0.0;
-    const int64_t lo = sp.seed_lo(), hi = sp.seed_hi();
-    for (int64_t c0 = lo; c0 <= hi; c0 += RC_THREADS) {
-        const int64_t i = c0 + threadIdx.x;
-        if (i <= hi) {
-            double t[K];
-            sp.term(i, t);
-#pragma unroll
-            for (int k = 0; k < K; ++k) stage[k][threadIdx.x] = t[k];
-        }
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            const int m = (int)(hi - c0 + 1 < RC_THREADS ? hi - c0 + 1 : RC_THREADS);
-            for (int j = 0; j < m; ++j) {
-                double t[K];
-#pragma unroll
-                for (int k = 0; k < K; ++k) t[k] = stage[k][j];
-                sp.acc(s, cnt, t);
-            }
-        }
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) {
-        sp.fin(s, cnt);
-#pragma unroll
-        for (int k = 0; k < K; ++k) stage[k][0] = s[k];
-    }
-    __syncthreads();
-#pragma unroll
-    for (int k = 0; k < K; ++k) sv[k] = stage[k][0];
-    __syncthreads();
-}
-
-// the thread's elements and what they do to a state: the identity before the seed and beyond the series, the constant sv at the seed
-template <class S>
-__device__ __forceinline__ RcMap<S::K> rc_thread_map(const S &sp, int64_t tile, int64_t n, const double (&sv)[S::K], typename S::In &in)
-{
-    constexpr int K = S::K;
-    const int64_t i0 = tile * RC_TILE + (int64_t)threadIdx.x * RC_ITEMS;
-    sp.load(i0, n, rc_whole(tile, n), in);
-    RcMap<K> m = rc_identity<K>();
-#pragma unroll
-    for (int j = 0; j < RC_ITEMS; ++j) {
-        const int64_t i = i0 + j;
-        if (i >= n) continue;
-        if (i > sp.seed) {
-            double x[K];
-            sp.x(in, j, i, x);
-            m.a = sp.a * m.a;
-#pragma unroll
-            for (int k = 0; k < K; ++k) m.b[k] = sp.a * m.b[k] + sp.lin(x[k]);
-        } else if (i == sp.seed) {
-            m.a = 0.0;
-#pragma unroll
-            for (int k = 0; k < K; ++k) m.b[k] = sv[k];
-        }
-    }
-    return m;
-}
-
-__device__ __forceinline__ bool rc_has_seed(int64_t tile, int64_t seed) { return seed >= tile * RC_TILE && seed < (tile + 1) * RC_TILE; }
-
-// first launch: the tile's map; the tile with the seed index leaves the seed value in seedv[K].  The host launches only when seed < n.
-template <class S>
-__global__ __launch_bounds__(RC_THREADS) void k_rc_tiles(S sp, int64_t n, RcMap<S::K> *__restrict__ tile_map, double *__restrict__ seedv)
-{
-    constexpr int K = S::K;
-    __shared__ RcMap<K> wl[RC_THREADS / 64];
-    __shared__ double stage[K][RC_THREADS];
-    double sv[K];
-#pragma unroll
-    for (int k = 0; k < K; ++k) sv[k] = 0.0;
-    if (rc_has_seed(blockIdx.x, sp.seed)) {                          // uniform over the workgroup
-        rc_seed(sp, stage, sv);
-        if (threadIdx.x == 0) {
-#pragma unroll
-            for (int k = 0; k < K; ++k) seedv[k] = sv[k];
-        }
-    }
-    typename S::In in;
-    const RcMap<K> m = rc_thread_map(sp, blockIdx.x, n, sv, in);
-    RcMap<K> tot;
-    (void)rc_block_exclusive(m, wl, &tot);
-    if (threadIdx.x == 0) tile_map[blockIdx.x] = tot;
-}
-
-// second launch, one workgroup: maps[t] <- the composition of maps[0 .. t - 1], RC_AGG_UNIT maps per trip, the next trip's loaded
-// ahead of the scan (a trip writes below the next one's maps only)
-template <int K>
-__global__ __launch_bounds__(RC_THREADS) void k_rc_aggscan(RcMap<K> *maps, int64_t m)
-{
-    __shared__ RcMap<K> wl[RC_THREADS / 64];
-    RcMap<K> run = rc_identity<K>();
-    RcMap<K> nxt = (int64_t)threadIdx.x < m ? maps[threadIdx.x] : rc_identity<K>();
-    for (int64_t b = 0; b < m; b += RC_AGG_UNIT) {
-        const int64_t i = b + threadIdx.x;
-        const RcMap<K> v = nxt;
-        nxt = i + RC_AGG_UNIT < m ? maps[i + RC_AGG_UNIT] : rc_identity<K>();
-        RcMap<K> tot;
-        const RcMap<K> ex = rc_block_exclusive(v, wl, &tot);
-        if (i < m) maps[i] = rc_compose(run, ex);
-        run = rc_compose(run, tot);
-    }
-}
-
-// third launch: the outputs
-template <class S>
-__global__ __launch_bounds__(RC_THREADS) void k_rc_apply(S sp, int64_t n, const RcMap<S::K> *__restrict__ tile_pre,
-                                                         const double *__restrict__ seedv, double *__restrict__ out)
-{
-    constexpr int K = S::K;
-    __shared__ RcMap<K> wl[RC_THREADS / 64];
-    double sv[K];
-#pragma unroll
-    for (int k = 0; k < K; ++k) sv[k] = rc_has_seed(blockIdx.x, sp.seed) ? seedv[k] : 0.0;
-    typename S::In in;
-    const RcMap<K> m = rc_thread_map(sp, blockIdx.x, n, sv, in);
-    RcMap<K> tot;
-    const RcMap<K> ex = rc_block_exclusive(m, wl, &tot);
-    const RcMap<K> pre = tile_pre[blockIdx.x];                       // applied to the zero state: its b
-    double s[K];
-#pragma unroll
-    for (int k = 0; k < K; ++k) s[k] = ex.a * pre.b[k] + ex.b[k];
-    const int64_t i0 = (int64_t)blockIdx.x * RC_TILE + (int64_t)threadIdx.x * RC_ITEMS;
-    double res[RC_ITEMS];
-#pragma unroll
-    for (int j = 0; j < RC_ITEMS; ++j) {
-        const int64_t i = i0 + j;
-        if (i < sp.seed) { res[j] = sp.before(); continue; }
-        if (i == sp.seed) {
-#pragma unroll
-            for (int k = 0; k < K; ++k) s[k] = sv[k];
-        } else {
-            double x[K];
-            sp.x(in, j, i, x);
-#pragma unroll
-            for (int k = 0; k < K; ++k) s[k] = sp.step(s[k], x[k]);
-        }
-        res[j] = sp.emit(s, in, j);
-    }
-    rc_store8(out, i0, n, rc_whole(blockIdx.x, n), res);
-}
-
-__global__ __launch_bounds__(256) void k_rc_fill(double *out, int64_t n, double v)
-{
-    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) out[i] = v;
-}
-
 __global__ __launch_bounds__(256) void k_true_range(const double *__restrict__ h, const double *__restrict__ l, const double *__restrict__ c,
                                                     int64_t n, double *__restrict__ out)
 {
@@ -531,32 +272,6 @@ __global__ __launch_bounds__(RC_THREADS) void k_atr_sma(AtrSmaArgs a)
         if (t == 2 && hi != hi && lw != lw && c[t] != c[t]) o = NAN;
         a.out[t] = a.normalize ? rc_normalize(o, hi, lw) : o;
     }
-}
-
-int rc_fill(fmk_ctx *ctx, double *d_out, int64_t n, double v)
-{
-    k_rc_fill<<<fmk_grid_blocks(ctx, n), 256, 0, ctx->stream>>>(d_out, n, v);
-    FMK_LAUNCH_CHECK(ctx);
-    return FMK_OK;
-}
-
-// one recurrence over n > 0 elements on the context's stream; a series that ends before the seed is before() everywhere
-template <class S>
-int rc_scan(fmk_ctx *ctx, const S &sp, int64_t n, double *d_out, double before)
-{
-    if (sp.seed >= n) return rc_fill(ctx, d_out, n, before);
-    const int64_t tiles = fmk_ceil_div(n, RC_TILE);
-    void *scr;
-    FMK_TRY(fmk_scratch(ctx, (size_t)tiles * sizeof(RcMap<S::K>) + S::K * sizeof(double), &scr));
-    RcMap<S::K> *maps = (RcMap<S::K> *)scr;
-    double *seedv = (double *)(maps + tiles);
-    k_rc_tiles<S><<<(unsigned)tiles, RC_THREADS, 0, ctx->stream>>>(sp, n, maps, seedv);
-    FMK_LAUNCH_CHECK(ctx);
-    k_rc_aggscan<S::K><<<1, RC_THREADS, 0, ctx->stream>>>(maps, tiles);
-    FMK_LAUNCH_CHECK(ctx);
-    k_rc_apply<S><<<(unsigned)tiles, RC_THREADS, 0, ctx->stream>>>(sp, n, maps, seedv, d_out);
-    FMK_LAUNCH_CHECK(ctx);
-    return FMK_OK;
 }
 
 }  // namespace

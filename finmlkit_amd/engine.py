@@ -483,6 +483,50 @@ class DeviceTrades:
         return self._hlc("fmk_adx_dev", "adx_core: high, low and close must have the same length.", high, low, close,
                          c_i64(int(length)))
 
+    # ------------------------------------------------------------------ running-sum indicators (csrc/fmk_runsum.hip)
+    def _pair(self, name: str, message: str, a: DeviceArray, b: DeviceArray, *args, dtype=np.float64) -> DeviceArray:
+        self._f64(name, a, b)
+        if a.n != b.n:
+            raise ValueError(message)
+        out = DeviceArray(self.ctx, a.n, dtype)
+        if a.n:
+            self.ctx.call(name, a.p, b.p, c_i64(a.n), *args, out.p)
+        return out
+
+    def bollinger_percent_b(self, y: DeviceArray, window: int, num_std: float = 2.0) -> DeviceArray:
+        """bollinger_percent_b (feature/core/volatility.py:289-338) of a resident float64 series."""
+        return self._series("fmk_bollinger_percent_b_dev", y, window, c_f64(float(num_std)),
+                            message="bollinger_percent_b: window must be at least 1.")
+
+    def vwap_distance(self, close: DeviceArray, volume: DeviceArray, n_periods: int, is_log: bool = False) -> DeviceArray:
+        """vwap_distance (feature/core/reversion.py:9-56) of two resident float64 series of one length."""
+        if int(n_periods) < 1:
+            raise ValueError("vwap_distance: n_periods must be at least 1.")
+        return self._pair("fmk_vwap_distance_dev", "vwap_distance: close and volume must have the same length.", close, volume,
+                          c_i64(int(n_periods)), C.c_int(bool(is_log)))
+
+    def parkinson_range(self, high: DeviceArray, low: DeviceArray) -> DeviceArray:
+        """parkinson_range (feature/core/volatility.py:341-349) of two resident float64 series of one length."""
+        return self._pair("fmk_parkinson_range_dev", "parkinson_range: high and low must have the same length.", high, low)
+
+    def flow_acceleration(self, volumes: DeviceArray, window: int, recent_periods: int) -> DeviceArray:
+        """comp_flow_acceleration (feature/core/volume.py:572-607) of a resident float64 series."""
+        if int(recent_periods) < 0:
+            raise ValueError("comp_flow_acceleration: recent_periods must not be negative.")
+        self._f64("fmk_flow_acceleration_dev", volumes)
+        out = DeviceArray(self.ctx, volumes.n, np.float64)
+        if volumes.n:
+            self.ctx.call("fmk_flow_acceleration_dev", volumes.p, c_i64(volumes.n), c_i64(int(window)), c_i64(int(recent_periods)),
+                          out.p)
+        return out
+
+    def vpin(self, volume_buy: DeviceArray, volume_sell: DeviceArray, window: int) -> DeviceArray:
+        """vpin (feature/core/volume.py:610-641) of two resident float64 series of one length -> a float32 array."""
+        if int(window) < 0:
+            raise ValueError("vpin: window must not be negative.")
+        return self._pair("fmk_vpin_dev", "vpin: volume_buy and volume_sell must have the same length.", volume_buy, volume_sell,
+                          c_i64(int(window)), dtype=np.float32)
+
     # ------------------------------------------------------------------ event sampling
     def cusum_filter(self, threshold, series: Optional[DeviceArray] = None) -> DeviceArray:
         """cusum_filter (sampling/filters.py:7-70) on a resident float64 series (default: the price column) -> int64 event indices

@@ -3,7 +3,7 @@
 The estimators that run on the raw tick frame are on the hot path: `ewmst`,
 `ewmst_mean0`, `ewms` and `realized_vol`; `rolling_variance_nb` and `variance_ratio_1_4_core` (the reference's
 microstructure-noise detector) run on a resident series too (csrc/fmk_rolling.hip), and so do `true_range` and `atr`
-(csrc/fmk_recur.hip).  The other bar-level indicators of that module (Bollinger, Parkinson) are out of scope.
+(csrc/fmk_recur.hip), `bollinger_percent_b` and `parkinson_range` (csrc/fmk_runsum.hip).
 """
 from __future__ import annotations
 
@@ -107,4 +107,34 @@ def atr(high: NDArray[np.float64], low: NDArray[np.float64], close: NDArray[np.f
     if len(h):
         _ffi.default_context().call("fmk_atr", ptr(h), ptr(lo), ptr(c), c_i64(len(h)), c_i64(int(window)), C.c_int(bool(ema_based)),
                                     C.c_int(bool(normalize)), ptr(out))
+    return out
+
+
+BOLLINGER_WINDOW_MESSAGE = "bollinger_percent_b: window must be at least 1."
+PARKINSON_MESSAGE = "parkinson_range: high and low must have the same length."
+
+
+def bollinger_percent_b(close: NDArray[np.float64], window: int, num_std: float) -> NDArray[np.float64]:
+    """Reference: finmlkit/feature/core/volatility.py:289-338: (close - lower) / (upper - lower) of the Bollinger bands mean -+
+    num_std * sd over `window`, from the reference's running sum and sum of squares (sum += close[i] - close[i-window]); NaN before
+    window - 1, where upper > lower is false, from a NaN of `close` on, everywhere when the series is shorter than the window
+    and for window 1.  `window < 1` raises ValueError.  A device-wide scan with the coefficient 1: bit for bit the reference on
+    exactly summable prices; otherwise the sum that enters a thread's 8 elements is added in another order, and as the variance
+    cancels the outputs agree within a few 2^-52 * sumsq / ((window - 1) * var).  Outside the contract:
+    infinite prices, and on prices that are not exactly summable a window whose elements are all equal (the reference's
+    NaN-or-number there is rounding noise)."""
+    if int(window) < 1:
+        raise ValueError(BOLLINGER_WINDOW_MESSAGE)
+    return series_call("fmk_bollinger_percent_b", close, window, c_f64(float(num_std)), message=BOLLINGER_WINDOW_MESSAGE)
+
+
+def parkinson_range(high: NDArray[np.float64], low: NDArray[np.float64]) -> NDArray[np.float64]:
+    """Reference: finmlkit/feature/core/volatility.py:341-349: log(high / low) ** 2 / (log(2.0) * 4.0) with the host's log, the
+    reference's bits: inf where low is 0, NaN where an input is NaN or the ratio negative.  Unequal lengths raise ValueError."""
+    h, lo = (np.ascontiguousarray(a, dtype=np.float64) for a in (high, low))
+    if not (h.ndim == lo.ndim == 1 and len(h) == len(lo)):
+        raise ValueError(PARKINSON_MESSAGE)
+    out = np.empty(len(h), np.float64)
+    if len(h):
+        _ffi.default_context().call("fmk_parkinson_range", ptr(h), ptr(lo), c_i64(len(h)), ptr(out))
     return out

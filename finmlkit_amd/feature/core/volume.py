@@ -5,6 +5,8 @@ The reference walks ragged `numba.typed.List`s of per-bar level arrays; here the
 CSR layout the footprint kernel produces (`FootprintData.level_offsets` + `.flat`) and one wave per bar
 aggregates its window in LDS (csrc/fmk_volprofile.hip).  Ragged lists are accepted too (concatenated
 once on the host).  Numba-typed semantics: float32 level sums in the reference's order, float64 scalars.
+
+`comp_flow_acceleration` and `vpin` (:572-641) run on resident series as prefix-sum scans (csrc/fmk_runsum.hip).
 """
 from __future__ import annotations
 
@@ -185,3 +187,43 @@ class VolumePro:
         sub = fp_data[adjusted_start:end]
         bars_sub = bars.loc[pd.to_datetime(sub.bar_timestamps, unit="ns")]
         return (sub.bar_timestamps,) + self.compute(bars_sub, sub)
+
+
+RECENT_MESSAGE = "comp_flow_acceleration: recent_periods must not be negative."
+VPIN_WINDOW_MESSAGE = "vpin: window must not be negative."
+VPIN_SHAPE_MESSAGE = "vpin: volume_buy and volume_sell must have the same length."
+
+
+def comp_flow_acceleration(volumes: NDArray[np.float64], window: int, recent_periods: int) -> NDArray[np.float64]:
+    """Reference: finmlkit/feature/core/volume.py:572-607: log((recent + 1e-12) / (past + 1e-12)) with the host's log, `recent` the
+    volume of the last `recent_periods` bars and `past` that of the window's other bars, both differences of the prefix sum S.
+    NaN before window - 1, and everywhere when the series is shorter than the window or recent_periods >= window (every
+    window < 1 included).  recent_periods 0 is valid; a negative one raises ValueError.  The prefix sum is a device-wide scan
+    with the coefficient 1: bit for bit the reference on exactly summable volumes, otherwise within a few units in the last place
+    of S.  Infinite volumes are outside the contract."""
+    if int(recent_periods) < 0:
+        raise ValueError(RECENT_MESSAGE)
+    v = np.ascontiguousarray(volumes, dtype=np.float64)
+    out = np.empty(len(v), np.float64)
+    if len(v):
+        _ffi.default_context().call("fmk_flow_acceleration", ptr(v), c_i64(len(v)), c_i64(int(window)), c_i64(int(recent_periods)),
+                                    ptr(out))
+    return out
+
+
+def vpin(volume_buy, volume_sell, window):
+    """Reference: finmlkit/feature/core/volume.py:610-641 -> float32: |buy - sell| summed over the window / (buy + sell) summed
+    over it, from prefix sums in which a bar with a NaN counts as 0.0; NaN before window - 1, where the window holds such a bar and
+    where the total is not above 1e-9.  The division is in float64 and is rounded to float32 once.  Window 0 gives NaN everywhere,
+    as the reference; a negative window and unequal lengths raise ValueError.  The prefix sums are a device-wide scan with the
+    coefficient 1: equal to the reference as float32, but for one float32 unit in the last place where the float64 quotient sits
+    on a rounding boundary.  Infinite volumes are outside the contract."""
+    if int(window) < 0:
+        raise ValueError(VPIN_WINDOW_MESSAGE)
+    b, s = (np.ascontiguousarray(a, dtype=np.float64) for a in (volume_buy, volume_sell))
+    if not (b.ndim == s.ndim == 1 and len(b) == len(s)):
+        raise ValueError(VPIN_SHAPE_MESSAGE)
+    out = np.empty(len(b), np.float32)
+    if len(b):
+        _ffi.default_context().call("fmk_vpin", ptr(b), ptr(s), c_i64(len(b)), c_i64(int(window)), ptr(out))
+    return out

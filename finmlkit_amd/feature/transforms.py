@@ -2,7 +2,9 @@
 `SMA`, `ZScore` and `VarianceRatio14` (reference transforms.py:549-574, :335-359, :867-897), the windowed order statistics
 `BurstRatio`, `ROC`, `PctChange` and `StochK` (reference transforms.py:362-385, :155-177, :180-203, :276-305), and the
 structural-break transform `CUSUMTest` (reference transforms.py:631-708), and the recursive indicators `EWMA`, `RSIWilder`, `ATR`
-and `ADX` (reference transforms.py:577-602, :206-273, :711-751, :991-1030).
+and `ADX` (reference transforms.py:577-602, :206-273, :711-751, :991-1030), and the running-sum indicators `BollingerPercentB`,
+`VWAPDistance`, `ParkinsonRange`, `FlowAcceleration` and `VPIN` (reference transforms.py:494-518, :388-418, :521-546, :605-628,
+:816-870).
 
 Counterparts of finmlkit/feature/transforms.py:89-117 (ReturnT), :308-332 (EWMST) and the
 pipeline part of finmlkit/feature/kit.py:Compose (:630-720), enough to run the QuickStart flow
@@ -25,7 +27,10 @@ from .core.ma import SPAN_MESSAGE, ewma, sma
 from .core.momentum import LENGTH_MESSAGE, PERIOD_MESSAGE, RSI_WINDOW_MESSAGE, roc, rsi_wilder, stoch_k
 from .core.trend import adx_core
 from .core.utils import PERIODS_MESSAGE, comp_burst_ratio, comp_lagged_returns, comp_zscore, pct_change
-from .core.volatility import atr, ewmst, realized_vol, variance_ratio_1_4_core
+from .core.reversion import vwap_distance
+from .core.volatility import (BOLLINGER_WINDOW_MESSAGE, atr, bollinger_percent_b, ewmst, parkinson_range, realized_vol,
+                              variance_ratio_1_4_core)
+from .core.volume import RECENT_MESSAGE, comp_flow_acceleration, vpin
 
 
 class SISOTransform:
@@ -261,6 +266,49 @@ class RSIWilder(_Rolling):
         return super()._dev(ts, y)
 
 
+class BollingerPercentB(SISOTransform):
+    """Bollinger %B (reference transforms.py:494-518).  Every backend is the kernel; the reference's `_pd` falls back to Numba."""
+
+    def __init__(self, window: int, num_std: float = 2., input_col: str = "close"):
+        super().__init__(input_col, f"bollb{window}")
+        self.window = window
+        self.num_std = num_std
+
+    def _hip(self, x):
+        res = bollinger_percent_b(np.asarray(self._prepare_input_nb(x), dtype=np.float64), self.window, self.num_std)
+        return self._prepare_output_nb(x.index, res)
+
+    def _dev(self, ts, y):
+        if int(self.window) < 1:
+            raise ValueError(BOLLINGER_WINDOW_MESSAGE)
+        out = DeviceArray(ts.ctx, y.n, np.float64)
+        if y.n:
+            ts.ctx.call("fmk_bollinger_percent_b_dev", y.p, c_i64(y.n), c_i64(int(self.window)), c_f64(float(self.num_std)), out.p)
+        return out
+
+
+class FlowAcceleration(SISOTransform):
+    """Flow acceleration (reference transforms.py:605-628).  Every backend is the kernel; the reference's `_pd` falls back to
+    Numba."""
+
+    def __init__(self, window: int, recent_periods, input_col: str = "volume"):
+        super().__init__(input_col, f"flowacc_{window}_{recent_periods}")
+        self.window = window
+        self.recent_periods = recent_periods
+
+    def _hip(self, x):
+        res = comp_flow_acceleration(np.asarray(self._prepare_input_nb(x), dtype=np.float64), self.window, self.recent_periods)
+        return self._prepare_output_nb(x.index, res)
+
+    def _dev(self, ts, y):
+        if int(self.recent_periods) < 0:
+            raise ValueError(RECENT_MESSAGE)
+        out = DeviceArray(ts.ctx, y.n, np.float64)
+        if y.n:
+            ts.ctx.call("fmk_flow_acceleration_dev", y.p, c_i64(y.n), c_i64(int(self.window)), c_i64(int(self.recent_periods)), out.p)
+        return out
+
+
 class _Lagged(SISOTransform):
     """An elementwise function of x[t] and x[t - periods] (csrc/fmk_order.hip)."""
     _host = None
@@ -403,6 +451,55 @@ class ADX(MISOTransform):
         cols = self._prepare_input_nb(x)
         high, low, close = (np.asarray(cols[c], dtype=np.float64) for c in self.requires[:3])
         return self._prepare_output_nb(x.index, adx_core(high, low, close, self.length))
+
+
+class VWAPDistance(MISOTransform):
+    """Distance of the price from the rolling VWAP (reference transforms.py:388-418); the columns are (close, volume).  Every
+    backend is the kernel; the reference's `_pd` falls back to Numba."""
+
+    def __init__(self, periods: int, is_log: bool = False, input_cols: str = None):
+        if input_cols is None:
+            input_cols = ["close", "volume"]
+        super().__init__(input_cols, f"vwapd{periods}")
+        self.periods = periods
+        self.is_log = is_log
+
+    def _hip(self, x):
+        cols = self._prepare_input_nb(x)
+        close, volume = (np.asarray(cols[c], dtype=np.float64) for c in self.requires[:2])
+        return self._prepare_output_nb(x.index, vwap_distance(close, volume, self.periods, self.is_log))
+
+
+class ParkinsonRange(MISOTransform):
+    """Parkinson's range estimator (reference transforms.py:521-546); the columns are (high, low).  Every backend is the kernel;
+    the reference's `_pd` falls back to Numba."""
+
+    def __init__(self, input_cols=None):
+        if input_cols is None:
+            input_cols = ["high", "low"]
+        super().__init__(input_cols, "parkrange")
+
+    def _hip(self, x):
+        cols = self._prepare_input_nb(x)
+        high, low = (np.asarray(cols[c], dtype=np.float64) for c in self.requires[:2])
+        return self._prepare_output_nb(x.index, parkinson_range(high, low))
+
+
+class VPIN(MISOTransform):
+    """Volume-synchronised probability of informed trading (reference transforms.py:816-870), float32; the columns are
+    (volume_buy, volume_sell).  Every backend is the kernel: the reference's `_pd` is a pandas arithmetic of its own (rolling sums
+    in float64 that let a NaN bar poison its windows only), its `_nb` the function this one restates."""
+
+    def __init__(self, window: int = 32, input_cols: list[str] = None):
+        if input_cols is None:
+            input_cols = ["volume_buy", "volume_sell"]
+        super().__init__(input_cols, f"vpin_{window}")
+        self.window = window
+
+    def _hip(self, x):
+        cols = self._prepare_input_nb(x)
+        buy, sell = (np.asarray(cols[c], dtype=np.float64) for c in self.requires[:2])
+        return self._prepare_output_nb(x.index, vpin(buy, sell, self.window))
 
 
 class SIMOTransform:

@@ -497,6 +497,44 @@ int fmk_adx_dev(fmk_ctx *ctx, const double *d_high, const double *d_low, const d
                 double *d_out);
 int fmk_adx(fmk_ctx *ctx, const double *high, const double *low, const double *close, int64_t n, int64_t length, double *out);
 
+/* ---- running-sum indicators: finmlkit/feature/core/volatility.py (bollinger_percent_b, parkinson_range), reversion.py
+ * (vwap_distance), volume.py (comp_flow_acceleration, vpin) on float64 series of n elements -> one array of n elements, float64 but
+ * for vpin's float32 (csrc/fmk_runsum.hip).
+ *   bollinger_percent_b: NaN before window - 1 and everywhere when n < window or window == 1.  sum and sum of squares of the first
+ *             window in index order, then sum += close[i] - close[i-window], sumsq += close[i]^2 - close[i-window]^2; mean = sum /
+ *             window, var = (sumsq - T) / (window - 1) with T = window * mean * mean at window - 1 and window * (mean * mean) after
+ *             it, sd = sqrt(var < 0 ? 0 : var); (close - lower) / (upper - lower) where upper > lower, NaN otherwise.
+ *   vwap_distance: NaN before n_periods - 1 and everywhere when n < n_periods.  wsum and vsum of the first window in index order,
+ *             then wsum += close[i] * volume[i] - close[i-w] * volume[i-w], vsum += volume[i] - volume[i-w].  Where vsum > 0:
+ *             close / (wsum / vsum) - 1.0, with is_log after the first window log(close / (wsum / vsum)); where it is not (a NaN
+ *             vsum included) the output before it, NaN when there is none.
+ *   flow_acceleration: NaN before window - 1 and everywhere when n < window or recent_periods >= window.  S the prefix sum of the
+ *             volumes; log(((S[i+1] - S[i+1-r]) + 1e-12) / ((S[i+1-r] - S[i+1-window]) + 1e-12)).
+ *   vpin:     prefix sums of buy, sell, |buy - sell| and of the bars with a NaN (which add 0.0 to the three sums).  Where i >= window
+ *             - 1, the window holds no NaN bar and its buy + sell total is > 1e-9: float32(|buy - sell| total / total), the division
+ *             in float64; NaN otherwise.  window 0: NaN everywhere.
+ *   parkinson_range: log(high / low)^2 / (log(2.0) * 4.0).  The reference's bits.
+ * log is the host's.  The four running sums are the scan of the recursive indicators with the coefficient 1: every step is the
+ * reference's own expression, but the sum that enters a thread's 8 elements is added in another order, so the outputs agree with the
+ * reference bit for bit on exactly summable inputs and to a few units in the last place of the largest running sum otherwise
+ * (measured: DESIGN.md section 7f); NaN positions, the outputs before the seed and which vwap_distance outputs are held are the
+ * reference's.  Not part of the contract: infinite inputs; on inputs that are not exactly summable, a Bollinger window whose elements
+ * are all equal and whether a window of all-zero volumes holds.  Memory: the context's scratch (one record per 2048 elements);
+ * from the context's pool vwap_distance takes n / 4 bytes, flow_acceleration n and vpin 4 n float64.
+ * FMK_E_ARG, checked before a device is touched and before any pointer is looked at: bollinger window < 1, n_periods < 1,
+ * recent_periods < 0, vpin window < 0, n >= 2^31. */
+int fmk_bollinger_percent_b_dev(fmk_ctx *ctx, const double *d_close, int64_t n, int64_t window, double num_std, double *d_out);
+int fmk_bollinger_percent_b(fmk_ctx *ctx, const double *close, int64_t n, int64_t window, double num_std, double *out);
+int fmk_vwap_distance_dev(fmk_ctx *ctx, const double *d_close, const double *d_volume, int64_t n, int64_t n_periods, int is_log,
+                          double *d_out);
+int fmk_vwap_distance(fmk_ctx *ctx, const double *close, const double *volume, int64_t n, int64_t n_periods, int is_log, double *out);
+int fmk_flow_acceleration_dev(fmk_ctx *ctx, const double *d_volumes, int64_t n, int64_t window, int64_t recent_periods, double *d_out);
+int fmk_flow_acceleration(fmk_ctx *ctx, const double *volumes, int64_t n, int64_t window, int64_t recent_periods, double *out);
+int fmk_vpin_dev(fmk_ctx *ctx, const double *d_volume_buy, const double *d_volume_sell, int64_t n, int64_t window, float *d_out);
+int fmk_vpin(fmk_ctx *ctx, const double *volume_buy, const double *volume_sell, int64_t n, int64_t window, float *out);
+int fmk_parkinson_range_dev(fmk_ctx *ctx, const double *d_high, const double *d_low, int64_t n, double *d_out);
+int fmk_parkinson_range(fmk_ctx *ctx, const double *high, const double *low, int64_t n, double *out);
+
 /* ---- labels and sample weights on the tick tape: finmlkit/label/tbm.py, label/weights.py ------------------------
  * triple_barrier (tbm.py:11-158) on the raw tape.  Per event: label (side labels -1 / +1; meta labels 0 / 1 when d_side is given),
  * index of the first barrier touch, the return there and the max return / barrier ratio.  Labels, touch indices, returns and ratios

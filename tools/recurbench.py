@@ -1,13 +1,16 @@
 #!/usr/bin/env python3
 """Times the recursive indicators (fmk_ewma_dev, fmk_rsi_wilder_dev, fmk_true_range_dev, fmk_atr_dev in both modes, fmk_adx_dev:
-csrc/fmk_recur.hip) on resident synthetic columns with the context's HIP-event timer, `fmk_ewms_dev` (the scan of
-csrc/fmk_ticklevel.hip) at the same sizes beside them as the yardstick, and prints one JSON line.
+csrc/fmk_recur.hip) and the running-sum indicators (fmk_bollinger_percent_b_dev, fmk_vwap_distance_dev, fmk_flow_acceleration_dev,
+fmk_vpin_dev, fmk_parkinson_range_dev: csrc/fmk_runsum.hip) on resident synthetic columns with the context's HIP-event timer,
+`fmk_ewms_dev` (the scan of csrc/fmk_ticklevel.hip) at the same sizes beside them as the yardstick, and prints one JSON line.
 
 Workloads: n = 1e7 and n = 1e8, window 14.  Every timed step (one function at one size: an untimed call, then REPS timed ones, the
 minimum counts) runs in a child process of its own under a time limit, so that a step that hangs ends alone; after a step that
 fails nothing more is started.  "bytes_per_element" is what the algorithm has to move: a scan reads its input series twice and writes
 once (ewma 2 x 8 + 8, rsi the same, atr and adx 2 x 24 + 8, adx also the dx series: written once, read twice, + 24), true_range and
-the SMA mode read three series and write one -> bytes per second, to hold against the HBM rate.
+the SMA mode read three series and write one; bollinger 2 x 8 + 8 (its lagged read is the same series), vwap_distance 2 x 16 + 8,
+flow_acceleration 2 x 8 + 8 for the prefix sum, which is read again, + 8 + 8, vpin 2 x 16 + 32 for four prefix sums, read again, + 32
++ 4, parkinson_range 16 + 8) -> bytes per second, to hold against the HBM rate.
 usage: recurbench.py [SCALE]        SCALE < 1 shrinks every n (a smoke run)
        recurbench.py --step NAME N  (internal) one step, prints its JSON"""
 import ctypes as C
@@ -31,6 +34,11 @@ STEPS = {
     "atr_sma": ("fmk_atr_dev", 3, 32),
     "atr_ema": ("fmk_atr_dev", 3, 56),
     "adx": ("fmk_adx_dev", 3, 80),
+    "bollinger_percent_b": ("fmk_bollinger_percent_b_dev", 1, 24),
+    "vwap_distance": ("fmk_vwap_distance_dev", 2, 40),
+    "flow_acceleration": ("fmk_flow_acceleration_dev", 1, 40),
+    "vpin": ("fmk_vpin_dev", 2, 100),
+    "parkinson_range": ("fmk_parkinson_range_dev", 2, 24),
 }
 
 
@@ -49,10 +57,12 @@ def step(name, n):
     low = DeviceArray.from_host(ctx, np.tile(host - 0.25, reps)[:n])
     high = DeviceArray.from_host(ctx, np.tile(host + 0.25, reps)[:n])
     out = DeviceArray(ctx, n, np.float64)
-    ins = (close.p,) if nin == 1 else (high.p, low.p, close.p)
+    # (two series: high and low stand for close and volume, for the buy and the sell volume, and for themselves)
+    ins = {1: (close.p,), 2: (high.p, low.p), 3: (high.p, low.p, close.p)}[nin]
     tail = {"ewms": (c_i64(WINDOW),), "ewma": (c_f64(float(WINDOW)),), "rsi_wilder": (c_i64(WINDOW),), "true_range": (),
             "atr_sma": (c_i64(WINDOW), C.c_int(0), C.c_int(0)), "atr_ema": (c_i64(WINDOW), C.c_int(1), C.c_int(0)),
-            "adx": (c_i64(WINDOW),)}[name]
+            "adx": (c_i64(WINDOW),), "bollinger_percent_b": (c_i64(WINDOW), c_f64(2.0)), "vwap_distance": (c_i64(WINDOW), C.c_int(1)),
+            "flow_acceleration": (c_i64(WINDOW), c_i64(5)), "vpin": (c_i64(WINDOW),), "parkinson_range": ()}[name]
 
     def call():
         ctx.call(entry, *ins, c_i64(n), *tail, out.p)
@@ -64,9 +74,10 @@ def step(name, n):
         call()
         ms.append(ctx.timer_stop())
     best = min(ms)
+    head = out.view(0, min(n, 50_000)).to_host()                     # (vpin writes float32 into the front of the buffer)
     print(json.dumps({"n": n, "window": WINDOW, "ms_min": best, "ms": ms, "bytes_per_element": bpe,
                       "bytes_per_s": bpe * n / (best * 1e-3), "ns_per_element": best * 1e6 / n,
-                      "checksum": float(np.nansum(out.view(0, min(n, 100_000)).to_host()))}))
+                      "checksum": float(np.nansum(head.view(np.float32) if name == "vpin" else head))}))
 
 
 def main():
