@@ -15,6 +15,9 @@
 
 #define VP_MAX_LEVELS 8192                  // widest window whose histogram lives in LDS
 #define VP_MAX_LEVELS_GLOBAL (1 << 24)      // wider windows: histogram in global scratch
+#define VP_NO_RANGE (1ull << 62)            // in place of the widest window: a window without a level range (a NaN low or high)
+#define VP_NO_RANGE_MESSAGE "a window holds a NaN low or high, or its lows / highs over price_tick are not finite: no level range " \
+                            "(the reference's int(round(nan)) raises here)"
 
 __device__ __forceinline__ int64_t vp_lower(const int64_t *a, int64_t n, int64_t key)
 {
@@ -46,11 +49,22 @@ __global__ __launch_bounds__(256) void k_vp_windows(const int64_t *__restrict__ 
         const int64_t e = vp_upper(ts, nb, end_ts);
         if (s == e) s = s - 1 > 0 ? s - 1 : 0;                   // volume.py:164-166
         double mn = INFINITY, mx = -INFINITY;
-        for (int64_t t = s; t < e; ++t) { mn = fmin(mn, lows[t]); mx = fmax(mx, highs[t]); }
-        const int64_t minl = (int64_t)rint(mn / tick), maxl = (int64_t)rint(mx / tick);   // int(round(x / price_tick)), half-even
+        bool nan = false;                                        // np.min / np.max hand a NaN on; fmin / fmax would skip it
+        for (int64_t t = s; t < e; ++t) {
+            const double lo = lows[t], hi = highs[t];
+            nan |= (lo != lo) | (hi != hi);
+            mn = fmin(mn, lo); mx = fmax(mx, hi);
+        }
+        const double qlo = mn / tick, qhi = mx / tick;
         int64_t *w = win + 4 * (i - first);
-        w[0] = s; w[1] = e; w[2] = minl; w[3] = maxl;
-        L = maxl - minl + 1;
+        if (nan || !(fabs(qlo) < 0x1p61) || !(fabs(qhi) < 0x1p61)) {             // no level range: the call is refused, nothing is sized by it
+            w[0] = s; w[1] = e; w[2] = 0; w[3] = -1;
+            atomicMax(max_levels, VP_NO_RANGE);
+        } else {
+            const int64_t minl = (int64_t)rint(qlo), maxl = (int64_t)rint(qhi);   // int(round(x / price_tick)), half-even
+            w[0] = s; w[1] = e; w[2] = minl; w[3] = maxl;
+            L = maxl - minl + 1;
+        }
     }
     // attempted only when it would raise the value: one same-address atomic per BAR serialises at ~10 ns each (8 ms for 8e5 bars)
     L = fmk_dpp_reduce(L, (int64_t)0, FmkOpMax());
@@ -253,6 +267,8 @@ extern "C" int fmk_volume_profile_rolling_dev(fmk_ctx *ctx, const int64_t *d_bar
     FMK_LAUNCH_CHECK(ctx);
     int64_t max_levels;
     FMK_TRY(fmk_read_back(ctx, &max_levels, d_max, 8));
+    if ((unsigned long long)max_levels >= VP_NO_RANGE)
+        return fmk_set_error(ctx, FMK_E_ARG, "volume_profile_rolling: " VP_NO_RANGE_MESSAGE);
     if (max_levels > VP_MAX_LEVELS_GLOBAL)
         return fmk_set_error(ctx, FMK_E_CAPACITY, "volume_profile_rolling: a window spans %lld price levels; this build "
                              "supports <= %d", (long long)max_levels, VP_MAX_LEVELS_GLOBAL);
@@ -395,7 +411,10 @@ extern "C" int fmk_aggregate_footprint(fmk_ctx *ctx, const int64_t *bar_ts, cons
     if (s == e) s = s - 1 > 0 ? s - 1 : 0;
     if (s >= e) return fmk_set_error(ctx, FMK_E_ARG, "zero-size array to reduction operation minimum which has no identity");   // np.min of an empty window
     double mn = INFINITY, mx = -INFINITY;
-    for (int64_t t = s; t < e; ++t) { mn = fmin(mn, lows[t]); mx = fmax(mx, highs[t]); }
+    bool nan = false;
+    for (int64_t t = s; t < e; ++t) { nan |= (lows[t] != lows[t]) | (highs[t] != highs[t]); mn = fmin(mn, lows[t]); mx = fmax(mx, highs[t]); }
+    if (nan || !(fabs(mn / price_tick) < 0x1p61) || !(fabs(mx / price_tick) < 0x1p61))
+        return fmk_set_error(ctx, FMK_E_ARG, "aggregate_footprint: " VP_NO_RANGE_MESSAGE);
     const int64_t minl = (int64_t)nearbyint(mn / price_tick), maxl = (int64_t)nearbyint(mx / price_tick);
     const int64_t L = maxl >= minl ? maxl - minl + 1 : 0;
     *min_level = (int32_t)minl;

@@ -35,7 +35,8 @@ def volume_profile_rolling_csr(ts: NDArray[np.int64], highs: NDArray[np.float64]
                                buy_volumes: NDArray[np.float32], sell_volumes: NDArray[np.float32],
                                window_size_sec: float, n_bins: Optional[int] = None, price_tick: float = None,
                                va_pct: float = 68.34) -> Tuple[NDArray, NDArray, NDArray, NDArray]:
-    """`volume_profile_rolling` on CSR footprints -> (poc, hva, lva int32 in tick units, share above POC float32)."""
+    """`volume_profile_rolling` on CSR footprints -> (poc, hva, lva int32 in tick units, share above POC float32).  A NaN low or
+    high in a window that is computed raises ValueError, as the reference's int(round(nan)) does (include/fmk.h)."""
     t = np.ascontiguousarray(ts, dtype=np.int64)
     hi = np.ascontiguousarray(highs, dtype=np.float64)
     lo = np.ascontiguousarray(lows, dtype=np.float64)

@@ -320,9 +320,14 @@ int fmk_realized_vol(fmk_ctx *ctx, const double *r, int64_t n, int64_t window, i
 /* volume_profile_rolling on CSR footprints (level_offsets[n_bars+1] + flat level arrays, the layout
  * fmk_comp_bar_footprints produces).  first_bar = searchsorted(bar_ts, bar_ts[0] + window_ns) (volume.py:432):
  * earlier bars keep 0.  n_bins < 0: no bucketing (n_bins=None).  Outputs: POC / HVA / LVA in tick units (int32) and
- * the share of volume above the POC (float32).  FMK_E_LEVEL: a level outside its window, or a single-level window
- * with bucketing (the reference raises); FMK_E_ZERODIV: n_bins == 0; FMK_E_CAPACITY: a window wider than 8192
- * levels. */
+ * the share of volume above the POC (float32).  FMK_E_LEVEL: a level outside its window (the reference raises IndexError above the
+ * range and folds a level below it onto the lowest one), or a single-level window with bucketing (refused here; the interpreted
+ * reference hands the one level back as its only bin -- both on record in tests/golden/vp_edges.json); FMK_E_ZERODIV: n_bins == 0; FMK_E_CAPACITY: a window wider than 1 << 24
+ * levels (up to 8192 the histogram is in LDS, above in global scratch).
+ * NaN rule: a NaN low or high in a window that is computed makes np.min / np.max NaN and the reference's int(round(nan)) raises
+ * ValueError; so does this entry, with FMK_E_ARG, for the whole call and before any histogram is sized -- also where a window's
+ * lows / highs over price_tick are infinite or beyond 2^61 (the reference: OverflowError, or a level no int32 holds).  A NaN in a bar
+ * that no computed window holds is not looked at.  fmk_aggregate_footprint follows the same rule for its one window. */
 int fmk_volume_profile_rolling_dev(fmk_ctx *ctx, const int64_t *d_bar_ts, const double *d_highs, const double *d_lows,
                                    const int64_t *d_level_offsets, const int32_t *d_price_levels,
                                    const float *d_buy_volumes, const float *d_sell_volumes, int64_t n_bars,

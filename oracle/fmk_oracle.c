@@ -1094,7 +1094,13 @@ int orc_volume_profile_rolling(const int64_t *ts, const double *highs, const dou
         int64_t s = orc_lower_i64(ts, nb, start_ts), e = orc_upper_i64(ts, nb, end_ts);
         if (s == e) s = s - 1 > 0 ? s - 1 : 0;
         double mn = lows[s], mx = highs[s];
-        for (int64_t t = s + 1; t < e; ++t) { if (lows[t] < mn) mn = lows[t]; if (highs[t] > mx) mx = highs[t]; }
+        int nan = 0;                                               /* np.min / np.max hand a NaN on: int(round(nan)) raises */
+        for (int64_t t = s; t < e; ++t) {
+            if (lows[t] != lows[t] || highs[t] != highs[t]) nan = 1;
+            if (lows[t] < mn) mn = lows[t];
+            if (highs[t] > mx) mx = highs[t];
+        }
+        if (nan || !(fabs(mn / tick) < 0x1p61) || !(fabs(mx / tick) < 0x1p61)) return ORC_E_ARG;
         int64_t minl = (int64_t)nearbyint(mn / tick), maxl = (int64_t)nearbyint(mx / tick);
         int64_t L = maxl - minl + 1;
         if (L < 1) return ORC_E_ARG;
