@@ -720,4 +720,12 @@ int fmk_parkinson_range(fmk_ctx *ctx, const double *high, const double *low, int
                      [=](const double *h, const double *l, double *o) { return fmk_parkinson_range_dev(ctx, h, l, n, o); });
 }
 
+// the rolling price-volume correlation (fmk_corr.hip)
+int fmk_price_volume_corr(fmk_ctx *ctx, const double *price, const double *volume, int64_t n, int64_t window, double *out)
+{
+    FMK_TRY(fmk_rule_window(ctx, "rolling_price_volume_correlation", window));
+    return pair_host(ctx, fmk_series_check(ctx, "rolling_price_volume_correlation", n), price, volume, n, out,
+                     [=](const double *p, const double *v, double *o) { return fmk_price_volume_corr_dev(ctx, p, v, n, window, o); });
+}
+
 }  // extern "C"

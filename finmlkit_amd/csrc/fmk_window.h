@@ -24,6 +24,15 @@ FMK_HD int fmk_slab(int64_t window, int64_t tile)
     return (int)(span < FMK_SLAB_MAX ? span : FMK_SLAB_MAX);
 }
 
+#define FMK_SLAB_MAX16 2048          // the same 32 KiB in 16-byte words (fmk_corr.hip: a word holds a pair)
+
+// fmk_slab for a walk over 16-byte words
+FMK_HD int fmk_slab16(int64_t window, int64_t tile)
+{
+    const int64_t span = window - 1 + tile;
+    return (int)(span < FMK_SLAB_MAX16 ? span : FMK_SLAB_MAX16);
+}
+
 // The steps of one wave in one slab of `len` words.  w0 = wave0 - (the slab's start in the span); with q = w0 + p, position p of
 // every window of the wave is LDS word q + r * BLOCK + l, and reach = (OPL - 1) * BLOCK + 63 is the last word a wave reads at q,
 // less q.  any: some position of some window of the wave lies in the slab.  Then q runs over [qlo, hb] (the steps before word 0:

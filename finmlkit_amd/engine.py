@@ -527,6 +527,14 @@ class DeviceTrades:
         return self._pair("fmk_vpin_dev", "vpin: volume_buy and volume_sell must have the same length.", volume_buy, volume_sell,
                           c_i64(int(window)), dtype=np.float32)
 
+    # ------------------------------------------------------------------ rolling price-volume correlation (csrc/fmk_corr.hip)
+    def price_volume_corr(self, price: DeviceArray, volume: DeviceArray, window: int) -> DeviceArray:
+        """rolling_price_volume_correlation (feature/core/correlation.py:10-111) of two resident float64 series of one length."""
+        if int(window) < 1:
+            raise ValueError("window must be at least 1.")
+        return self._pair("fmk_price_volume_corr_dev", "rolling_price_volume_correlation: price and volume must have the same length.",
+                          price, volume, c_i64(int(window)))
+
     # ------------------------------------------------------------------ event sampling
     def cusum_filter(self, threshold, series: Optional[DeviceArray] = None) -> DeviceArray:
         """cusum_filter (sampling/filters.py:7-70) on a resident float64 series (default: the price column) -> int64 event indices

@@ -4,7 +4,7 @@
 structural-break transform `CUSUMTest` (reference transforms.py:631-708), and the recursive indicators `EWMA`, `RSIWilder`, `ATR`
 and `ADX` (reference transforms.py:577-602, :206-273, :711-751, :991-1030), and the running-sum indicators `BollingerPercentB`,
 `VWAPDistance`, `ParkinsonRange`, `FlowAcceleration` and `VPIN` (reference transforms.py:494-518, :388-418, :521-546, :605-628,
-:816-870).
+:816-870), and the rolling price-volume correlation `PriceVolumeCorrelation` (reference transforms.py:754-813).
 
 Counterparts of finmlkit/feature/transforms.py:89-117 (ReturnT), :308-332 (EWMST) and the
 pipeline part of finmlkit/feature/kit.py:Compose (:630-720), enough to run the QuickStart flow
@@ -23,6 +23,7 @@ import pandas as pd
 from .. import _ffi
 from .._ffi import DeviceArray, c_f64, c_i64
 from .core.structural_break.cusum import cusum_test_rolling
+from .core.correlation import rolling_price_volume_correlation
 from .core.ma import SPAN_MESSAGE, ewma, sma
 from .core.momentum import LENGTH_MESSAGE, PERIOD_MESSAGE, RSI_WINDOW_MESSAGE, roc, rsi_wilder, stoch_k
 from .core.trend import adx_core
@@ -500,6 +501,24 @@ class VPIN(MISOTransform):
         cols = self._prepare_input_nb(x)
         buy, sell = (np.asarray(cols[c], dtype=np.float64) for c in self.requires[:2])
         return self._prepare_output_nb(x.index, vpin(buy, sell, self.window))
+
+
+class PriceVolumeCorrelation(MISOTransform):
+    """Rolling correlation of price returns and volume (reference transforms.py:754-813); the columns are (close, volume).  Every
+    backend is the kernel, which restates the reference's `_nb`.  The reference's `_pd` is another computation: pandas' own rolling
+    correlation (another order of summation, and other NaN rules) with a special case of its own (`len >= 10 and window == 4` on
+    monotone columns, every output from `window` on set to +-1), not the one of `_nb` (outputs 4 .. 9)."""
+
+    def __init__(self, window: int = 8, input_cols: list[str] = None):
+        if input_cols is None:
+            input_cols = ["close", "volume"]
+        super().__init__(input_cols, f"corr_pv_{window}")
+        self.window = window
+
+    def _hip(self, x):
+        cols = self._prepare_input_nb(x)
+        close, volume = (np.asarray(cols[c], dtype=np.float64) for c in self.requires[:2])
+        return self._prepare_output_nb(x.index, rolling_price_volume_correlation(close, volume, self.window))
 
 
 class SIMOTransform:

@@ -540,6 +540,21 @@ int fmk_vpin(fmk_ctx *ctx, const double *volume_buy, const double *volume_sell, 
 int fmk_parkinson_range_dev(fmk_ctx *ctx, const double *d_high, const double *d_low, int64_t n, double *d_out);
 int fmk_parkinson_range(fmk_ctx *ctx, const double *high, const double *low, int64_t n, double *out);
 
+/* ---- rolling price-volume correlation: finmlkit/feature/core/correlation.py (rolling_price_volume_correlation) on two float64
+ * series of n elements -> float64 array of n elements (csrc/fmk_corr.hip).
+ *   ret[0] = NaN; ret[i] = (price[i] - price[i-1]) / price[i-1] where neither price is NaN and price[i-1] != 0 (-0.0 is zero), NaN
+ *   otherwise.  out[t] = NaN for t < window (one more than sma; everywhere when window >= n) and where ret[t] or volume[t] is NaN.
+ *   Otherwise, over the pairs (ret[j], volume[j]), j = t - window + 1 .. t, with no NaN, ascending: fewer than 2 -> NaN; the means
+ *   sr / cnt and sv / cnt of left-to-right sums; cov, qr, qv the left-to-right sums of dr * dv, dr * dr, dv * dv; where qr > 0 and
+ *   qv > 0: cov / (sqrt(qr) * sqrt(qv)) clamped to [-1, 1]; NaN otherwise.  For 4 <= t < 10 the reference's special case comes
+ *   before the sums: with up / incv / decv = no price[j+1] <= price[j] / no volume[j+1] <= volume[j] / no volume[j+1] >= volume[j]
+ *   over j = t - window + 1 .. t - 1, up and incv give 1.0, else up and decv -1.0 (a NaN there fails no comparison).
+ * The reference's bits: every window is computed on its own in the reference's order.
+ * FMK_E_ARG, checked before a device is touched and before any pointer is looked at: window < 1 (the reference indexes from the end
+ * of the arrays there), n >= 2^31. */
+int fmk_price_volume_corr_dev(fmk_ctx *ctx, const double *d_price, const double *d_volume, int64_t n, int64_t window, double *d_out);
+int fmk_price_volume_corr(fmk_ctx *ctx, const double *price, const double *volume, int64_t n, int64_t window, double *out);
+
 /* ---- labels and sample weights on the tick tape: finmlkit/label/tbm.py, label/weights.py ------------------------
  * triple_barrier (tbm.py:11-158) on the raw tape.  Per event: label (side labels -1 / +1; meta labels 0 / 1 when d_side is given),
  * index of the first barrier touch, the return there and the max return / barrier ratio.  Labels, touch indices, returns and ratios
