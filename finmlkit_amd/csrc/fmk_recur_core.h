@@ -229,7 +229,9 @@ __global__ __launch_bounds__(RC_THREADS) void k_rc_aggscan(RcMap<K> *maps, int64
 
 // Two optional members of a specification (fmk_runsum.hip).  NOUT > 1: emit(s, in, j, r) gives NOUT values per element, series c of
 // the output lies at out + c * n.  tile_end(in, n): called by every thread of the workgroup after its elements are stored (it may
-// use barriers), for what a later launch needs to know about the tile.
+// use barriers), for what a later launch needs to know about the tile.  `in` is the thread's own S::In, the one load() filled and
+// every emit() of the thread was handed, and the core does not read it: an emit() that takes it as `In &` may leave there, per
+// element, what is not a float64 series (RsPrefix's 4-byte counts), and tile_end() stores it, checking i < n itself as rc_store8 does.
 template <class S, class = void> struct RcNout { static constexpr int N = 1; };
 template <class S> struct RcNout<S, decltype((void)S::NOUT)> { static constexpr int N = S::NOUT; };
 template <class S, class = void> struct RcTileEnd { static constexpr bool has = false; };

@@ -7,10 +7,16 @@
 //   bollinger_percent_b  K = 2  sum += c[i] - c[i-w], sumsq += c[i]^2 - c[i-w]^2, seeded at w - 1 by the in-order sums
 //   vwap_distance        K = 2  wsum += c[i] v[i] - c[i-w] v[i-w], vsum += v[i] - v[i-w], seeded at w - 1; where vsum > 0 is false the
 //                               output is the one before it: a launch of its own (k_rs_hold) after the scan
-//   comp_flow_accel.     K = 1  the prefix sum S[i+1] as a scratch series, then an elementwise kernel on its differences
-//   vpin                 K = 4  the prefix sums of buy, sell, |buy - sell| and the NaN count (a float64 channel: counts are exact
-//                               there) as four scratch series, then an elementwise kernel that writes float32
+//   comp_flow_accel.     K = 2  the prefix sum S[i+1] and the count of bars that are not zero (4 bytes each) as two scratch series,
+//                               then an elementwise kernel on their differences
+//   vpin                 K = 7  the prefix sums of buy, sell and |buy - sell|, the counts of their terms that are not zero and the
+//                               NaN count (float64 channels: counts are exact there) as five scratch series, the counts two to a
+//                               series, then an elementwise kernel that writes float32
 //   parkinson_range             elementwise
+// Zero-volume bars: the reference differences sequential prefix sums, and adding 0.0 changes no bit of one, so its sum over a window
+// part whose terms are all 0.0 is exactly 0.0 and its outputs there are log(1e-12 / (past + 1e-12)), log((recent + 1e-12) / 1e-12)
+// and vpin's NaN.  Two prefix sums of this scan may differ in their last bits across a thread's edge although nothing but zeros
+// lies between them, so the elementwise kernels take 0.0 where the window's count of non-zero terms is 0 (rs_window).
 // No workgroup waits for another: every cross-tile dependence is a launch boundary.  log is the host's (fmk_log.h).  Outside the
 // contract: infinite inputs to the four scans (0 * inf in the composed maps is not inf).
 #include <math.h>
@@ -180,30 +186,80 @@ __global__ __launch_bounds__(RC_THREADS) void k_rs_hold(double *out, const RsTil
     }
 }
 
-// the prefix sum of comp_flow_acceleration (volume.py:596-600): out[i] = S[i + 1]
+// Two exact counts below 2^31 in one 8-byte element of a scratch series: a count is a float64 channel of the scan (sums of 1.0 are
+// exact in any order); its prefix is stored as an integer beside another one, so that two counts cost one series.
+__device__ __forceinline__ double rs_pack(double hi, double lo)
+{
+    return __longlong_as_double((long long)hi << 32 | (long long)lo);
+}
+__device__ __forceinline__ int64_t rs_hi(double p) { return (int64_t)(__double_as_longlong(p) >> 32); }
+__device__ __forceinline__ int64_t rs_lo(double p) { return (int64_t)(__double_as_longlong(p) & 0xFFFFFFFFll); }
+
+typedef int rs_i4 __attribute__((ext_vector_type(4), aligned(8)));             // as rc_d2: the counts lie behind n float64
+
+// the prefix sum of comp_flow_acceleration (volume.py:596-600): out[i] = S[i + 1], and beside it cnt[i], the number of bars up to
+// i that are not zero (below 2^31: 4 bytes each, written by tile_end).  Adding 0.0 leaves the reference's S as it is in every bit,
+// so a window part of zero bars has a sum of exactly 0.0 there; here S[i + 1] and S[i] may come from different orders of addition,
+// and the count says what the difference is.
 struct RsPrefix {
-    static constexpr int K = 1;
+    static constexpr int K = 2;
     const double *v;
+    int32_t *cnt;
     double a;                        // 1.0
     int64_t seed;                    // 0
-    struct In { double v[RC_ITEMS]; };
-    __device__ __forceinline__ void load(int64_t i0, int64_t n, bool whole, In &in) const { rc_load8(v, i0, n, whole, in.v); }
-    __device__ __forceinline__ void x(const In &in, int j, int64_t, double (&x)[K]) const { x[0] = in.v[j]; }
+    struct In { double v[RC_ITEMS]; int64_t i0; int32_t c[RC_ITEMS]; };          // c: the counts, from emit to tile_end
+    __device__ __forceinline__ static void bar(double v, double (&x)[K])
+    {
+        x[0] = v;
+        x[1] = v != 0.0 ? 1.0 : 0.0;                                 // (a NaN counts; what decides behind one is rs_window)
+    }
+    __device__ __forceinline__ void load(int64_t i0, int64_t n, bool whole, In &in) const
+    {
+        rc_load8(v, i0, n, whole, in.v);
+        in.i0 = i0;
+    }
+    __device__ __forceinline__ void x(const In &in, int j, int64_t, double (&x)[K]) const { bar(in.v[j], x); }
     __device__ __forceinline__ double lin(double x) const { return x; }
     __device__ __forceinline__ double step(double s, double x) const { return s + x; }
-    __device__ __forceinline__ double emit(const double (&s)[K], const In &, int) const { return s[0]; }
+    __device__ __forceinline__ double emit(const double (&s)[K], In &in, int j) const
+    {
+        in.c[j] = (int32_t)s[1];
+        return s[0];
+    }
     __device__ __forceinline__ double before() const { return NAN; }
     __device__ __forceinline__ int64_t seed_lo() const { return 0; }
     __device__ __forceinline__ int64_t seed_hi() const { return 0; }
-    __device__ __forceinline__ void term(int64_t i, double (&t)[K]) const { t[0] = v[i]; }
-    __device__ __forceinline__ void acc(double (&s)[K], int64_t &, const double (&t)[K]) const { s[0] += t[0]; }   // S[0] = 0.0
+    __device__ __forceinline__ void term(int64_t i, double (&t)[K]) const { bar(v[i], t); }
+    __device__ __forceinline__ void acc(double (&s)[K], int64_t &, const double (&t)[K]) const { s[0] += t[0]; s[1] += t[1]; }   // S[0] = 0.0
     __device__ __forceinline__ void fin(double (&)[K], int64_t) const {}
+    __device__ __forceinline__ void tile_end(const In &in, int64_t n) const
+    {
+        if (rc_whole(blockIdx.x, n)) {
+            rs_i4 *q = (rs_i4 *)(cnt + in.i0);
+#pragma unroll
+            for (int k = 0; k < RC_ITEMS / 4; ++k) {
+                rs_i4 t;
+                t.x = in.c[4 * k];
+                t.y = in.c[4 * k + 1];
+                t.z = in.c[4 * k + 2];
+                t.w = in.c[4 * k + 3];
+                q[k] = t;
+            }
+        } else {
+#pragma unroll
+            for (int k = 0; k < RC_ITEMS; ++k)
+                if (in.i0 + k < n) cnt[in.i0 + k] = in.c[k];
+        }
+    }
 };
 
-// the four prefix sums of vpin (volume.py:616-632): series c of the output is the sum c at i + 1
+// the prefix sums of vpin (volume.py:616-632): series 0 to 2 of the output are the sums of buy, sell and |buy - sell| at i + 1,
+// series 3 the counts of buy and of sell terms that are not zero, series 4 those of |buy - sell| terms that are not zero and of
+// bars with a NaN (rs_pack).  The counts are what the window differences are decided by: a sum over terms that are all 0.0 is
+// exactly 0.0 in the reference, and a bar with a NaN in the window gives NaN.
 struct RsVpin {
-    static constexpr int K = 4;
-    static constexpr int NOUT = 4;
+    static constexpr int K = 7;
+    static constexpr int NOUT = 5;
     const double *b, *s;
     double a;                        // 1.0
     int64_t seed;                    // 0
@@ -214,7 +270,10 @@ struct RsVpin {
         x[0] = nan ? 0.0 : vb;
         x[1] = nan ? 0.0 : vs;
         x[2] = nan ? 0.0 : fabs(vb - vs);
-        x[3] = nan ? 1.0 : 0.0;
+        x[3] = x[0] != 0.0 ? 1.0 : 0.0;
+        x[4] = x[1] != 0.0 ? 1.0 : 0.0;
+        x[5] = x[2] != 0.0 ? 1.0 : 0.0;
+        x[6] = nan ? 1.0 : 0.0;
     }
     __device__ __forceinline__ void load(int64_t i0, int64_t n, bool whole, In &in) const
     {
@@ -226,8 +285,11 @@ struct RsVpin {
     __device__ __forceinline__ double step(double st, double x) const { return st + x; }
     __device__ __forceinline__ void emit(const double (&st)[K], const In &, int, double (&r)[NOUT]) const
     {
-#pragma unroll
-        for (int k = 0; k < K; ++k) r[k] = st[k];
+        r[0] = st[0];
+        r[1] = st[1];
+        r[2] = st[2];
+        r[3] = rs_pack(st[3], st[4]);
+        r[4] = rs_pack(st[5], st[6]);
     }
     __device__ __forceinline__ double before() const { return NAN; }
     __device__ __forceinline__ int64_t seed_lo() const { return 0; }
@@ -244,28 +306,46 @@ struct RsVpin {
 // S[k] of a prefix sum stored as q[i] = S[i + 1]
 __device__ __forceinline__ double rs_prefix(const double *__restrict__ q, int64_t k) { return k > 0 ? q[k - 1] : 0.0; }
 
-// comp_flow_acceleration (volume.py:602-605); 0 <= recent < window <= n
-__global__ __launch_bounds__(256) void k_flow_acc(const double *__restrict__ q, int64_t n, int64_t window, int64_t recent,
-                                                  double *__restrict__ out)
+// a - b of a prefix sum where `terms` of the elements between them are not zero: exactly 0.0 where none is, as long as the prefix
+// sum is a number.  Behind a NaN or an infinity in the series every S of the reference is NaN or infinite for good, and so is every
+// difference of two of them, over zero bars as well (NaN - NaN): there the plain difference is the reference's.
+__device__ __forceinline__ double rs_window(double a, double b, int64_t terms)
+{
+    return terms != 0 || !__builtin_isfinite(a) ? a - b : 0.0;
+}
+
+// the count that goes with S[k]
+__device__ __forceinline__ int64_t rs_count(const int32_t *__restrict__ c, int64_t k) { return k > 0 ? c[k - 1] : 0; }
+
+// comp_flow_acceleration (volume.py:602-605); 0 <= recent < window <= n; q, qc: the prefix sum and the count of RsPrefix
+__global__ __launch_bounds__(256) void k_flow_acc(const double *__restrict__ q, const int32_t *__restrict__ qc, int64_t n, int64_t window,
+                                                  int64_t recent, double *__restrict__ out)
 {
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
         if (i < window - 1) { out[i] = NAN; continue; }
         const double mid = rs_prefix(q, i + 1 - recent);
-        const double recent_sum = q[i] - mid, past_sum = mid - rs_prefix(q, i + 1 - window);
+        const int64_t cmid = rs_count(qc, i + 1 - recent);
+        const double recent_sum = rs_window(q[i], mid, qc[i] - cmid);
+        const double past_sum = rs_window(mid, rs_prefix(q, i + 1 - window), cmid - rs_count(qc, i + 1 - window));
         out[i] = fmk_log_host((recent_sum + 1e-12) / (past_sum + 1e-12));
     }
 }
 
-// vpin (volume.py:634-640); 1 <= window <= n; q: the four prefix sums, n elements each
+// vpin (volume.py:634-640); 1 <= window <= n; q: the five series of RsVpin, n elements each
 __global__ __launch_bounds__(256) void k_vpin(const double *__restrict__ q, int64_t n, int64_t window, float *__restrict__ out)
 {
-    const double *qb = q, *qs = q + n, *qa = q + 2 * n, *qn = q + 3 * n;
+    const double *qb = q, *qs = q + n, *qa = q + 2 * n, *qbs = q + 3 * n, *qan = q + 4 * n;
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
         float o = NAN;
         const int64_t k = i + 1 - window;
-        if (k >= 0 && qn[i] - rs_prefix(qn, k) == 0.0) {
-            const double tot = (qb[i] - rs_prefix(qb, k)) + (qs[i] - rs_prefix(qs, k));
-            if (tot > 1e-9) o = (float)((qa[i] - rs_prefix(qa, k)) / tot);
+        if (k >= 0) {
+            const double an1 = qan[i], an0 = rs_prefix(qan, k);
+            if (rs_lo(an1) - rs_lo(an0) == 0) {
+                const double bs1 = qbs[i], bs0 = rs_prefix(qbs, k);
+                const double tot = rs_window(qb[i], rs_prefix(qb, k), rs_hi(bs1) - rs_hi(bs0)) +
+                                   rs_window(qs[i], rs_prefix(qs, k), rs_lo(bs1) - rs_lo(bs0));
+                if (tot > 1e-9) o = (float)(rs_window(qa[i], rs_prefix(qa, k), rs_hi(an1) - rs_hi(an0)) / tot);
+            }
         }
         out[i] = o;
     }
@@ -344,14 +424,15 @@ extern "C" int fmk_flow_acceleration_dev(fmk_ctx *ctx, const double *d_volumes, 
     if (n == 0) return FMK_OK;
     if (n < window || recent_periods >= window) return rc_fill(ctx, d_out, n, NAN);
     void *work;
-    FMK_TRY(fmk_alloc(ctx, (size_t)n * sizeof(double), &work));
+    FMK_TRY(fmk_alloc(ctx, (size_t)n * (sizeof(double) + sizeof(int32_t)), &work));
     RsPrefix sp;
     sp.v = d_volumes;
+    sp.cnt = (int32_t *)((double *)work + n);
     sp.a = 1.0;
     sp.seed = 0;
     int rc = rc_scan(ctx, sp, n, (double *)work, NAN);
     if (rc == FMK_OK) {
-        k_flow_acc<<<fmk_grid_blocks(ctx, n), 256, 0, ctx->stream>>>((const double *)work, n, window, recent_periods, d_out);
+        k_flow_acc<<<fmk_grid_blocks(ctx, n), 256, 0, ctx->stream>>>((const double *)work, sp.cnt, n, window, recent_periods, d_out);
         if (hipGetLastError() != hipSuccess) rc = fmk_set_error(ctx, FMK_E_HIP, "comp_flow_acceleration: the launch failed");
     }
     const int frc = fmk_free(ctx, work);

@@ -10,6 +10,7 @@ expression; `** 2` is a product.
   comp_flow_accel.     negative recent_periods refused; NaN everywhere when n < window or recent_periods >= window
   vpin                 negative window refused; float32; a bar with a NaN adds 0.0 to the sums and 1 to the count
   parkinson_range      log(high / low) ** 2 / (log(2.0) * 4.0)
+The generators are in integer arithmetic and seeded; zero_lot_volumes has zero-volume bars among volumes that are not exactly summable.
 `sums=True` returns the internal sums beside the output (for the condition number of the Bollinger variance).
 Reads nothing outside the repository."""
 import math
@@ -53,8 +54,32 @@ def lot_volumes(n, seed):
     return np.random.default_rng(seed).integers(1, 5001, n) / 100.0
 
 
+def zero_lot_volumes(n, seed, runs=(), share=0.3):
+    """Volumes 1.01 .. 51.00 on a 0.01 grid (not exactly summable) with zero-volume bars: a `share` of the bars at seeded places and
+    every bar of each (start, length) of `runs` is 0.0.  The floor of 1.01 keeps every window sum that is not zero far above the
+    rounding noise of a prefix sum (about 3e-11 at these totals)."""
+    v = np.random.default_rng(seed).integers(1, 5001, n) / 100.0 + 1.0
+    v[np.random.default_rng(seed + 1000).random(n) < share] = 0.0
+    for start, length in runs:
+        v[start:start + length] = 0.0
+    return v
+
+
+def zero_lot_kilo(n, seed, runs=(), share=0.3):
+    """zero_lot_volumes x 1024 (exact): totals of 1e8, where one unit in the last place of a prefix sum exceeds vpin's 1e-9."""
+    return zero_lot_volumes(n, seed, runs, share) * 1024.0
+
+
+def zero_lot_nan(n, seed, runs, at):
+    """zero_lot_volumes with a NaN in element `at`: every prefix sum behind it is NaN, over zero bars as well."""
+    v = zero_lot_volumes(n, seed, runs)
+    v[at] = NAN
+    return v
+
+
 GENERATORS = {
     "grid_walk": grid_walk, "grid64_walk": grid64_walk, "int_volumes": int_volumes, "lot_volumes": lot_volumes,
+    "zero_lot_volumes": zero_lot_volumes, "zero_lot_kilo": zero_lot_kilo, "zero_lot_nan": zero_lot_nan,
     "hlc_high": lambda *a: hlc_walk(*a)[0], "hlc_low": lambda *a: hlc_walk(*a)[1], "hlc_close": lambda *a: hlc_walk(*a)[2],
 }
 
@@ -194,6 +219,15 @@ def flat_windows(close, window):
         view = np.lib.stride_tricks.sliding_window_view(c, window)
         flat[window - 1:] = (view == view[:, :1]).all(axis=1)
     return flat
+
+
+def zero_windows(v, window):
+    """Where the window that ends at i holds zeros only (the twin of flat_windows); False before window - 1."""
+    v = np.asarray(v, np.float64)
+    zero = np.zeros(len(v), bool)
+    if window >= 1 and len(v) >= window:
+        zero[window - 1:] = (np.lib.stride_tricks.sliding_window_view(v, window) == 0.0).all(axis=1)
+    return zero
 
 
 NAMES = {"boll": "bollinger_percent_b", "vwap": "vwap_distance", "flow": "comp_flow_acceleration", "vpin": "vpin",

@@ -27,6 +27,11 @@ _HASHED = {}
 ENTRIES = ("fmk_bollinger_percent_b", "fmk_vwap_distance", "fmk_flow_acceleration", "fmk_vpin", "fmk_parkinson_range")
 EXACT_GENERATORS = {"grid64_walk", "int_volumes"}      # exactly summable: the order of addition cannot matter
 FLAT_SHARE = 0.02
+ZERO_SHARE = 0.01                      # all-zero vwap windows of volumes that are not exactly summable: at most this share of a case
+TILE = 2048                            # elements per workgroup of the scan (csrc/fmk_recur_core.h: RC_TILE)
+# zero-volume runs in a thread's first elements, up to and over the first tile edge, inside a tile, over the second edge, to the third
+MANY = [[3, 30], [TILE - 21, 21], [TILE + 500, 19], [2 * TILE - 1, 22], [3 * TILE - 10, 60]]
+FLOW_ARGS = ((1, 0), (2, 1), (3, 0), (20, 1), (20, 5), (100, 99))
 
 
 def product():
@@ -109,6 +114,13 @@ def test_fixture_holds_what_it_should():
     out = expected("nan.vpin_buy_after_w20")
     assert np.isnan(out[300:320]).all() and np.isfinite(out[320:]).all() and np.isfinite(out[19:300]).all()
     assert MANIFEST["zeros.vpin_w20"]["nan"] == 19 + 21 and MANIFEST["window0.vpin"]["nan"] == 40
+    # zero bars among volumes that are not exactly summable: flow has a number at every window, vpin NaN on the 41 all-zero ones
+    assert MANIFEST["zerolot.flow_w20_r1"]["nan"] == MANIFEST["zerolot.flow_w20_r5"]["nan"] == 19
+    assert MANIFEST["zerolot.vpin_kilo_w20"]["nan"] == 19 + 41 and MANIFEST["zerolot.vwap_log_w20"]["zero_windows"] == 42
+    assert not any(exactly_summable(k) for k in OK_CASES if k.startswith("zerolot."))
+    # a NaN in element 5 in front of them: NaN from there on, the windows of zero bars included
+    assert MANIFEST["zerolot.flow_nan_w1_r0"]["nan"] == 2100 - 5 and np.isnan(expected("zerolot.flow_nan_w1_r0")[5:]).all()
+    assert MANIFEST["zerolot.flow_nan_w20_r1"]["finite"] == MANIFEST["zerolot.flow_nan_w20_r5"]["finite"] == 0
     # parkinson: inf at a zero low and at a zero high, NaN at a negative ratio and at 0 / 0
     out = expected("edge.park")
     assert np.isinf(out[3]) and np.isnan(out[4]) and np.isinf(out[5]) and np.isnan(out[6]) and np.isfinite(out[7:]).all()
@@ -148,6 +160,100 @@ def test_exactly_summable_generators_are_exact():
     c, v = H.grid64_walk(6444, 872), H.int_volumes(6444, 873, [[700, 100]])
     assert (c * 64 == np.round(c * 64)).all() and (v == np.round(v)).all() and v.max() < 64 and (v[700:800] == 0).all()
     assert float(np.sum(c * c * 4096.0)) < 2.0 ** 52 and c.max() < 1024
+
+
+def test_zero_lot_volumes_are_what_the_device_tests_take_them_for():
+    v = H.zero_lot_volumes(6444, 818, MANY)
+    plain = H.zero_lot_volumes(6444, 818, share=0)
+    assert np.array_equal(plain, H.lot_volumes(6444, 818) + 1.0) and plain.min() >= 1.01 and plain.max() <= 51.0
+    assert ((v == 0.0) | (v == plain)).all() and 0.28 < (v == 0.0).mean() < 0.33
+    assert all((v[s:s + m] == 0.0).all() for s, m in MANY)
+    assert not (plain * 64 == np.round(plain * 64)).all()                          # not exactly summable
+    assert np.array_equal(H.zero_lot_kilo(6444, 818, MANY), v * 1024.0)
+    z = H.zero_windows(v, 20)
+    assert not z[:19].any() and z[22:33].all() and not z[21] and not z[33]         # the run [3, 33)
+    assert np.array_equal(z, np.array([i >= 19 and (v[i - 19:i + 1] == 0.0).all() for i in range(len(v))]))
+    assert not H.zero_windows(v, 7000).any() and np.array_equal(H.zero_windows(v, 1), v == 0.0)
+
+
+def test_flow_over_zero_volume_bars_has_exactly_zero_sums_in_the_restatement():
+    """Adding 0.0 leaves a prefix sum as it is, bit for bit: the recent sum of a window whose recent bars are all zero is exactly
+    0.0, whatever the total in front of it, and the output is log((0.0 + EPS) / (past + EPS)), never the NaN of a negative sum.
+    The device tests ask the kernels for the same on volumes whose prefix sums depend on the order of addition."""
+    v = H.zero_lot_volumes(6444, 818, MANY)
+    s = [0.0]
+    for x in v.tolist():
+        s.append(s[-1] + x)
+    for w, r in FLOW_ARGS:
+        out = H.comp_flow_acceleration(v, w, r)
+        at = np.nonzero(H.zero_windows(v, r)[w - 1:] if r else np.ones(len(v) - (w - 1), bool))[0] + (w - 1)
+        want = np.array([H._log(H._div(0.0 + H.EPS, (s[i + 1 - r] - s[i + 1 - w]) + H.EPS)) for i in at])
+        assert same_bits(out[at], want), (w, r)
+        assert not np.isnan(out[w - 1:]).any(), (w, r)
+        if (w, r) == (20, 1):
+            assert len(at) >= 1600                                                 # (2014 here)
+        # the past part too: all zero -> exactly 0.0 -> log((recent + EPS) / EPS)
+        past = np.nonzero(H.zero_windows(v, w - r)[w - 1 - r:len(v) - r])[0] + (w - 1)
+        want = np.array([H._log(H._div((s[i + 1] - s[i + 1 - r]) + H.EPS, 0.0 + H.EPS)) for i in past])
+        assert same_bits(out[past], want) and (len(past) > 0 or w - r > 30), (w, r)
+
+
+def flow_windows_of_zero_bars(v, w, r):
+    """Where both parts of the flow window that ends at i, the recent r bars and the w - r in front of them, hold zeros only."""
+    v = np.asarray(v, np.float64)
+    both = np.zeros(len(v), bool)
+    both[w - 1:] = H.zero_windows(v, w)[w - 1:] if w else False
+    return both
+
+
+def test_flow_behind_a_nan_is_nan_on_windows_of_zero_bars_too():
+    """A NaN volume makes every later prefix sum NaN, and NaN - NaN is NaN: behind it the restatement has NaN at every output, also
+    where the whole window is zero bars and both of its sums would be exactly 0.0 (log(EPS / EPS) = 0.0) without the NaN in front."""
+    for at in (5, TILE - 1, TILE):
+        v = H.zero_lot_volumes(6444, 802, MANY)
+        clean = v.copy()
+        v[at] = np.nan
+        for (w, r), least in (((1, 0), 1000), ((20, 1), 40), ((20, 5), 40)):
+            out, before = H.comp_flow_acceleration(v, w, r), H.comp_flow_acceleration(clean, w, r)
+            first = max(at, w - 1)
+            assert np.isnan(out[first:]).all() and same_bits(out[:at], before[:at]) and np.isfinite(out[w - 1:at]).all(), (at, w, r)
+            zero = flow_windows_of_zero_bars(v, w, r)
+            zero[:first] = False
+            assert zero.sum() >= least and (before[zero] == 0.0).all(), (at, w, r, int(zero.sum()))
+
+
+def test_vpin_over_zero_volume_bars_is_nan_in_the_restatement():
+    """A window in which both series are zero throughout has a total of exactly 0.0, which is not above 1e-9: NaN.  Elsewhere the
+    total is at least 1.01 x 1024."""
+    for share, windows in ((0, (1, 2, 20)), (0.3, (1,))):
+        b, s = H.zero_lot_kilo(6444, 802, MANY, share), H.zero_lot_kilo(6444, 803, MANY, share)
+        for w in windows:
+            out = H.vpin(b, s, w)
+            zero = H.zero_windows(b, w) & H.zero_windows(s, w)
+            assert zero.sum() >= 50 and np.isnan(out[zero]).all(), (share, w)
+            assert np.isfinite(out[w - 1:][~zero[w - 1:]]).all() and np.isnan(out[:w - 1]).all(), (share, w)
+    # one bar with equal sides, neither zero: |buy - sell| adds 0.0 and the window-1 output there is exactly 0.0
+    assert b[6208] == s[6208] != 0.0 and out[6208] == 0.0 and 6208 % 8 == 0
+
+
+def test_vwap_on_all_zero_windows_is_the_references_own_residue():
+    """On volumes that are not exactly summable the sliding vsum of an all-zero window is what the earlier additions and
+    subtractions left behind, of either sign: the reference holds, computes a number of order 1 or takes the log of a negative
+    number there, by chance.  The device tests leave those outputs out; off them every output from the seed on is finite."""
+    c, w = H.grid_walk(6444, 801), 20
+    seen = set()
+    for runs in ([[TILE - 40, 40]], [[TILE - 30, 60]], [[TILE, 40]], [[2 * TILE - 30, 60]], MANY):
+        v = H.zero_lot_volumes(6444, 802, runs)
+        zero = H.zero_windows(v, w)
+        assert 0 < zero.sum() <= ZERO_SHARE * (len(v) - (w - 1))
+        for lg in (False, True):
+            out, held = H.vwap_distance(c, v, w, lg, sums=True)
+            assert np.isfinite(out[w - 1:][~zero[w - 1:]]).all() and not held[~zero].any()
+            seen |= {"held"} if held[zero].any() else set()
+            seen |= {"computed"} if np.isfinite(out[zero & ~held]).any() else set()
+            seen |= {"nan"} if np.isnan(out[zero]).any() else set()
+            seen |= {"near 2"} if (np.abs(out[zero & ~held]) > 1.5).any() else set()
+    assert seen == {"held", "computed", "nan", "near 2"}
 
 
 def test_regenerated_series_hash_to_the_recorded_ones():

@@ -2,9 +2,9 @@
 """Writes tests/golden/runsum.npz + runsum.json: outputs of the REFERENCE's running-sum indicators -- bollinger_percent_b and
 parkinson_range (feature/core/volatility.py), vwap_distance (feature/core/reversion.py), comp_flow_acceleration and vpin
 (feature/core/volume.py) -- on seeded series that the tests regenerate (tests/_runsum_ref.py: walks and volumes in integer
-arithmetic), on series with NaN in and after the first window, with zero-volume runs, on the edge lengths, on vpin's window 0, and
-the refused arguments.  Build container only: imports the reference in pure-Python mode through oracle/shim, like
-tools/gen_recur_golden.py; no GPU, nothing of the product.
+arithmetic), on series with NaN in and after the first window, with zero-volume runs, with zero-volume bars among volumes that are
+not exactly summable, on the edge lengths, on vpin's window 0, and the refused arguments.  Build container only: imports the
+reference in pure-Python mode through oracle/shim, like tools/gen_recur_golden.py; no GPU, nothing of the product.
 
 The truth is the UNTOUCHED reference's code with two things as the compiled reference has them.  `log` in the reference modules'
 `np` is the host's (tools/gen_rolling_golden.py does the same); NumPy's own log rounds some arguments differently, and the elements
@@ -172,6 +172,22 @@ def zero_run_cases():
     return out
 
 
+def zero_lot_cases():
+    """Zero-volume bars among volumes that are not exactly summable (30 % of the bars and a run of 60 over the tile edge), one tile
+    and 52 elements so that every output is stored: a zero recent or past part of a flow window and a vpin window of zero bars are
+    exactly 0.0 in the reference, whatever the total in front of them; vwap's all-zero windows are its own sliding-sum residue.
+    With a NaN in element 5 every prefix sum of flow behind it is NaN, and so is every output, on windows of zero bars too."""
+    out = {}
+    n, runs = 2048 + 52, [[2048 - 30, 60]]
+    out["zerolot.flow_w20_r1"] = seeded("flow", [20, 1], ("zero_lot_volumes", n, 960, runs))
+    out["zerolot.flow_w20_r5"] = seeded("flow", [20, 5], ("zero_lot_volumes", n, 960, runs))
+    for w, r in ((1, 0), (20, 1), (20, 5)):
+        out[f"zerolot.flow_nan_w{w}_r{r}"] = seeded("flow", [w, r], ("zero_lot_nan", n, 960, runs, 5))
+    out["zerolot.vpin_kilo_w20"] = seeded("vpin", [20], ("zero_lot_kilo", n, 961, runs), ("zero_lot_kilo", n, 962, runs))
+    out["zerolot.vwap_log_w20"] = seeded("vwap", [20, True], ("grid_walk", n, 963), ("zero_lot_volumes", n, 964, runs))
+    return out
+
+
 def nan_cases():
     out = {}
     for where, at in (("first", 5), ("after", 300)):
@@ -268,7 +284,7 @@ def differs(a, b):
 def main():
     out, manifest = {}, {}
     cases = {}
-    for group in (series_cases, zero_run_cases, nan_cases, length_cases, refused_calls):
+    for group in (series_cases, zero_run_cases, zero_lot_cases, nan_cases, length_cases, refused_calls):
         cases.update(group())
     for name, c in cases.items():
         ins = c["inputs"]
@@ -309,6 +325,7 @@ def main():
                      inf=int(np.isinf(ref[1]).sum()))
         if c["fn"] == "vwap":
             entry["held"] = int(H.vwap_distance(*ins, *c["args"], sums=True)[1].sum())
+            entry["zero_windows"] = int(H.zero_windows(ins[1], c["args"][0]).sum())
         if c["fn"] == "boll":
             entry["flat"] = int(H.flat_windows(ins[0], c["args"][0]).sum())
         manifest[name] = entry

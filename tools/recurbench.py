@@ -9,8 +9,8 @@ minimum counts) runs in a child process of its own under a time limit, so that a
 fails nothing more is started.  "bytes_per_element" is what the algorithm has to move: a scan reads its input series twice and writes
 once (ewma 2 x 8 + 8, rsi the same, atr and adx 2 x 24 + 8, adx also the dx series: written once, read twice, + 24), true_range and
 the SMA mode read three series and write one; bollinger 2 x 8 + 8 (its lagged read is the same series), vwap_distance 2 x 16 + 8,
-flow_acceleration 2 x 8 + 8 for the prefix sum, which is read again, + 8 + 8, vpin 2 x 16 + 32 for four prefix sums, read again, + 32
-+ 4, parkinson_range 16 + 8) -> bytes per second, to hold against the HBM rate.
+flow_acceleration 2 x 8 + 12 for the prefix sum and the 4-byte count of non-zero bars, which are read again, + 12 + 8, vpin 2 x 16 + 40 for
+three prefix sums and two series of counts, read again, + 40 + 4, parkinson_range 16 + 8) -> bytes per second, to hold against the HBM rate.
 usage: recurbench.py [SCALE]        SCALE < 1 shrinks every n (a smoke run)
        recurbench.py --step NAME N  (internal) one step, prints its JSON"""
 import ctypes as C
@@ -36,8 +36,8 @@ STEPS = {
     "adx": ("fmk_adx_dev", 3, 80),
     "bollinger_percent_b": ("fmk_bollinger_percent_b_dev", 1, 24),
     "vwap_distance": ("fmk_vwap_distance_dev", 2, 40),
-    "flow_acceleration": ("fmk_flow_acceleration_dev", 1, 40),
-    "vpin": ("fmk_vpin_dev", 2, 100),
+    "flow_acceleration": ("fmk_flow_acceleration_dev", 1, 48),
+    "vpin": ("fmk_vpin_dev", 2, 116),
     "parkinson_range": ("fmk_parkinson_range_dev", 2, 24),
 }
 
