@@ -25,7 +25,11 @@
 //                its elements with the reference's own expression.  Only that carried-in state is not the reference's arithmetic.
 // true_range is an elementwise kernel and the SMA mode of atr a lockstep window walk (fmk_window.h) over true ranges computed on the
 // fly: both are the reference's bits.  Outside the contract: infinities in the inputs of the scans (a^len underflows to zero and
-// 0 * inf is not inf), and the exact step at which a smoothed average underflows to zero.
+// 0 * inf is not inf), and a state that has decayed below 2^-969 over elements that add nothing to it (969, 1 657, 9 063 of them in
+// a row at windows 2, 3, 14), until every channel has taken a non-zero term again: there the reference stalls at the smallest
+// subnormals for windows >= 3 (((w - 1) * 5e-324) / w rounds back to 5e-324; rsi_wilder reads 50.0 off them) and reaches 0.0 for
+// windows <= 2, while the composed a^len underflows to 0.0 here (rsi_wilder NaN until the next loss).  Up to that line exact zeros
+// and NaN positions are the reference's and the values within the tolerance; tests/test_gpu_recur_runs.py pins both sides.
 #include <math.h>
 
 #include "fmk_common.h"

@@ -34,7 +34,9 @@ def ewma(y: NDArray, span: int) -> NDArray[np.float64]:
     v = 1 + (1 - alpha) * v with alpha = 2 / (span + 1), out = u / v; NaN from the first NaN of `y` on.  `span < 1` raises
     ValueError with the reference's message.  An empty series gives an empty array (the reference raises IndexError there).
     A device-wide scan: the outputs agree with the reference to a few units in the last place (1e-9 relative is the contract),
-    NaN positions exactly.  Infinite inputs are outside the contract."""
+    NaN positions and exact zeros exactly.  Outside the contract: infinite inputs, and a numerator that has decayed below 2^-969 over
+    a run of zeros in `y` until the next non-zero one (the reference stalls at the smallest subnormals for 1 - alpha >= 2 / 3 and
+    reaches 0.0 below, the scan's composed state underflows to 0.0)."""
     if not float(span) >= 1.0:
         raise ValueError(SPAN_MESSAGE)
     yy = np.ascontiguousarray(y, dtype=np.float64)

@@ -41,6 +41,9 @@ def rsi_wilder(close: NDArray[np.float64], window: int) -> NDArray[np.float64]:
     avg = ((window - 1) * avg + x) / window; 100 - 100 / (1 + gain / loss) where loss > 0, NaN otherwise, before `window`, and
     everywhere when a difference of the first window is NaN (a later NaN difference counts as no gain and no loss).
     `window < 1` raises ValueError (the reference divides by zero there).  A device-wide scan: the outputs agree with the
-    reference within 1e-7 absolute on the 0-100 scale, NaN positions exactly.  Outside the contract: infinite prices, and the exact
-    bar at which an average underflows to zero after thousands of bars without a loss (there the output turns NaN)."""
+    reference within 1e-7 absolute on the 0-100 scale, NaN positions exactly.  Outside the contract: infinite prices, and an
+    average that has decayed below 2^-969 (969, 1 657, 9 063 bars without a gain or without a loss at windows 2, 3, 14) until both
+    averages have taken a non-zero term again: there the reference stalls at the smallest subnormal for windows of 3 and more (and
+    reads 50.0, 0.0 or 100.0 off it for good) and reaches 0.0 at windows 1 and 2 (NaN), while the scan's composed state underflows to
+    0.0 at every window (NaN until the next loss).  tests/test_gpu_recur_runs.py pins both sides of that line."""
     return series_call("fmk_rsi_wilder", close, window, message=RSI_WINDOW_MESSAGE)

@@ -97,8 +97,11 @@ def atr(high: NDArray[np.float64], low: NDArray[np.float64], close: NDArray[np.f
     """Reference: finmlkit/feature/core/volatility.py:352-437.  SMA mode: the mean of the non-NaN true ranges of the window, the
     reference's bits (its NaN at bar 2 included).  EMA mode: the mean of the first window's non-NaN true ranges, then
     ((window - 1) * atr + tr) / window, NaN for good from the first NaN true range on; a device-wide scan that agrees with the
-    reference to a few units in the last place (1e-9 relative is the contract), NaN positions exactly; infinite prices are
-    outside the contract there.  `normalize` divides by (high + low) / 2.0.  Window 0 gives NaN everywhere, as the reference;
+    reference to a few units in the last place (1e-9 relative is the contract), NaN positions and exact zeros exactly; outside the
+    contract there: infinite prices, and an average that has decayed below 2^-969 over bars without a range (1 657 of them at window
+    3, 9 063 at window 14) until the next bar with one: the reference stalls at the smallest subnormals for windows of 3 and more and
+    reaches 0.0 at windows 1 and 2, the scan's composed state underflows to 0.0 (DESIGN.md section 7e;
+    tests/test_gpu_recur_runs.py pins it).  `normalize` divides by (high + low) / 2.0.  Window 0 gives NaN everywhere, as the reference;
     a negative window raises ValueError."""
     if int(window) < 0:
         raise ValueError(ATR_WINDOW_MESSAGE)

@@ -484,8 +484,9 @@ int fmk_pct_change(fmk_ctx *ctx, const double *x, int64_t n, int64_t periods, do
  * thread's 8 elements is composed from per-tile aggregates, so the outputs from the seed index on agree with the reference to a few
  * units in the last place of the running averages (1e-9 relative is the contract; for rsi_wilder and adx 1e-7 absolute on their
  * 0 .. 100 scale), while NaN positions, the outputs before the seed and adx's exact zeros are the reference's.  The seeds are added
- * in index order.  Not part of the contract: infinite inputs to the four recurrences, and the exact step at which an average
- * underflows to zero.  Scratch: the context's scratch (one record per 2048 elements); adx takes n float64 from the context's pool.
+ * in index order.  Not part of the contract: infinite inputs to the four recurrences, and a state that has decayed below
+ * 2^-969 over elements that add nothing to it, until every channel has taken a non-zero term again (the reference stalls at the
+ * smallest subnormals for windows >= 3 and reaches 0.0 for windows <= 2; the composed state here underflows to 0.0).  Scratch: the context's scratch (one record per 2048 elements); adx takes n float64 from the context's pool.
  * FMK_E_ARG, checked before a device is touched and before any pointer is looked at: span < 1, rsi_wilder window < 1, atr window < 0,
  * length < 1, n >= 2^31. */
 int fmk_ewma_dev(fmk_ctx *ctx, const double *d_y, int64_t n, double span, double *d_out);

@@ -3,7 +3,13 @@ against the reference's recorded outputs (tests/golden/recur.npz, written by too
 reference), the regenerated series against their recorded hashes, the argument checks of the host layer, which need no device, the
 signatures and transform names, and the library's symbols.  Every comparison is bit for bit, NaN positions and the sign of every zero
 included: the restatement is sequential.  Cases of more than 2100 elements record the hash of the reference's output instead of the
-output: the restatement is held against the hash at full size (expected())."""
+output: the restatement is held against the hash at full size (expected()).
+
+The cases runs.* (runs without a loss, a gain, a range or a term, where the state carried from element to element is all there is;
+memories of several tiles) are no part of OK_CASES: past the step at which a decaying state leaves the normal range the kernels are
+not held to the reference, so they have tests of their own, here and in tests/test_gpu_recur_runs.py.  Here: the
+restatement against the recorded hash, the long-double evaluation (index ranges to compare, elements left out, the restatement's own
+deviation) against the record, and what the reference really does past that step."""
 import inspect
 import json
 import math
@@ -21,9 +27,11 @@ GOLD = os.path.join(ROOT, "tests", "golden")
 MANIFEST = json.load(open(os.path.join(GOLD, "recur.json")))
 _NPZ = np.load(os.path.join(GOLD, "recur.npz"))
 
-OK_CASES = sorted(k for k, v in MANIFEST.items() if "raises" not in v)
+RUN_CASES = sorted(k for k in MANIFEST if k.startswith("runs."))
+OK_CASES = sorted(k for k, v in MANIFEST.items() if "raises" not in v and not k.startswith("runs."))
 REFUSED = sorted(k for k, v in MANIFEST.items() if "raises" in v)
-GENERATORS = {"grid_walk": lambda *a: (H.grid_walk(*a),), "hlc_walk": H.hlc_walk}
+GENERATORS = {"grid_walk": lambda *a: (H.grid_walk(*a),), "hlc_walk": H.hlc_walk,
+              "run_close": lambda *a: (H.run_series(*a)[2],), "run_hlc": H.run_series}
 N_INPUTS = {"ewma": 1, "rsi": 1, "tr": 3, "atr": 3, "adx": 3}
 _HASHED = {}
 ENTRIES = ("fmk_ewma", "fmk_rsi_wilder", "fmk_true_range", "fmk_atr", "fmk_adx")
@@ -128,6 +136,135 @@ def test_regenerated_series_hash_to_the_recorded_ones():
 def test_restatement_equals_the_reference(name):
     c = MANIFEST[name]
     assert same_bits(H.call(c["fn"], case_input(name), c["args"]), expected(name)), name
+
+
+# ---------------------------------------------------------------------------------------------- runs.*
+TILE = 2048
+
+
+def run_of(name):
+    """(start, length) of the run of a case runs.b.* / runs.c.*."""
+    kind, n, _, start, length = MANIFEST[name]["source"]["args"][:5]
+    assert start + length + 1500 == n == MANIFEST[name]["n"]
+    return start, length
+
+
+def test_horizon_figures():
+    assert [H.horizon((w - 1) / w) for w in (2, 3, 5, 14)] == [969, 1657, 3010, 9063]
+    assert H.horizon(1 - 2 / (27 + 1)) == H.horizon(13 / 14)          # ewma's span 2 w - 1 has the a of window w
+    for w in (2, 3, 5, 14):                                           # a state from 1.0 is still 2^-969 there, and within two steps below
+        a = (w - 1) / w
+        assert a ** (H.horizon(a) - 1) >= 2.0 ** -969 > a ** (H.horizon(a) + 1)
+
+
+def test_run_series_kinds():
+    n, start, length = 700, 200, 300
+    run = slice(start, start + length)
+    plain = H.run_series("flat", n, 5, start, 0)
+    for kind in ("flat", "rising", "falling", "zeros"):
+        h, lo, c = H.run_series(kind, n, 5, start, length)
+        again = H.run_series(kind, n, 5, start, length)
+        assert all(same_bits(a, b) for a, b in zip((h, lo, c), again))
+        assert all(same_bits(a[:start], b[:start]) for a, b in zip((h, lo, c), plain))       # the walk in front of the run
+        assert (h >= c).all() and (c >= lo).all() and np.isfinite(h).all()
+        d = np.diff(c)[start - 1:start + length - 1]                   # the moves of the run's bars
+        if kind == "zeros":
+            assert (c[run] == 0).all() and (h[run] == 0).all() and (lo[run] == 0).all() and c[start + length] > 50
+            continue
+        assert {"flat": (d == 0).all(), "rising": (d >= 0).all() and (d == 0).any() and (d > 0).any(),
+                "falling": (d <= 0).all() and (d == 0).any() and (d < 0).any()}[kind]
+        assert ((h[run] == lo[run]).all() and (h[run] == c[run]).all()) == (kind == "flat")
+        tr = H.true_range(h, lo, c)
+        assert ((tr[run] == 0).all()) == (kind == "flat") and (tr[:start] > 0).sum() > start * 0.9
+        assert np.abs(np.diff(c)[start + length:]).max() > 0.02        # the walk goes on from the held level
+        assert abs(c[start + length] - c[start + length - 1]) <= 0.35 + 1e-9
+    h, lo, c = H.run_series("from_start", n, 6, 0, 50)
+    assert (c[:50] == c[0]).all() and (h[:50] == lo[:50]).all() and len(set(c[49:60])) > 3
+    assert H.run_series("rising", n, 6, 0, 50, after=-7)[2][50] == pytest.approx(H.run_series("rising", n, 6, 0, 50)[2][49] - 0.07)
+    with pytest.raises(ValueError):
+        H.run_series("from_start", n, 6, 1, 50)
+    with pytest.raises(ValueError):
+        H.run_series("flat", n, 6, 600, 101)
+    with pytest.raises(ValueError):
+        H.run_series("level", n, 6, 0, 50)
+
+
+def test_runs_hold_the_cases_they_should():
+    names = set(RUN_CASES)
+    b = {k for k in names if k.startswith("runs.b.")}
+    assert len(b) == 96 and all(MANIFEST[k]["left_out"] == 0 for k in b)
+    for w, lengths in ((2, (100, 870)), (3, (1490,)), (5, (TILE + 8, 2700)), (14, (TILE + 8, 2 * TILE + 100, 8156)), (100, (3 * TILE,))):
+        for length in lengths:
+            for tag in ("rsi_flat", "rsi_rising", "atr_ema", "atr_ema_norm", "adx", "ewma_zeros"):
+                assert f"runs.b.{tag}.w{w}.s{TILE}.l{length}" in names
+                assert (f"runs.b.{tag}.w{w}.s{TILE + 1003}.l{length}" in names) == (length != TILE + 8)
+            if w > 2:
+                assert length <= 0.9 * H.horizon((w - 1) / w) + 1
+    c = {k for k in names if k.startswith("runs.c.")}
+    assert len(c) == 14 and {MANIFEST[k]["fn"] for k in c} == {"rsi", "atr", "adx"}
+    for k in c:
+        w = MANIFEST[k]["args"][0]
+        assert run_of(k)[1] == int(1.3 * math.log(2.0 ** -1074) / math.log((w - 1) / w)) > 1.3 * H.horizon((w - 1) / w)
+        assert 0 < MANIFEST[k]["left_out"] < 0.35 * MANIFEST[k]["n"]
+    e = {k: MANIFEST[k] for k in names if k.startswith("runs.e.")}
+    assert sorted((v["fn"], v["args"][0]) for v in e.values()) == sorted(
+        [("rsi", 3 * TILE + 1), ("rsi", 10 * TILE - 1), ("atr", 3 * TILE + 1), ("atr", 10 * TILE - 1), ("adx", 2 * TILE + 1), ("adx", 5 * TILE),
+         ("ewma", 4097), ("ewma", 200_001)])
+    assert all(v["left_out"] == 0 and v["n"] <= 22_600 for v in e.values()) and len(names) == len(b) + len(c) + len(e)
+    # the tolerance the GPU tests derive from the record stays ten times and more below the contract's ceiling
+    for k in names:
+        ceiling = 1e-9 if MANIFEST[k]["fn"] in ("ewma", "atr") else 1e-7
+        assert 0 < 16 * MANIFEST[k]["ref_dev"] * 10 <= ceiling, k
+
+
+@pytest.mark.parametrize("name", RUN_CASES)
+def test_run_case_record(name):
+    """The restatement hashes to the reference's recorded output; index ranges, the count left out and the restatement's deviation
+    come out of the long-double evaluation as recorded."""
+    c, ins = MANIFEST[name], case_input(name)
+    own = expected(name)
+    assert "output_sha256" in c and len(own) == c["n"] > 2100
+    states, exact = H.exact_states(c["fn"], ins, c["args"])
+    assert states.dtype == np.longdouble and states.shape[1] == c["n"]
+    mask = H.compare_mask(c["fn"], c["args"], states)
+    assert H.mask_ranges(mask) == c["compare"] and int((~mask).sum()) == c["left_out"]
+    assert np.array_equal(H.ranges_mask(c["compare"], c["n"]), mask)
+    assert H.deviation(c["fn"], own, exact, mask) == c["ref_dev"]
+    e64 = exact.astype(np.float64)
+    assert np.array_equal(np.isnan(own)[mask], np.isnan(e64)[mask])
+    floor = np.longdouble(2.0) ** -969
+    live = np.abs(states[:, mask])
+    assert ((live == 0) | (live >= floor)).all()
+    if not name.startswith("runs.e."):
+        start, length = run_of(name)
+        if c["left_out"]:                                             # compared up to the horizon, and again behind the run
+            (a0, a1), (b0, b1) = c["compare"]
+            w = c["args"][0]
+            assert a0 == 0 and b1 == c["n"] and start + 0.85 * H.horizon((w - 1) / w) < a1 < start + 1.1 * H.horizon((w - 1) / w)
+            assert start + length <= b0 < start + length + 700
+
+
+@pytest.mark.parametrize("name", [k for k in RUN_CASES if k.startswith("runs.c.")])
+def test_past_the_horizon_the_reference_stalls(name):
+    """What the reference does with a state far below 2^-969: for windows of 3 and more ((w - 1) * 5e-324) / w rounds back to
+    5e-324, so an average that has nothing to add stays at the smallest subnormals for good and rsi_wilder reads 50.0 off two of
+    them; at window 2 it halves to 0.0 and rsi_wilder is NaN until the next loss."""
+    c = MANIFEST[name]
+    fn, w = c["fn"], c["args"][0]
+    tiny = 5e-324
+    assert ((w - 1) * tiny) / w == (tiny if w >= 3 else 0.0)
+    own = expected(name)
+    start, length = run_of(name)
+    tail = own[start + length - 200:start + length]                   # the last bars of the run
+    left = ~H.ranges_mask(c["compare"], c["n"])
+    assert left[start + length - 200:start + length].all()
+    if fn == "rsi":
+        assert np.isnan(tail).all() if w == 2 else (tail == 50.0).all()
+        assert np.isfinite(own[start:start + H.horizon((w - 1) / w)]).all()
+    elif fn == "atr":
+        assert (tail == tail[0]).all() and 0 < tail[0] <= (w // 2 + 1) * tiny and ((w - 1) * tail[0] + 0.0) / w == tail[0]
+    else:
+        assert np.isfinite(own).all() and (own >= 0).all() and (own <= 100).all()
 
 
 @pytest.mark.parametrize("name", REFUSED)

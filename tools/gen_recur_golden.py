@@ -10,9 +10,16 @@ positions and the sign of every zero included: the restatement is sequential, so
 is the order in which a `max` meets a NaN in adx_core, which has no NaN checks; the restatement takes Python's order, the first of
 the largest, and the gate below shows that nothing differs.)  Cases of more than 2100 elements record `output_sha256` (over the
 output's bytes, every NaN made the canonical quiet NaN) instead of the output: the host test recomputes it from the restatement.
+
+The group runs.* (flat, one-sided, rangeless and zero runs behind a walk, up to and past the step at which a decaying state leaves
+the normal range, and memories of several tiles) also records, from the same recurrences in np.longdouble (tests/_recur_ref.py:
+exact_states, compare_mask): `compare`, the index ranges in which every live state is exactly 0.0 or at least 2^-969; `left_out`,
+how many elements lie outside them; `ref_dev`, the restatement's largest deviation from the long-double output over `compare` in
+the function's measure.  The GPU tests take their tolerance from `ref_dev`, never from a kernel's output.
     python tools/gen_recur_golden.py <reference checkout>
 """
 import json
+import math
 import os
 import sys
 import warnings
@@ -46,7 +53,9 @@ class Reference:
     adx_core = staticmethod(RTR.adx_core)
 
 
-GENERATORS = {"grid_walk": lambda *a: (H.grid_walk(*a),), "hlc_walk": H.hlc_walk}
+GENERATORS = {"grid_walk": lambda *a: (H.grid_walk(*a),), "hlc_walk": H.hlc_walk,
+              "run_close": lambda *a: (H.run_series(*a)[2],), "run_hlc": H.run_series}
+TILE = 2048                            # elements per workgroup of the scans (csrc/fmk_recur_core.h: RC_TILE)
 STORED_MAX = 2100                      # longer cases record the hash of their output, not the output
 WINDOWS = (1, 2, 3, 14, 100)
 
@@ -146,6 +155,63 @@ def length_cases():
     return out
 
 
+RUN_FUNCTIONS = (("rsi_flat", "rsi", "flat"), ("rsi_rising", "rsi", "rising"), ("atr_ema", "atr", "flat"), ("atr_ema_norm", "atr", "flat"),
+                 ("adx", "adx", "flat"), ("ewma_zeros", "ewma", "zeros"))
+RUN_STARTS = (TILE, TILE + 1000 + 3)   # on a tile edge and off one
+# window -> run lengths inside the contract (0.9 x the horizon at the longest) and whether the run is tried off the tile edge too
+RUN_LENGTHS = {2: ((100, True), (870, True)), 3: ((1490, True),), 5: ((TILE + 8, False), (2700, True)),
+               14: ((TILE + 8, False), (2 * TILE + 100, True), (8156, True)), 100: ((3 * TILE, True),)}
+
+
+def run_args(tag, fn, w):
+    """ewma takes the span with the same a = (w - 1) / w, adx_core the window as its length."""
+    return {"rsi": [w], "atr": [w, True, tag.endswith("norm")], "adx": [w], "ewma": [2 * w - 1]}[fn]
+
+
+def run_case(tag, fn, kind, w, start, length, seed):
+    gen = "run_close" if fn in ("rsi", "ewma") else "run_hlc"
+    return seeded(fn, run_args(tag, fn, w), gen, kind, start + length + 1500, seed, start, length)
+
+
+def runs_cases():
+    """b: decaying runs inside the contract; c: 1.3 x the steps to the smallest subnormal; e: memories of several tiles."""
+    out = {}
+    seed = 900
+    for w, lengths in RUN_LENGTHS.items():
+        for length, both in lengths:
+            for start in RUN_STARTS if both else RUN_STARTS[:1]:
+                for tag, fn, kind in RUN_FUNCTIONS:
+                    seed += 1
+                    out[f"runs.b.{tag}.w{w}.s{start}.l{length}"] = run_case(tag, fn, kind, w, start, length, seed)
+    for w in (2, 3, 14):
+        length = int(1.3 * math.log(2.0 ** -1074) / math.log((w - 1) / w))
+        for start in RUN_STARTS:
+            for tag, fn, kind in (RUN_FUNCTIONS[0], RUN_FUNCTIONS[2], RUN_FUNCTIONS[4]):
+                if w == 2 and fn != "rsi":
+                    continue
+                seed += 1
+                out[f"runs.c.{tag}.w{w}.s{start}.l{length}"] = run_case(tag, fn, kind, w, start, length, seed)
+    for w in (3 * TILE + 1, 10 * TILE - 1):
+        out[f"runs.e.rsi.w{w}"] = seeded("rsi", [w], "grid_walk", w + TILE + 9, 1101, 35, 0.0)
+        out[f"runs.e.atr_ema.w{w}"] = seeded("atr", [w, True, False], "hlc_walk", w - 1 + TILE + 9, 1102)
+    for length in (2 * TILE + 1, 5 * TILE):
+        out[f"runs.e.adx.l{length}"] = seeded("adx", [length], "hlc_walk", 2 * length - 1 + TILE + 9, 1103)
+    for span in (4097, 200_001):
+        out[f"runs.e.ewma.s{span}"] = seeded("ewma", [span], "grid_walk", 4 * TILE + 9, 1104, 35, 0.0)
+    return out
+
+
+def exact_record(name, c, own):
+    """compare, left_out, ref_dev of a runs.* case; refuses one whose restatement and long-double evaluation part in a NaN or,
+    for adx_core, in a zero over `compare`."""
+    states, exact = H.exact_states(c["fn"], c["inputs"], c["args"])
+    mask = H.compare_mask(c["fn"], c["args"], states)
+    e64 = exact.astype(np.float64)
+    if (np.isnan(own) != np.isnan(e64))[mask].any() or (c["fn"] == "adx" and ((own == 0) != (e64 == 0))[mask].any()):
+        raise SystemExit(f"{name}: restatement and long-double evaluation differ in a NaN or a zero inside `compare` -- case refused")
+    return dict(compare=H.mask_ranges(mask), left_out=int((~mask).sum()), ref_dev=H.deviation(c["fn"], own, exact, mask))
+
+
 def refused_calls():
     """Arguments this project refuses with ValueError; what the interpreted reference does with them is recorded beside."""
     y = H.grid_walk(40, 791)
@@ -182,7 +248,7 @@ def differs(a, b):
 def main():
     out, manifest = {}, {}
     cases = {}
-    for group in (series_cases, nan_cases, length_cases, refused_calls):
+    for group in (series_cases, nan_cases, length_cases, refused_calls, runs_cases):
         cases.update(group())
     for name, c in cases.items():
         ins = c["inputs"]
@@ -214,6 +280,8 @@ def main():
         else:
             entry["output_sha256"] = H.sha256(H.nan_canonical(ref[1]))
         entry.update(finite=int(np.isfinite(ref[1]).sum()), nan=int(np.isnan(ref[1]).sum()), zeros=int((ref[1] == 0).sum()))
+        if name.startswith("runs."):
+            entry.update(exact_record(name, c, own[1]))
         manifest[name] = entry
     for k in sorted(manifest):
         print(k, {a: b for a, b in manifest[k].items() if not a.endswith("_sha256")})
