@@ -266,6 +266,8 @@ static inline int fmk_rule_flow_acceleration(fmk_ctx *ctx, int64_t recent_period
     return fmk_rule_least(ctx, recent_periods, 0, "comp_flow_acceleration: recent_periods must not be negative.");
 }
 static inline int fmk_rule_vpin(fmk_ctx *ctx, int64_t window) { return fmk_rule_least(ctx, window, 0, "vpin: window must not be negative."); }
+// the window statistics (fmk_shape.hip): hurst's lag 8 needs one difference (asked after fmk_rule_window)
+static inline int fmk_rule_hurst(fmk_ctx *ctx, int64_t window) { return fmk_rule_least(ctx, window, 9, "hurst_exponent: window must be at least 9."); }
 
 // One excursion of a call onto the context's auxiliary stream (fmk_api.hip), the only way there.  Rules:
 //  - one fork per context at a time: fork() while another FmkSide of the context is open is an error;

@@ -728,4 +728,30 @@ int fmk_price_volume_corr(fmk_ctx *ctx, const double *price, const double *volum
                      [=](const double *p, const double *v, double *o) { return fmk_price_volume_corr_dev(ctx, p, v, n, window, o); });
 }
 
+// the window statistics (fmk_shape.hip)
+int fmk_rolling_kurtosis(fmk_ctx *ctx, const double *x, int64_t n, int64_t window, double *out)
+{
+    return series_host(ctx, fmk_rule_window(ctx, nullptr, window), x, n, out,
+                       [=](const double *d_x, double *d_o) { return fmk_rolling_kurtosis_dev(ctx, d_x, n, window, d_o); });
+}
+
+int fmk_trend_slope(fmk_ctx *ctx, const double *x, int64_t n, int64_t window, double *out)
+{
+    return series_host(ctx, fmk_rule_window(ctx, nullptr, window), x, n, out,
+                       [=](const double *d_x, double *d_o) { return fmk_trend_slope_dev(ctx, d_x, n, window, d_o); });
+}
+
+int fmk_hurst_exponent(fmk_ctx *ctx, const double *x, int64_t n, int64_t window, double *out)
+{
+    FMK_TRY(fmk_rule_window(ctx, nullptr, window));
+    return series_host(ctx, fmk_rule_hurst(ctx, window), x, n, out,
+                       [=](const double *d_x, double *d_o) { return fmk_hurst_exponent_dev(ctx, d_x, n, window, d_o); });
+}
+
+int fmk_bipower_variation(fmk_ctx *ctx, const double *x, int64_t n, int64_t window, double *out)
+{
+    return series_host(ctx, fmk_rule_window(ctx, nullptr, window), x, n, out,
+                       [=](const double *d_x, double *d_o) { return fmk_bipower_variation_dev(ctx, d_x, n, window, d_o); });
+}
+
 }  // extern "C"

@@ -1,4 +1,5 @@
-// fmk_window.h -- the lockstep window walk of the rolling moments (fmk_rolling.hip) and the windowed order statistics (fmk_order.hip).
+// fmk_window.h -- the lockstep window walk of the rolling moments (fmk_rolling.hip), the windowed order statistics (fmk_order.hip),
+// the price-volume correlation (fmk_corr.hip) and the window statistics (fmk_shape.hip).
 // A workgroup of BLOCK lanes owns BLOCK * OPL consecutive outputs, a lane OPL of them, BLOCK apart.  The tile reads a span of
 // window - 1 + outputs elements; the window of output r of lane l of the wave whose first lane is `wave0` is the span elements
 // wave0 + r * BLOCK + l + p, p = 0 .. window - 1.  All lanes walk p upwards in lockstep, so a wave reads 64 consecutive LDS words
@@ -31,6 +32,15 @@ FMK_HD int fmk_slab16(int64_t window, int64_t tile)
 {
     const int64_t span = window - 1 + tile;
     return (int)(span < FMK_SLAB_MAX16 ? span : FMK_SLAB_MAX16);
+}
+
+#define FMK_SLAB_MAX32 1024          // and in 32-byte words (fmk_shape.hip: a word holds four running sums)
+
+// fmk_slab for a walk over 32-byte words
+FMK_HD int fmk_slab32(int64_t window, int64_t tile)
+{
+    const int64_t span = window - 1 + tile;
+    return (int)(span < FMK_SLAB_MAX32 ? span : FMK_SLAB_MAX32);
 }
 
 // The steps of one wave in one slab of `len` words.  w0 = wave0 - (the slab's start in the span); with q = w0 + p, position p of

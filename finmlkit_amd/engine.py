@@ -535,6 +535,26 @@ class DeviceTrades:
         return self._pair("fmk_price_volume_corr_dev", "rolling_price_volume_correlation: price and volume must have the same length.",
                           price, volume, c_i64(int(window)))
 
+    # ------------------------------------------------------------------ window statistics (csrc/fmk_shape.hip)
+    def kurtosis(self, y: DeviceArray, window: int) -> DeviceArray:
+        """rolling_kurtosis (feature/core/shape.py; reference transforms.py:900-933) of a resident float64 series."""
+        return self._series("fmk_rolling_kurtosis_dev", y, window)
+
+    def trend_slope(self, y: DeviceArray, window: int) -> DeviceArray:
+        """trend_slope (feature/core/shape.py; reference transforms.py:936-988) of a resident float64 price series, in degrees."""
+        return self._series("fmk_trend_slope_dev", y, window)
+
+    def hurst_exponent(self, y: DeviceArray, window: int) -> DeviceArray:
+        """hurst_exponent (feature/core/shape.py; reference transforms.py:1341-1397) of a resident float64 series; ValueError when
+        window < 9."""
+        if int(window) < 1:
+            raise ValueError("window must be at least 1.")
+        return self._series("fmk_hurst_exponent_dev", y, window, least=9, message="hurst_exponent: window must be at least 9.")
+
+    def bipower_variation(self, y: DeviceArray, window: int) -> DeviceArray:
+        """bipower_variation (feature/core/shape.py; reference transforms.py:1551-1602) of a resident float64 series."""
+        return self._series("fmk_bipower_variation_dev", y, window)
+
     # ------------------------------------------------------------------ event sampling
     def cusum_filter(self, threshold, series: Optional[DeviceArray] = None) -> DeviceArray:
         """cusum_filter (sampling/filters.py:7-70) on a resident float64 series (default: the price column) -> int64 event indices

@@ -1,4 +1,5 @@
-"""The core feature functions; `adx_core` is exported here as well as from `.trend`."""
+"""The core feature functions; `adx_core` is exported here as well as from `.trend`, and the window statistics of `.shape`."""
+from .shape import bipower_variation, hurst_exponent, rolling_kurtosis, trend_slope
 from .trend import adx_core
 
-__all__ = ["adx_core"]
+__all__ = ["adx_core", "bipower_variation", "hurst_exponent", "rolling_kurtosis", "trend_slope"]

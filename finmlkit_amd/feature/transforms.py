@@ -4,7 +4,9 @@
 structural-break transform `CUSUMTest` (reference transforms.py:631-708), and the recursive indicators `EWMA`, `RSIWilder`, `ATR`
 and `ADX` (reference transforms.py:577-602, :206-273, :711-751, :991-1030), and the running-sum indicators `BollingerPercentB`,
 `VWAPDistance`, `ParkinsonRange`, `FlowAcceleration` and `VPIN` (reference transforms.py:494-518, :388-418, :521-546, :605-628,
-:816-870), and the rolling price-volume correlation `PriceVolumeCorrelation` (reference transforms.py:754-813).
+:816-870), and the rolling price-volume correlation `PriceVolumeCorrelation` (reference transforms.py:754-813), and the window
+statistics `KurtosisTransform`, `TrendSlope`, `HurstExponent` and `BiPowerVariation` (reference transforms.py:900-933, :936-988,
+:1341-1397, :1551-1602; there pandas' rolling.apply on either backend, here the kernels of csrc/fmk_shape.hip).
 
 Counterparts of finmlkit/feature/transforms.py:89-117 (ReturnT), :308-332 (EWMST) and the
 pipeline part of finmlkit/feature/kit.py:Compose (:630-720), enough to run the QuickStart flow
@@ -29,6 +31,7 @@ from .core.momentum import LENGTH_MESSAGE, PERIOD_MESSAGE, RSI_WINDOW_MESSAGE, r
 from .core.trend import adx_core
 from .core.utils import PERIODS_MESSAGE, comp_burst_ratio, comp_lagged_returns, comp_zscore, pct_change
 from .core.reversion import vwap_distance
+from .core.shape import HURST_MIN_WINDOW, HURST_WINDOW_MESSAGE, bipower_variation, hurst_exponent, rolling_kurtosis, trend_slope
 from .core.volatility import (BOLLINGER_WINDOW_MESSAGE, atr, bollinger_percent_b, ewmst, parkinson_range, realized_vol,
                               variance_ratio_1_4_core)
 from .core.volume import RECENT_MESSAGE, comp_flow_acceleration, vpin
@@ -218,6 +221,54 @@ class BurstRatio(_Rolling):
 
     def __init__(self, window: int, input_col: str):
         super().__init__(input_col, f"burst{window}")
+        self.window = window
+
+
+class KurtosisTransform(_Rolling):
+    """Rolling excess kurtosis (reference transforms.py:900-933: scipy's biased Fisher form under pandas' rolling.apply)."""
+    _host = staticmethod(rolling_kurtosis)
+    _entry = "fmk_rolling_kurtosis_dev"
+
+    def __init__(self, window: int = 32, input_col: str = "ret1"):
+        super().__init__(input_col, f"kurt_{window}")
+        self.window = window
+
+
+class TrendSlope(_Rolling):
+    """The least-squares slope of ln(close) over the window as an angle in degrees (reference transforms.py:936-988: a Python loop
+    around scipy's linregress)."""
+    _host = staticmethod(trend_slope)
+    _entry = "fmk_trend_slope_dev"
+
+    def __init__(self, window: int = 24, input_col: str = "close"):
+        super().__init__(input_col, f"trend_slope_{window}")
+        self.window = window
+
+
+class HurstExponent(_Rolling):
+    """The aggregated-variance Hurst exponent over lags 1, 2, 4, 8 (reference transforms.py:1341-1397).  `window < 9` raises
+    ValueError when the transform is applied; the reference raises TypeError out of polyfit there."""
+    _host = staticmethod(hurst_exponent)
+    _entry = "fmk_hurst_exponent_dev"
+
+    def __init__(self, window: int = 24, input_col: str = "ret1"):
+        super().__init__(input_col, f"hurst{window}")
+        self.window = window
+
+    def _dev(self, ts, y):
+        if 1 <= int(self.window) < HURST_MIN_WINDOW:
+            raise ValueError(HURST_WINDOW_MESSAGE)
+        return super()._dev(ts, y)
+
+
+class BiPowerVariation(_Rolling):
+    """Bi-power variation: sqrt(pi / 2) times the sum of `window` products of consecutive absolute returns (reference
+    transforms.py:1551-1602); the first output is at index `window`."""
+    _host = staticmethod(bipower_variation)
+    _entry = "fmk_bipower_variation_dev"
+
+    def __init__(self, window: int = 12, input_col: str = "ret1"):
+        super().__init__(input_col, f"bv_{window}")
         self.window = window
 
 

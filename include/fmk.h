@@ -556,6 +556,28 @@ int fmk_parkinson_range(fmk_ctx *ctx, const double *high, const double *low, int
 int fmk_price_volume_corr_dev(fmk_ctx *ctx, const double *d_price, const double *d_volume, int64_t n, int64_t window, double *d_out);
 int fmk_price_volume_corr(fmk_ctx *ctx, const double *price, const double *volume, int64_t n, int64_t window, double *out);
 
+/* ---- window statistics of finmlkit/feature/transforms.py on a float64 series of n elements -> float64 array of n elements
+ * (csrc/fmk_shape.hip): KurtosisTransform (:900-933), TrendSlope (:936-988), HurstExponent (:1341-1397), BiPowerVariation (:1551-1602).
+ * Every window is recomputed on its own.  A window that reads a NaN or an infinity gives NaN; window > n gives NaN everywhere.
+ *   kurtosis  t >= window - 1 over x[t-window+1 .. t]: m4 / (m2 * m2) - 3 of the biased central moments (NaN where m2 == 0).
+ *   slope     t >= window - 1: the least-squares slope of ln x on 0 .. window-1 as an angle, atan(slope) * 180 / pi; a price that is
+ *             not finite and > 0 gives NaN; window 1 gives NaN.
+ *   hurst     t >= window - 1, window >= 9: with tau_k the population standard deviation of the window - k sums of k consecutive
+ *             elements of x[t-window+2 .. t], k = 1, 2, 4, 8: the least-squares slope of ln tau_k on ln k where all four are > 0,
+ *             NaN otherwise (everywhere at window 9).  x[t-window+1] enters no sum and must be finite all the same.
+ *   bipower   t >= window over x[t-window .. t]: sqrt(pi / 2) * the sum of |x[j]| * |x[j-1]|, j = t-window+1 .. t.
+ * The reference's values within the tolerances of tests/golden/shape.json, its NaN positions exactly.
+ * FMK_E_ARG, checked before a device is touched and before any pointer is looked at: window < 1 (the reference returns all NaN or
+ * zeros there), hurst with window < 9 (the reference raises TypeError), n >= 2^31. */
+int fmk_rolling_kurtosis_dev(fmk_ctx *ctx, const double *d_x, int64_t n, int64_t window, double *d_out);
+int fmk_rolling_kurtosis(fmk_ctx *ctx, const double *x, int64_t n, int64_t window, double *out);
+int fmk_trend_slope_dev(fmk_ctx *ctx, const double *d_x, int64_t n, int64_t window, double *d_out);
+int fmk_trend_slope(fmk_ctx *ctx, const double *x, int64_t n, int64_t window, double *out);
+int fmk_hurst_exponent_dev(fmk_ctx *ctx, const double *d_x, int64_t n, int64_t window, double *d_out);
+int fmk_hurst_exponent(fmk_ctx *ctx, const double *x, int64_t n, int64_t window, double *out);
+int fmk_bipower_variation_dev(fmk_ctx *ctx, const double *d_x, int64_t n, int64_t window, double *d_out);
+int fmk_bipower_variation(fmk_ctx *ctx, const double *x, int64_t n, int64_t window, double *out);
+
 /* ---- labels and sample weights on the tick tape: finmlkit/label/tbm.py, label/weights.py ------------------------
  * triple_barrier (tbm.py:11-158) on the raw tape.  Per event: label (side labels -1 / +1; meta labels 0 / 1 when d_side is given),
  * index of the first barrier touch, the return there and the max return / barrier ratio.  Labels, touch indices, returns and ratios
