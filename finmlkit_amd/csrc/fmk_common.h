@@ -268,6 +268,20 @@ static inline int fmk_rule_flow_acceleration(fmk_ctx *ctx, int64_t recent_period
 static inline int fmk_rule_vpin(fmk_ctx *ctx, int64_t window) { return fmk_rule_least(ctx, window, 0, "vpin: window must not be negative."); }
 // the window statistics (fmk_shape.hip): hurst's lag 8 needs one difference (asked after fmk_rule_window)
 static inline int fmk_rule_hurst(fmk_ctx *ctx, int64_t window) { return fmk_rule_least(ctx, window, 9, "hurst_exponent: window must be at least 9."); }
+// the approximate entropy (fmk_entropy.hip): the order-(m + 1) embedding needs one vector; one tile's span and the table of
+// logarithms have to fit in LDS; the kernels are instantiated per m
+#define FMK_APEN_MAX_M 4
+#define FMK_APEN_MAX_WINDOW 1024
+static inline int fmk_rule_apen(fmk_ctx *ctx, int64_t window, int64_t m, double tolerance)
+{
+    FMK_TRY(fmk_rule_least(ctx, m, 1, "approximate_entropy: m must be at least 1."));
+    if (m > FMK_APEN_MAX_M) return fmk_set_error(ctx, FMK_E_ARG, "approximate_entropy: m must be at most 4.");
+    if (window < m + 1) return fmk_set_error(ctx, FMK_E_ARG, "approximate_entropy: window must be at least m + 1.");
+    if (window > FMK_APEN_MAX_WINDOW) return fmk_set_error(ctx, FMK_E_ARG, "approximate_entropy: window must be at most 1024.");
+    if (!(tolerance >= 0.0 && tolerance < INFINITY))
+        return fmk_set_error(ctx, FMK_E_ARG, "approximate_entropy: tolerance must be finite and not negative.");
+    return FMK_OK;
+}
 
 // One excursion of a call onto the context's auxiliary stream (fmk_api.hip), the only way there.  Rules:
 //  - one fork per context at a time: fork() while another FmkSide of the context is open is an error;

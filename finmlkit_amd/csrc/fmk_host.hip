@@ -754,4 +754,11 @@ int fmk_bipower_variation(fmk_ctx *ctx, const double *x, int64_t n, int64_t wind
                        [=](const double *d_x, double *d_o) { return fmk_bipower_variation_dev(ctx, d_x, n, window, d_o); });
 }
 
+// the approximate entropy (fmk_entropy.hip)
+int fmk_approximate_entropy(fmk_ctx *ctx, const double *x, int64_t n, int64_t window, int64_t m, double tolerance, double *out)
+{
+    return series_host(ctx, fmk_rule_apen(ctx, window, m, tolerance), x, n, out,
+                       [=](const double *d_x, double *d_o) { return fmk_approximate_entropy_dev(ctx, d_x, n, window, m, tolerance, d_o); });
+}
+
 }  // extern "C"

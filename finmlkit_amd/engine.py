@@ -555,6 +555,14 @@ class DeviceTrades:
         """bipower_variation (feature/core/shape.py; reference transforms.py:1551-1602) of a resident float64 series."""
         return self._series("fmk_bipower_variation_dev", y, window)
 
+    # ------------------------------------------------------------------ approximate entropy (csrc/fmk_entropy.hip)
+    def approximate_entropy(self, y: DeviceArray, window: int, m: int = 2, tolerance: float = 0.2) -> DeviceArray:
+        """approximate_entropy (feature/core/entropy.py; reference transforms.py:1400-1457) of a resident float64 series; ValueError
+        for the arguments that function refuses."""
+        from .feature.core.entropy import check_arguments
+        check_arguments(window, m, tolerance)
+        return self._series("fmk_approximate_entropy_dev", y, window, c_i64(int(m)), c_f64(float(tolerance)))
+
     # ------------------------------------------------------------------ event sampling
     def cusum_filter(self, threshold, series: Optional[DeviceArray] = None) -> DeviceArray:
         """cusum_filter (sampling/filters.py:7-70) on a resident float64 series (default: the price column) -> int64 event indices

@@ -6,7 +6,9 @@ and `ADX` (reference transforms.py:577-602, :206-273, :711-751, :991-1030), and 
 `VWAPDistance`, `ParkinsonRange`, `FlowAcceleration` and `VPIN` (reference transforms.py:494-518, :388-418, :521-546, :605-628,
 :816-870), and the rolling price-volume correlation `PriceVolumeCorrelation` (reference transforms.py:754-813), and the window
 statistics `KurtosisTransform`, `TrendSlope`, `HurstExponent` and `BiPowerVariation` (reference transforms.py:900-933, :936-988,
-:1341-1397, :1551-1602; there pandas' rolling.apply on either backend, here the kernels of csrc/fmk_shape.hip).
+:1341-1397, :1551-1602; there pandas' rolling.apply on either backend, here the kernels of csrc/fmk_shape.hip), and the rolling
+approximate entropy `ApproximateEntropy` (reference transforms.py:1400-1457; there pandas' rolling.apply around
+`antropy.app_entropy`, here the kernel of csrc/fmk_entropy.hip, which needs no `antropy`).
 
 Counterparts of finmlkit/feature/transforms.py:89-117 (ReturnT), :308-332 (EWMST) and the
 pipeline part of finmlkit/feature/kit.py:Compose (:630-720), enough to run the QuickStart flow
@@ -26,6 +28,7 @@ from .. import _ffi
 from .._ffi import DeviceArray, c_f64, c_i64
 from .core.structural_break.cusum import cusum_test_rolling
 from .core.correlation import rolling_price_volume_correlation
+from .core.entropy import approximate_entropy, check_arguments as check_entropy_arguments
 from .core.ma import SPAN_MESSAGE, ewma, sma
 from .core.momentum import LENGTH_MESSAGE, PERIOD_MESSAGE, RSI_WINDOW_MESSAGE, roc, rsi_wilder, stoch_k
 from .core.trend import adx_core
@@ -270,6 +273,30 @@ class BiPowerVariation(_Rolling):
     def __init__(self, window: int = 12, input_col: str = "ret1"):
         super().__init__(input_col, f"bv_{window}")
         self.window = window
+
+
+class ApproximateEntropy(_Rolling):
+    """Rolling approximate entropy (reference transforms.py:1400-1457: pandas' rolling.apply around antropy.app_entropy with the
+    Chebyshev metric and the tolerance `tolerance * std(window)`).  Refused arguments raise ValueError when the transform is
+    applied (core/entropy.py)."""
+    _host = staticmethod(approximate_entropy)
+    _entry = "fmk_approximate_entropy_dev"
+
+    def __init__(self, window: int = 24, m: int = 2, tolerance: float = 0.2, input_col: str = "ret1"):
+        super().__init__(input_col, f"apen{window}")
+        self.window = window
+        self.m = m
+        self.tolerance = tolerance
+
+    def _args(self):
+        return (self.m, self.tolerance)
+
+    def _c_args(self):
+        return (c_i64(int(self.m)), c_f64(float(self.tolerance)))
+
+    def _dev(self, ts, y):
+        check_entropy_arguments(self.window, self.m, self.tolerance)
+        return super()._dev(ts, y)
 
 
 class EWMA(SISOTransform):

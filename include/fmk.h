@@ -578,6 +578,20 @@ int fmk_hurst_exponent(fmk_ctx *ctx, const double *x, int64_t n, int64_t window,
 int fmk_bipower_variation_dev(fmk_ctx *ctx, const double *d_x, int64_t n, int64_t window, double *d_out);
 int fmk_bipower_variation(fmk_ctx *ctx, const double *x, int64_t n, int64_t window, double *out);
 
+/* ---- rolling approximate entropy of a float64 series of n elements -> float64 array of n elements (csrc/fmk_entropy.hip): the
+ * reference's ApproximateEntropy transform (transforms.py:1400-1457), antropy.app_entropy(x, order=m, metric="chebyshev",
+ * tolerance=tolerance * std(x)) on every window.  For t >= window - 1 over x[t-window+1 .. t], written x_0 .. x_{w-1}:
+ *   r = tolerance * the window's population standard deviation; for k in (m, m + 1) the N_k = window - k + 1 vectors
+ *   (x_i .. x_{i+k-1}); C_k[i] = the number of j with max_q |x_{i+q} - x_{j+q}| <= r (inclusive, j = i counts);
+ *   phi_k = mean_i ln(C_k[i] / N_k); out[t] = phi_m - phi_{m+1}, which can be negative.
+ * NaN before the first full window and in every window that reads a NaN or an infinity; window > n gives NaN everywhere.  A window
+ * in which every pair matches (a constant one; tolerance 0 means only equal values match) gives exactly 0.0.  The published
+ * algorithm within the tolerance of tests/golden/entropy.json, NaN positions exactly.  O(n * window^2).
+ * FMK_E_ARG, checked in this order before a device is touched and before any pointer is looked at: m < 1, m > 4, window < m + 1,
+ * window > 1024, tolerance negative, NaN or infinite; n >= 2^31. */
+int fmk_approximate_entropy_dev(fmk_ctx *ctx, const double *d_x, int64_t n, int64_t window, int64_t m, double tolerance, double *d_out);
+int fmk_approximate_entropy(fmk_ctx *ctx, const double *x, int64_t n, int64_t window, int64_t m, double tolerance, double *out);
+
 /* ---- labels and sample weights on the tick tape: finmlkit/label/tbm.py, label/weights.py ------------------------
  * triple_barrier (tbm.py:11-158) on the raw tape.  Per event: label (side labels -1 / +1; meta labels 0 / 1 when d_side is given),
  * index of the first barrier touch, the return there and the max return / barrier ratio.  Labels, touch indices, returns and ratios
