@@ -70,7 +70,7 @@ int series_host(fmk_ctx *ctx, int rule, const double *x, int64_t n, double *out,
     return down(ctx, out, (const double *)d_o, n);
 }
 
-// high, low and close up, dev(d_high, d_low, d_close, d_out), one series down
+// three series up in the order given (high, low, close; stoch_k's close, low, high), dev(d_1, d_2, d_3, d_out), one series down
 template <typename Dev>
 int hlc_host(fmk_ctx *ctx, int rule, const double *high, const double *low, const double *close, int64_t n, double *out, Dev dev)
 {
@@ -635,15 +635,8 @@ int fmk_pct_change(fmk_ctx *ctx, const double *x, int64_t n, int64_t periods, do
 
 int fmk_stoch_k(fmk_ctx *ctx, const double *close, const double *low, const double *high, int64_t n, int64_t length, double *out)
 {
-    FMK_TRY(fmk_rule_stoch_k(ctx, length));
-    DevBag bag(ctx);
-    double *d_c, *d_l, *d_h, *d_o;
-    FMK_TRY(bag.up(close, n, &d_c));
-    FMK_TRY(bag.up(low, n, &d_l));
-    FMK_TRY(bag.up(high, n, &d_h));
-    FMK_TRY(bag.out(n, &d_o));
-    FMK_TRY(fmk_stoch_k_dev(ctx, d_c, d_l, d_h, n, length, d_o));
-    return down(ctx, out, (const double *)d_o, n);
+    return hlc_host(ctx, fmk_rule_stoch_k(ctx, length), close, low, high, n, out,
+                    [=](const double *c, const double *l, const double *h, double *o) { return fmk_stoch_k_dev(ctx, c, l, h, n, length, o); });
 }
 
 // the recursive indicators (fmk_recur.hip)

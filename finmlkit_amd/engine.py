@@ -15,6 +15,7 @@ import numpy as np
 from . import _ffi
 from ._ffi import (DIRECTIONAL_FIELDS, FOOTPRINT_BAR_FIELDS, FOOTPRINT_FLAT_FIELDS, Context, DeviceArray,
                    DirectionalOut, FootprintOut, c_f64, c_i64, c_vp)
+from .feature.series_ops import OPS, resident
 
 DENSE_GAP_MOD = 100_000_000          # mean gap 50 ms, no empty 1-min bar
 SPARSE_GAP_MOD = 500_000_000_000     # "sparse" variant: exercises empty bars
@@ -26,6 +27,7 @@ OHLCV_FIELDS = [("open", np.float64), ("high", np.float64), ("low", np.float64),
 
 class DeviceTrades:
     """Trade columns resident in HBM: ts int64 ns, price f64, amount f32|f64, side int8."""
+    ctx: Optional[Context] = None        # set by __init__; the series features refuse their arguments without one
 
     def __init__(self, ctx: Context, ts: DeviceArray, price: DeviceArray, amount: DeviceArray,
                  side: Optional[DeviceArray]):
@@ -379,189 +381,114 @@ class DeviceTrades:
         self.ctx.call("fmk_realized_vol_dev", r.p, c_i64(r.n), c_i64(int(window)), C.c_int(bool(is_sample)), out.p)
         return out
 
-    # ------------------------------------------------------------------ rolling-window moments (csrc/fmk_rolling.hip)
-    def _f64(self, name: str, *series) -> None:
-        for y in series:
-            if y.dtype != np.float64:
-                raise TypeError(f"{name}: the series must be float64, not {y.dtype}")
-
-    def _series(self, name: str, y: DeviceArray, arg: int, *extra, least: int = 1,
-                message: str = "window must be at least 1.") -> DeviceArray:
-        if int(arg) < least:
-            raise ValueError(message)
-        self._f64(name, y)
-        out = DeviceArray(self.ctx, y.n, np.float64)
-        if y.n:
-            self.ctx.call(name, y.p, c_i64(y.n), c_i64(int(arg)), *extra, out.p)
-        return out
-
+    # ------------------------------------------------------------------ series features: one `resident` call per row of
+    # feature/series_ops.py, which checks the arguments, the dtype and the lengths before the context is looked at
+    # rolling-window moments (csrc/fmk_rolling.hip)
     def sma(self, y: DeviceArray, window: int) -> DeviceArray:
         """sma (feature/core/ma.py:46-62) of a resident float64 series."""
-        return self._series("fmk_sma_dev", y, window)
+        return resident(self.ctx, OPS["sma"], (y,), window)
 
     def zscore(self, y: DeviceArray, window: int, ddof: int = 0) -> DeviceArray:
         """comp_zscore (feature/core/utils.py:67-90) of a resident float64 series; ValueError when window - ddof <= 0."""
-        if int(window) >= 1 and int(window) - int(ddof) <= 0:
-            raise ValueError("comp_zscore: window - ddof must be positive.")
-        return self._series("fmk_zscore_dev", y, window, c_i64(int(ddof)))
+        return resident(self.ctx, OPS["zscore"], (y,), window, ddof)
 
     def rolling_variance(self, y: DeviceArray, window: int, ddof: int = 1, min_periods: int = 1) -> DeviceArray:
         """rolling_variance_nb (feature/core/volatility.py:440-478) of a resident float64 series."""
-        return self._series("fmk_rolling_variance_dev", y, window, c_i64(int(ddof)), c_i64(int(min_periods)))
+        return resident(self.ctx, OPS["rolling_variance"], (y,), window, ddof, min_periods)
 
     def variance_ratio_1_4(self, window: int = 32, ddof: int = 0, ret_type: str = "log",
                            series: Optional[DeviceArray] = None) -> DeviceArray:
         """variance_ratio_1_4_core (feature/core/volatility.py:481-540) on a resident float64 series (default: the price column)."""
-        x = self.price if series is None else series
-        return self._series("fmk_variance_ratio_1_4_dev", x, window, c_i64(int(ddof)), C.c_int(ret_type == "log"))
+        return resident(self.ctx, OPS["variance_ratio_1_4"], (self.price if series is None else series,), window, ddof, ret_type == "log")
 
-    # ------------------------------------------------------------------ windowed order statistics (csrc/fmk_order.hip)
+    # windowed order statistics (csrc/fmk_order.hip)
     def burst_ratio(self, y: DeviceArray, window: int) -> DeviceArray:
         """comp_burst_ratio (feature/core/utils.py:92-108) of a resident float64 series: y / its rolling median."""
-        return self._series("fmk_burst_ratio_dev", y, window)
+        return resident(self.ctx, OPS["burst_ratio"], (y,), window)
 
     def roc(self, y: DeviceArray, period: int) -> DeviceArray:
         """roc (feature/core/momentum.py:6-22) of a resident float64 series."""
-        return self._series("fmk_roc_dev", y, period, least=0, message="roc: period must not be negative.")
+        return resident(self.ctx, OPS["roc"], (y,), period)
 
     def pct_change(self, y: DeviceArray, periods: int) -> DeviceArray:
         """pct_change (feature/core/utils.py:110-124) of a resident float64 series."""
-        return self._series("fmk_pct_change_dev", y, periods, least=0, message="pct_change: periods must not be negative.")
+        return resident(self.ctx, OPS["pct_change"], (y,), periods)
 
     def stoch_k(self, close: DeviceArray, low: DeviceArray, high: DeviceArray, length: int) -> DeviceArray:
         """stoch_k (feature/core/momentum.py:68-112) of three resident float64 series of one length."""
-        if int(length) < 1:
-            raise ValueError("stoch_k: length must be at least 1.")
-        self._f64("fmk_stoch_k_dev", close, low, high)
-        if not close.n == low.n == high.n:
-            raise ValueError("stoch_k: close, low and high must have the same length.")
-        out = DeviceArray(self.ctx, close.n, np.float64)
-        if close.n:
-            self.ctx.call("fmk_stoch_k_dev", close.p, low.p, high.p, c_i64(close.n), c_i64(int(length)), out.p)
-        return out
+        return resident(self.ctx, OPS["stoch_k"], (close, low, high), length)
 
-    # ------------------------------------------------------------------ recursive indicators (csrc/fmk_recur.hip)
+    # recursive indicators (csrc/fmk_recur.hip)
     def ewma(self, y: DeviceArray, span) -> DeviceArray:
         """ewma (feature/core/ma.py:6-43) of a resident float64 series."""
-        if not float(span) >= 1.0:
-            raise ValueError("span size is less than or equal to 1. Please provide a span size greater than 1.")
-        self._f64("fmk_ewma_dev", y)
-        out = DeviceArray(self.ctx, y.n, np.float64)
-        if y.n:
-            self.ctx.call("fmk_ewma_dev", y.p, c_i64(y.n), c_f64(float(span)), out.p)
-        return out
+        return resident(self.ctx, OPS["ewma"], (y,), span)
 
     def rsi_wilder(self, close: DeviceArray, window: int) -> DeviceArray:
         """rsi_wilder (feature/core/momentum.py:25-65) of a resident float64 series."""
-        return self._series("fmk_rsi_wilder_dev", close, window, message="rsi_wilder: window must be at least 1.")
-
-    def _hlc(self, name: str, message: str, high: DeviceArray, low: DeviceArray, close: DeviceArray, *args) -> DeviceArray:
-        self._f64(name, high, low, close)
-        if not high.n == low.n == close.n:
-            raise ValueError(message)
-        out = DeviceArray(self.ctx, high.n, np.float64)
-        if high.n:
-            self.ctx.call(name, high.p, low.p, close.p, c_i64(high.n), *args, out.p)
-        return out
+        return resident(self.ctx, OPS["rsi_wilder"], (close,), window)
 
     def true_range(self, high: DeviceArray, low: DeviceArray, close: DeviceArray) -> DeviceArray:
         """true_range (feature/core/volatility.py:222-253) of three resident float64 series of one length."""
-        return self._hlc("fmk_true_range_dev", "The length of high, low, and close prices must be the same.", high, low, close)
+        return resident(self.ctx, OPS["true_range"], (high, low, close))
 
     def atr(self, high: DeviceArray, low: DeviceArray, close: DeviceArray, window: int, ema_based: bool = False,
             normalize: bool = False) -> DeviceArray:
         """atr (feature/core/volatility.py:352-437) of three resident float64 series of one length."""
-        if int(window) < 0:
-            raise ValueError("atr: window must not be negative.")
-        return self._hlc("fmk_atr_dev", "The length of high, low, and close prices must be the same.", high, low, close,
-                         c_i64(int(window)), C.c_int(bool(ema_based)), C.c_int(bool(normalize)))
+        return resident(self.ctx, OPS["atr"], (high, low, close), window, ema_based, normalize)
 
     def adx(self, high: DeviceArray, low: DeviceArray, close: DeviceArray, length: int = 14) -> DeviceArray:
         """adx_core (feature/core/trend.py:8-96) of three resident float64 series of one length."""
-        if int(length) < 1:
-            raise ValueError("adx_core: length must be at least 1.")
-        return self._hlc("fmk_adx_dev", "adx_core: high, low and close must have the same length.", high, low, close,
-                         c_i64(int(length)))
+        return resident(self.ctx, OPS["adx"], (high, low, close), length)
 
-    # ------------------------------------------------------------------ running-sum indicators (csrc/fmk_runsum.hip)
-    def _pair(self, name: str, message: str, a: DeviceArray, b: DeviceArray, *args, dtype=np.float64) -> DeviceArray:
-        self._f64(name, a, b)
-        if a.n != b.n:
-            raise ValueError(message)
-        out = DeviceArray(self.ctx, a.n, dtype)
-        if a.n:
-            self.ctx.call(name, a.p, b.p, c_i64(a.n), *args, out.p)
-        return out
-
+    # running-sum indicators (csrc/fmk_runsum.hip)
     def bollinger_percent_b(self, y: DeviceArray, window: int, num_std: float = 2.0) -> DeviceArray:
         """bollinger_percent_b (feature/core/volatility.py:289-338) of a resident float64 series."""
-        return self._series("fmk_bollinger_percent_b_dev", y, window, c_f64(float(num_std)),
-                            message="bollinger_percent_b: window must be at least 1.")
+        return resident(self.ctx, OPS["bollinger_percent_b"], (y,), window, num_std)
 
     def vwap_distance(self, close: DeviceArray, volume: DeviceArray, n_periods: int, is_log: bool = False) -> DeviceArray:
         """vwap_distance (feature/core/reversion.py:9-56) of two resident float64 series of one length."""
-        if int(n_periods) < 1:
-            raise ValueError("vwap_distance: n_periods must be at least 1.")
-        return self._pair("fmk_vwap_distance_dev", "vwap_distance: close and volume must have the same length.", close, volume,
-                          c_i64(int(n_periods)), C.c_int(bool(is_log)))
+        return resident(self.ctx, OPS["vwap_distance"], (close, volume), n_periods, is_log)
 
     def parkinson_range(self, high: DeviceArray, low: DeviceArray) -> DeviceArray:
         """parkinson_range (feature/core/volatility.py:341-349) of two resident float64 series of one length."""
-        return self._pair("fmk_parkinson_range_dev", "parkinson_range: high and low must have the same length.", high, low)
+        return resident(self.ctx, OPS["parkinson_range"], (high, low))
 
     def flow_acceleration(self, volumes: DeviceArray, window: int, recent_periods: int) -> DeviceArray:
         """comp_flow_acceleration (feature/core/volume.py:572-607) of a resident float64 series."""
-        if int(recent_periods) < 0:
-            raise ValueError("comp_flow_acceleration: recent_periods must not be negative.")
-        self._f64("fmk_flow_acceleration_dev", volumes)
-        out = DeviceArray(self.ctx, volumes.n, np.float64)
-        if volumes.n:
-            self.ctx.call("fmk_flow_acceleration_dev", volumes.p, c_i64(volumes.n), c_i64(int(window)), c_i64(int(recent_periods)),
-                          out.p)
-        return out
+        return resident(self.ctx, OPS["flow_acceleration"], (volumes,), window, recent_periods)
 
     def vpin(self, volume_buy: DeviceArray, volume_sell: DeviceArray, window: int) -> DeviceArray:
         """vpin (feature/core/volume.py:610-641) of two resident float64 series of one length -> a float32 array."""
-        if int(window) < 0:
-            raise ValueError("vpin: window must not be negative.")
-        return self._pair("fmk_vpin_dev", "vpin: volume_buy and volume_sell must have the same length.", volume_buy, volume_sell,
-                          c_i64(int(window)), dtype=np.float32)
+        return resident(self.ctx, OPS["vpin"], (volume_buy, volume_sell), window)
 
-    # ------------------------------------------------------------------ rolling price-volume correlation (csrc/fmk_corr.hip)
+    # rolling price-volume correlation (csrc/fmk_corr.hip)
     def price_volume_corr(self, price: DeviceArray, volume: DeviceArray, window: int) -> DeviceArray:
         """rolling_price_volume_correlation (feature/core/correlation.py:10-111) of two resident float64 series of one length."""
-        if int(window) < 1:
-            raise ValueError("window must be at least 1.")
-        return self._pair("fmk_price_volume_corr_dev", "rolling_price_volume_correlation: price and volume must have the same length.",
-                          price, volume, c_i64(int(window)))
+        return resident(self.ctx, OPS["price_volume_corr"], (price, volume), window)
 
-    # ------------------------------------------------------------------ window statistics (csrc/fmk_shape.hip)
+    # window statistics (csrc/fmk_shape.hip)
     def kurtosis(self, y: DeviceArray, window: int) -> DeviceArray:
         """rolling_kurtosis (feature/core/shape.py; reference transforms.py:900-933) of a resident float64 series."""
-        return self._series("fmk_rolling_kurtosis_dev", y, window)
+        return resident(self.ctx, OPS["rolling_kurtosis"], (y,), window)
 
     def trend_slope(self, y: DeviceArray, window: int) -> DeviceArray:
         """trend_slope (feature/core/shape.py; reference transforms.py:936-988) of a resident float64 price series, in degrees."""
-        return self._series("fmk_trend_slope_dev", y, window)
+        return resident(self.ctx, OPS["trend_slope"], (y,), window)
 
     def hurst_exponent(self, y: DeviceArray, window: int) -> DeviceArray:
         """hurst_exponent (feature/core/shape.py; reference transforms.py:1341-1397) of a resident float64 series; ValueError when
         window < 9."""
-        if int(window) < 1:
-            raise ValueError("window must be at least 1.")
-        return self._series("fmk_hurst_exponent_dev", y, window, least=9, message="hurst_exponent: window must be at least 9.")
+        return resident(self.ctx, OPS["hurst_exponent"], (y,), window)
 
     def bipower_variation(self, y: DeviceArray, window: int) -> DeviceArray:
         """bipower_variation (feature/core/shape.py; reference transforms.py:1551-1602) of a resident float64 series."""
-        return self._series("fmk_bipower_variation_dev", y, window)
+        return resident(self.ctx, OPS["bipower_variation"], (y,), window)
 
-    # ------------------------------------------------------------------ approximate entropy (csrc/fmk_entropy.hip)
+    # approximate entropy (csrc/fmk_entropy.hip)
     def approximate_entropy(self, y: DeviceArray, window: int, m: int = 2, tolerance: float = 0.2) -> DeviceArray:
         """approximate_entropy (feature/core/entropy.py; reference transforms.py:1400-1457) of a resident float64 series; ValueError
         for the arguments that function refuses."""
-        from .feature.core.entropy import check_arguments
-        check_arguments(window, m, tolerance)
-        return self._series("fmk_approximate_entropy_dev", y, window, c_i64(int(m)), c_f64(float(tolerance)))
+        return resident(self.ctx, OPS["approximate_entropy"], (y,), window, m, tolerance)
 
     # ------------------------------------------------------------------ event sampling
     def cusum_filter(self, threshold, series: Optional[DeviceArray] = None) -> DeviceArray:

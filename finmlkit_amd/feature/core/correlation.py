@@ -4,11 +4,7 @@ from __future__ import annotations
 import numpy as np
 from numpy.typing import NDArray
 
-from ... import _ffi
-from ..._ffi import c_i64, ptr
-
-WINDOW_MESSAGE = "window must be at least 1."
-SHAPE_MESSAGE = "rolling_price_volume_correlation: price and volume must be one-dimensional and of the same length."
+from ..series_ops import CORR_SHAPE_MESSAGE as SHAPE_MESSAGE, OPS, WINDOW_MESSAGE, host  # noqa: F401
 
 
 def rolling_price_volume_correlation(price: NDArray[np.float64], volume: NDArray[np.float64], window: int) -> NDArray[np.float64]:
@@ -24,12 +20,4 @@ def rolling_price_volume_correlation(price: NDArray[np.float64], volume: NDArray
     it is before 3.12 and what Numba compiles).  Departures, where the reference is undefined: `window < 1` (it indexes from the
     end of the arrays) and unequal lengths (IndexError, or a short read) raise ValueError; an empty series returns an empty array
     (the reference raises IndexError)."""
-    if int(window) < 1:
-        raise ValueError(WINDOW_MESSAGE)
-    p, v = (np.ascontiguousarray(a, dtype=np.float64) for a in (price, volume))
-    if not (p.ndim == v.ndim == 1 and len(p) == len(v)):
-        raise ValueError(SHAPE_MESSAGE)
-    out = np.empty(len(p), np.float64)
-    if len(p):
-        _ffi.default_context().call("fmk_price_volume_corr", ptr(p), ptr(v), c_i64(len(p)), c_i64(int(window)), ptr(out))
-    return out
+    return host(OPS["price_volume_corr"], (price, volume), window)

@@ -5,35 +5,22 @@ from __future__ import annotations
 import numpy as np
 from numpy.typing import NDArray
 
-from ... import _ffi
-from ..._ffi import c_i64, ptr
-from .ma import series_call
-
-PERIOD_MESSAGE = "roc: period must not be negative."
-LENGTH_MESSAGE = "stoch_k: length must be at least 1."
-RSI_WINDOW_MESSAGE = "rsi_wilder: window must be at least 1."
-SHAPE_MESSAGE = "stoch_k: close, low and high must have the same length."
+from ..series_ops import OPS, host
+from ..series_ops import (ROC_PERIOD_MESSAGE as PERIOD_MESSAGE, RSI_WINDOW_MESSAGE, STOCH_LENGTH_MESSAGE as LENGTH_MESSAGE,  # noqa: F401
+                          STOCH_SHAPE_MESSAGE as SHAPE_MESSAGE)
 
 
 def roc(price: NDArray, period: int) -> NDArray:
     """Reference: finmlkit/feature/core/momentum.py:6-22: ((price[i] - price[i - period]) / price[i - period]) * 100, NaN before
     `period`; a zero divisor gives the IEEE result."""
-    return series_call("fmk_roc", price, period, least=0, message=PERIOD_MESSAGE)
+    return host(OPS["roc"], (price,), period)
 
 
 def stoch_k(close: NDArray[np.float64], low: NDArray[np.float64], high: NDArray[np.float64], length: int) -> NDArray[np.float64]:
     """Reference: finmlkit/feature/core/momentum.py:68-112: (100 * (close[t] - lo)) / (hi - lo) with lo / hi the minimum of `low` /
     maximum of `high` over the `length` bars ending at t, NaN where hi <= lo, where the window holds a NaN in `low` or `high`, and
     before the first full window."""
-    if int(length) < 1:
-        raise ValueError(LENGTH_MESSAGE)
-    c, lo, hi = (np.ascontiguousarray(a, dtype=np.float64) for a in (close, low, high))
-    if not (c.ndim == lo.ndim == hi.ndim == 1 and len(c) == len(lo) == len(hi)):
-        raise ValueError(SHAPE_MESSAGE)
-    out = np.empty(len(c), np.float64)
-    if len(c):
-        _ffi.default_context().call("fmk_stoch_k", ptr(c), ptr(lo), ptr(hi), c_i64(len(c)), c_i64(int(length)), ptr(out))
-    return out
+    return host(OPS["stoch_k"], (close, low, high), length)
 
 
 def rsi_wilder(close: NDArray[np.float64], window: int) -> NDArray[np.float64]:
@@ -46,4 +33,4 @@ def rsi_wilder(close: NDArray[np.float64], window: int) -> NDArray[np.float64]:
     averages have taken a non-zero term again: there the reference stalls at the smallest subnormal for windows of 3 and more (and
     reads 50.0, 0.0 or 100.0 off it for good) and reaches 0.0 at windows 1 and 2 (NaN), while the scan's composed state underflows to
     0.0 at every window (NaN until the next loss).  tests/test_gpu_recur_runs.py pins both sides of that line."""
-    return series_call("fmk_rsi_wilder", close, window, message=RSI_WINDOW_MESSAGE)
+    return host(OPS["rsi_wilder"], (close,), window)

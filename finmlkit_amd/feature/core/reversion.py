@@ -1,16 +1,10 @@
 """Drop-in for finmlkit/feature/core/reversion.py::vwap_distance, computed on the MI355X (csrc/fmk_runsum.hip)."""
 from __future__ import annotations
 
-import ctypes as C
-
 import numpy as np
 from numpy.typing import NDArray
 
-from ... import _ffi
-from ..._ffi import c_i64, ptr
-
-PERIODS_MESSAGE = "vwap_distance: n_periods must be at least 1."
-SHAPE_MESSAGE = "vwap_distance: close and volume must have the same length."
+from ..series_ops import OPS, VWAP_PERIODS_MESSAGE as PERIODS_MESSAGE, VWAP_SHAPE_MESSAGE as SHAPE_MESSAGE, host  # noqa: F401
 
 
 def vwap_distance(close: NDArray[np.float64], volume: NDArray[np.float64], n_periods: int, is_log: bool) -> NDArray[np.float64]:
@@ -23,13 +17,4 @@ def vwap_distance(close: NDArray[np.float64], volume: NDArray[np.float64], n_per
     reference on exactly summable inputs, NaN positions and which outputs are held included; otherwise within a few units in the
     last place of the largest running sum.  Outside the contract: infinite inputs, and on inputs that are not
     exactly summable whether a window of all-zero volumes holds (the reference's vsum there is a residue, not 0)."""
-    if int(n_periods) < 1:
-        raise ValueError(PERIODS_MESSAGE)
-    c, v = (np.ascontiguousarray(a, dtype=np.float64) for a in (close, volume))
-    if not (c.ndim == v.ndim == 1 and len(c) == len(v)):
-        raise ValueError(SHAPE_MESSAGE)
-    out = np.empty(len(c), np.float64)
-    if len(c):
-        _ffi.default_context().call("fmk_vwap_distance", ptr(c), ptr(v), c_i64(len(c)), c_i64(int(n_periods)), C.c_int(bool(is_log)),
-                                    ptr(out))
-    return out
+    return host(OPS["vwap_distance"], (close, volume), n_periods, is_log)

@@ -8,23 +8,20 @@ from __future__ import annotations
 import numpy as np
 from numpy.typing import NDArray
 
-from .ma import WINDOW_MESSAGE, series_call  # noqa: F401 -- WINDOW_MESSAGE is part of this module's interface
-
-HURST_MIN_WINDOW = 9
-HURST_WINDOW_MESSAGE = "hurst_exponent: window must be at least 9."
+from ..series_ops import HURST_MIN_WINDOW, HURST_WINDOW_MESSAGE, OPS, WINDOW_MESSAGE, host  # noqa: F401 -- part of this module's interface
 
 
 def rolling_kurtosis(x: NDArray[np.float64], window: int) -> NDArray[np.float64]:
     """Excess kurtosis of x[t-window+1 .. t] in scipy's biased Fisher form: `m4 / (m2 * m2) - 3` of the central moments about the
     window's mean.  NaN before the first full window and where `m2 == 0` (every window at `window = 1`)."""
-    return series_call("fmk_rolling_kurtosis", x, window)
+    return host(OPS["rolling_kurtosis"], (x,), window)
 
 
 def trend_slope(x: NDArray[np.float64], window: int) -> NDArray[np.float64]:
     """The least-squares slope of `ln x` over t-window+1 .. t on the positions 0 .. window-1, as an angle in degrees:
     `atan(slope) * 180 / pi`.  NaN before the first full window, where a price of the window is not finite and > 0, and at
     `window = 1`."""
-    return series_call("fmk_trend_slope", x, window)
+    return host(OPS["trend_slope"], (x,), window)
 
 
 def hurst_exponent(x: NDArray[np.float64], window: int) -> NDArray[np.float64]:
@@ -32,12 +29,10 @@ def hurst_exponent(x: NDArray[np.float64], window: int) -> NDArray[np.float64]:
     consecutive elements after the window's first, k = 1, 2, 4, 8, the least-squares slope of `ln tau_k` on `ln k`; NaN where a
     tau_k is not > 0 (every window at `window = 9`) and where an element of the window, the first included, is not finite.
     `window < 9` raises ValueError (the reference raises TypeError out of polyfit)."""
-    if int(window) < 1:
-        raise ValueError(WINDOW_MESSAGE)
-    return series_call("fmk_hurst_exponent", x, window, least=HURST_MIN_WINDOW, message=HURST_WINDOW_MESSAGE)
+    return host(OPS["hurst_exponent"], (x,), window)
 
 
 def bipower_variation(x: NDArray[np.float64], window: int) -> NDArray[np.float64]:
     """`sqrt(pi / 2) * sum(|x[j]| * |x[j-1]|, j = t-window+1 .. t)`: `window` products over the window + 1 elements x[t-window .. t],
     so the first output is at `t = window`, one later than the other three."""
-    return series_call("fmk_bipower_variation", x, window)
+    return host(OPS["bipower_variation"], (x,), window)

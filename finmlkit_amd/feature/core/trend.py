@@ -1,13 +1,7 @@
 """Drop-in for finmlkit/feature/core/trend.py::adx_core, computed on the MI355X (csrc/fmk_recur.hip)."""
 from __future__ import annotations
 
-import numpy as np
-
-from ... import _ffi
-from ..._ffi import c_i64, ptr
-
-LENGTH_MESSAGE = "adx_core: length must be at least 1."
-SHAPE_MESSAGE = "adx_core: high, low and close must have the same length."
+from ..series_ops import ADX_LENGTH_MESSAGE as LENGTH_MESSAGE, ADX_SHAPE_MESSAGE as SHAPE_MESSAGE, OPS, host  # noqa: F401
 
 
 def adx_core(high, low, close, length):
@@ -20,12 +14,4 @@ def adx_core(high, low, close, length):
     stall at the smallest subnormals for lengths of 3 and more (0.0 at lengths 1 and 2) and dx is a quotient of those, the scan's
     composed sums underflow to 0.0 and dx is 0.0; this ends once each sum has taken a non-zero term and the last average has
     forgotten those dx (100 * (1 - 1 / length)^t after t bars).  DESIGN.md section 7e; tests/test_gpu_recur_runs.py pins it."""
-    if int(length) < 1:
-        raise ValueError(LENGTH_MESSAGE)
-    h, lo, c = (np.ascontiguousarray(a, dtype=np.float64) for a in (high, low, close))
-    if not (h.ndim == lo.ndim == c.ndim == 1 and len(h) == len(lo) == len(c)):
-        raise ValueError(SHAPE_MESSAGE)
-    out = np.empty(len(h), np.float64)
-    if len(h):
-        _ffi.default_context().call("fmk_adx", ptr(h), ptr(lo), ptr(c), c_i64(len(h)), c_i64(int(length)), ptr(out))
-    return out
+    return host(OPS["adx"], (high, low, close), length)

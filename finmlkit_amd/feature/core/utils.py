@@ -9,9 +9,7 @@ from numpy.typing import NDArray
 
 from ... import _ffi
 from ..._ffi import c_f64, c_i64, ptr
-from .ma import series_call
-
-PERIODS_MESSAGE = "pct_change: periods must not be negative."
+from ..series_ops import OPS, PCT_PERIODS_MESSAGE as PERIODS_MESSAGE, host  # noqa: F401 -- the message is part of this module's interface
 
 
 def comp_lagged_returns(timestamps: NDArray[np.int64], close: NDArray[np.float64], return_window_sec: float,
@@ -32,18 +30,16 @@ def comp_zscore(x: NDArray[np.float64], window: int, ddof: int) -> NDArray[np.fl
     """Reference: finmlkit/feature/core/utils.py:67-90: (x[i] - mean) / std of the window ending at i, mean and the squared deviations
     summed left to right, NaN where std == 0 and before the first full window.  `window - ddof <= 0` raises ValueError (the
     reference divides by zero or takes the root of a negative number there)."""
-    if int(window) >= 1 and int(window) - int(ddof) <= 0:
-        raise ValueError("comp_zscore: window - ddof must be positive.")
-    return series_call("fmk_zscore", x, window, c_i64(int(ddof)))
+    return host(OPS["zscore"], (x,), window, ddof)
 
 
 def comp_burst_ratio(series: NDArray[np.float64], window: int) -> NDArray[np.float64]:
     """Reference: finmlkit/feature/core/utils.py:92-108: series[i] / np.median(the window ending at i) where that median is > 0,
     NaN elsewhere, where the window holds a NaN, and before the first full window (csrc/fmk_order.hip)."""
-    return series_call("fmk_burst_ratio", series, window)
+    return host(OPS["burst_ratio"], (series,), window)
 
 
 def pct_change(x: NDArray[np.float64], periods: int) -> NDArray[np.float64]:
     """Reference: finmlkit/feature/core/utils.py:110-124: (x[t] - base) / base with base = x[t - periods] where base > 0, NaN
     elsewhere and before `periods`."""
-    return series_call("fmk_pct_change", x, periods, least=0, message=PERIODS_MESSAGE)
+    return host(OPS["pct_change"], (x,), periods)

@@ -14,7 +14,7 @@ from numpy.typing import NDArray
 
 from ... import _ffi
 from ..._ffi import c_f64, c_i64, ptr
-from .ma import series_call
+from ..series_ops import ATR_WINDOW_MESSAGE, BOLLINGER_WINDOW_MESSAGE, HLC_MESSAGE, OPS, PARKINSON_MESSAGE, host  # noqa: F401
 
 
 def _ewmst(timestamps, y, half_life, sigma_floor, mean0):
@@ -62,34 +62,19 @@ def realized_vol(r: NDArray[np.float64], window: int, is_sample: bool) -> NDArra
 def rolling_variance_nb(series: NDArray[np.float64], window: int, ddof: int = 1, min_periods: int = 1) -> NDArray[np.float64]:
     """Reference: finmlkit/feature/core/volatility.py:440-478: per window the count, sum and sum of squares of the non-NaN
     elements, max(0, (sum_sq / cnt - mean^2) * (cnt / (cnt - ddof))) when cnt >= min_periods and cnt > ddof, NaN otherwise."""
-    return series_call("fmk_rolling_variance", series, window, c_i64(int(ddof)), c_i64(int(min_periods)))
+    return host(OPS["rolling_variance"], (series,), window, ddof, min_periods)
 
 
 def variance_ratio_1_4_core(price: NDArray[np.float64], window: int, ddof: int, ret_type: str) -> NDArray[np.float64]:
     """Reference: finmlkit/feature/core/volatility.py:481-540: var(1-step returns) / (var(4-step returns) / 4) over `window`;
     `ret_type` "log" takes log returns (the host's log), anything else simple returns."""
-    return series_call("fmk_variance_ratio_1_4", price, window, c_i64(int(ddof)), C.c_int(ret_type == "log"))
-
-
-HLC_MESSAGE = "The length of high, low, and close prices must be the same."
-ATR_WINDOW_MESSAGE = "atr: window must not be negative."
-
-
-def _hlc(high, low, close):
-    h, lo, c = (np.ascontiguousarray(a, dtype=np.float64) for a in (high, low, close))
-    if not (h.ndim == lo.ndim == c.ndim == 1 and len(h) == len(lo) == len(c)):
-        raise ValueError(HLC_MESSAGE)
-    return h, lo, c
+    return host(OPS["variance_ratio_1_4"], (price,), window, ddof, ret_type == "log")
 
 
 def true_range(high: NDArray, low: NDArray, close: NDArray) -> NDArray:
     """Reference: finmlkit/feature/core/volatility.py:222-253: max(high - low, |high - close[i-1]|, |low - close[i-1]|), NaN where
     one of the three inputs is; bar 0 is high - low.  The reference's bits."""
-    h, lo, c = _hlc(high, low, close)
-    out = np.empty(len(h), np.float64)
-    if len(h):
-        _ffi.default_context().call("fmk_true_range", ptr(h), ptr(lo), ptr(c), c_i64(len(h)), ptr(out))
-    return out
+    return host(OPS["true_range"], (high, low, close))
 
 
 def atr(high: NDArray[np.float64], low: NDArray[np.float64], close: NDArray[np.float64], window: int, ema_based: bool = False,
@@ -103,18 +88,7 @@ def atr(high: NDArray[np.float64], low: NDArray[np.float64], close: NDArray[np.f
     reaches 0.0 at windows 1 and 2, the scan's composed state underflows to 0.0 (DESIGN.md section 7e;
     tests/test_gpu_recur_runs.py pins it).  `normalize` divides by (high + low) / 2.0.  Window 0 gives NaN everywhere, as the reference;
     a negative window raises ValueError."""
-    if int(window) < 0:
-        raise ValueError(ATR_WINDOW_MESSAGE)
-    h, lo, c = _hlc(high, low, close)
-    out = np.empty(len(h), np.float64)
-    if len(h):
-        _ffi.default_context().call("fmk_atr", ptr(h), ptr(lo), ptr(c), c_i64(len(h)), c_i64(int(window)), C.c_int(bool(ema_based)),
-                                    C.c_int(bool(normalize)), ptr(out))
-    return out
-
-
-BOLLINGER_WINDOW_MESSAGE = "bollinger_percent_b: window must be at least 1."
-PARKINSON_MESSAGE = "parkinson_range: high and low must have the same length."
+    return host(OPS["atr"], (high, low, close), window, ema_based, normalize)
 
 
 def bollinger_percent_b(close: NDArray[np.float64], window: int, num_std: float) -> NDArray[np.float64]:
@@ -126,18 +100,10 @@ def bollinger_percent_b(close: NDArray[np.float64], window: int, num_std: float)
     cancels the outputs agree within a few 2^-52 * sumsq / ((window - 1) * var).  Outside the contract:
     infinite prices, and on prices that are not exactly summable a window whose elements are all equal (the reference's
     NaN-or-number there is rounding noise)."""
-    if int(window) < 1:
-        raise ValueError(BOLLINGER_WINDOW_MESSAGE)
-    return series_call("fmk_bollinger_percent_b", close, window, c_f64(float(num_std)), message=BOLLINGER_WINDOW_MESSAGE)
+    return host(OPS["bollinger_percent_b"], (close,), window, num_std)
 
 
 def parkinson_range(high: NDArray[np.float64], low: NDArray[np.float64]) -> NDArray[np.float64]:
     """Reference: finmlkit/feature/core/volatility.py:341-349: log(high / low) ** 2 / (log(2.0) * 4.0) with the host's log, the
     reference's bits: inf where low is 0, NaN where an input is NaN or the ratio negative.  Unequal lengths raise ValueError."""
-    h, lo = (np.ascontiguousarray(a, dtype=np.float64) for a in (high, low))
-    if not (h.ndim == lo.ndim == 1 and len(h) == len(lo)):
-        raise ValueError(PARKINSON_MESSAGE)
-    out = np.empty(len(h), np.float64)
-    if len(h):
-        _ffi.default_context().call("fmk_parkinson_range", ptr(h), ptr(lo), c_i64(len(h)), ptr(out))
-    return out
+    return host(OPS["parkinson_range"], (high, low))

@@ -18,6 +18,7 @@ from numpy.typing import NDArray
 
 from ... import _ffi
 from ..._ffi import c_f64, c_i64, ptr
+from ..series_ops import OPS, RECENT_MESSAGE, VPIN_SHAPE_MESSAGE, VPIN_WINDOW_MESSAGE, host  # noqa: F401 -- this module's interface
 
 
 def _to_csr(price_levels: Sequence, buy_volumes: Sequence, sell_volumes: Sequence):
@@ -190,11 +191,6 @@ class VolumePro:
         return (sub.bar_timestamps,) + self.compute(bars_sub, sub)
 
 
-RECENT_MESSAGE = "comp_flow_acceleration: recent_periods must not be negative."
-VPIN_WINDOW_MESSAGE = "vpin: window must not be negative."
-VPIN_SHAPE_MESSAGE = "vpin: volume_buy and volume_sell must have the same length."
-
-
 def comp_flow_acceleration(volumes: NDArray[np.float64], window: int, recent_periods: int) -> NDArray[np.float64]:
     """Reference: finmlkit/feature/core/volume.py:572-607: log((recent + 1e-12) / (past + 1e-12)) with the host's log, `recent` the
     volume of the last `recent_periods` bars and `past` that of the window's other bars, both differences of the prefix sum S.
@@ -202,14 +198,7 @@ def comp_flow_acceleration(volumes: NDArray[np.float64], window: int, recent_per
     window < 1 included).  recent_periods 0 is valid; a negative one raises ValueError.  The prefix sum is a device-wide scan
     with the coefficient 1: bit for bit the reference on exactly summable volumes, otherwise within a few units in the last place
     of S.  Infinite volumes are outside the contract."""
-    if int(recent_periods) < 0:
-        raise ValueError(RECENT_MESSAGE)
-    v = np.ascontiguousarray(volumes, dtype=np.float64)
-    out = np.empty(len(v), np.float64)
-    if len(v):
-        _ffi.default_context().call("fmk_flow_acceleration", ptr(v), c_i64(len(v)), c_i64(int(window)), c_i64(int(recent_periods)),
-                                    ptr(out))
-    return out
+    return host(OPS["flow_acceleration"], (volumes,), window, recent_periods)
 
 
 def vpin(volume_buy, volume_sell, window):
@@ -219,12 +208,4 @@ def vpin(volume_buy, volume_sell, window):
     as the reference; a negative window and unequal lengths raise ValueError.  The prefix sums are a device-wide scan with the
     coefficient 1: equal to the reference as float32, but for one float32 unit in the last place where the float64 quotient sits
     on a rounding boundary.  Infinite volumes are outside the contract."""
-    if int(window) < 0:
-        raise ValueError(VPIN_WINDOW_MESSAGE)
-    b, s = (np.ascontiguousarray(a, dtype=np.float64) for a in (volume_buy, volume_sell))
-    if not (b.ndim == s.ndim == 1 and len(b) == len(s)):
-        raise ValueError(VPIN_SHAPE_MESSAGE)
-    out = np.empty(len(b), np.float32)
-    if len(b):
-        _ffi.default_context().call("fmk_vpin", ptr(b), ptr(s), c_i64(len(b)), c_i64(int(window)), ptr(out))
-    return out
+    return host(OPS["vpin"], (volume_buy, volume_sell), window)

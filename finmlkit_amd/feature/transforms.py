@@ -28,16 +28,13 @@ from .. import _ffi
 from .._ffi import DeviceArray, c_f64, c_i64
 from .core.structural_break.cusum import cusum_test_rolling
 from .core.correlation import rolling_price_volume_correlation
-from .core.entropy import approximate_entropy, check_arguments as check_entropy_arguments
-from .core.ma import SPAN_MESSAGE, ewma, sma
-from .core.momentum import LENGTH_MESSAGE, PERIOD_MESSAGE, RSI_WINDOW_MESSAGE, roc, rsi_wilder, stoch_k
+from .core.momentum import LENGTH_MESSAGE, stoch_k
 from .core.trend import adx_core
-from .core.utils import PERIODS_MESSAGE, comp_burst_ratio, comp_lagged_returns, comp_zscore, pct_change
+from .core.utils import comp_lagged_returns
 from .core.reversion import vwap_distance
-from .core.shape import HURST_MIN_WINDOW, HURST_WINDOW_MESSAGE, bipower_variation, hurst_exponent, rolling_kurtosis, trend_slope
-from .core.volatility import (BOLLINGER_WINDOW_MESSAGE, atr, bollinger_percent_b, ewmst, parkinson_range, realized_vol,
-                              variance_ratio_1_4_core)
-from .core.volume import RECENT_MESSAGE, comp_flow_acceleration, vpin
+from .core.volatility import atr, ewmst, parkinson_range, realized_vol
+from .core.volume import vpin
+from .series_ops import OPS, host, resident
 
 
 class SISOTransform:
@@ -144,65 +141,47 @@ class RealizedVolatility(SISOTransform):
         return out
 
 
-class _Rolling(SISOTransform):
-    """A rolling-window moment (csrc/fmk_rolling.hip): `_host` is the NumPy-level function, `_entry` the device entry point, and
-    `_args()` what both take after the window."""
-    _host = None
-    _entry = ""
+class _SeriesOp(SISOTransform):
+    """A transform over one row of series_ops.OPS: `_op` names the row, `_params()` gives the row's scalars in ABI order.  The
+    NumPy form and the device form used by `Compose` are that row's two drivers."""
+    _op = ""
 
-    def _args(self):
-        return ()
-
-    def _c_args(self):
-        return tuple(c_i64(int(v)) for v in self._args())
+    def _params(self):
+        return (self.window,)
 
     def _hip(self, x):
-        res = type(self)._host(np.asarray(self._prepare_input_nb(x), dtype=np.float64), self.window, *self._args())
-        return self._prepare_output_nb(x.index, res)
+        return self._prepare_output_nb(x.index, host(OPS[self._op], (self._prepare_input_nb(x),), *self._params()))
 
     def _dev(self, ts, y):
-        if int(self.window) < 1:
-            raise ValueError("window must be at least 1.")
-        out = DeviceArray(ts.ctx, y.n, np.float64)
-        if y.n:
-            ts.ctx.call(self._entry, y.p, c_i64(y.n), c_i64(int(self.window)), *self._c_args(), out.p)
-        return out
+        return resident(ts.ctx, OPS[self._op], (y,), *self._params())
 
 
-class SMA(_Rolling):
+class SMA(_SeriesOp):
     """Simple moving average (reference transforms.py:549-574; the reference's "pd" backend is pandas' rolling mean, this is its
     Numba kernel on either backend)."""
-    _host = staticmethod(sma)
-    _entry = "fmk_sma_dev"
+    _op = "sma"
 
     def __init__(self, window: int, input_col: str = "x"):
         super().__init__(input_col, f"sma{window}")
         self.window = window
 
 
-class ZScore(_Rolling):
+class ZScore(_SeriesOp):
     """Rolling z-score (reference transforms.py:335-359)."""
-    _host = staticmethod(comp_zscore)
-    _entry = "fmk_zscore_dev"
+    _op = "zscore"
 
     def __init__(self, window: int, input_col: str, ddof: int = 0):
         super().__init__(input_col, f"z{window}")
         self.window = window
         self.ddof = ddof
 
-    def _args(self):
-        return (self.ddof,)
-
-    def _dev(self, ts, y):
-        if int(self.window) >= 1 and int(self.window) - int(self.ddof) <= 0:
-            raise ValueError("comp_zscore: window - ddof must be positive.")
-        return super()._dev(ts, y)
+    def _params(self):
+        return (self.window, self.ddof)
 
 
-class VarianceRatio14(_Rolling):
+class VarianceRatio14(_SeriesOp):
     """var(1-step returns) / (var(4-step returns) / 4) (reference transforms.py:867-897)."""
-    _host = staticmethod(variance_ratio_1_4_core)
-    _entry = "fmk_variance_ratio_1_4_dev"
+    _op = "variance_ratio_1_4"
 
     def __init__(self, window: int = 32, input_col: str = "close", ret_type: str = "log", ddof: int = 0):
         super().__init__(input_col, f"var_ratio_1_4_{window}")
@@ -210,77 +189,63 @@ class VarianceRatio14(_Rolling):
         self.ret_type = ret_type
         self.ddof = ddof
 
-    def _args(self):
-        return (self.ddof, self.ret_type)
-
-    def _c_args(self):
-        return (c_i64(int(self.ddof)), C.c_int(self.ret_type == "log"))
+    def _params(self):
+        return (self.window, self.ddof, self.ret_type == "log")
 
 
-class BurstRatio(_Rolling):
+class BurstRatio(_SeriesOp):
     """series / rolling median (reference transforms.py:362-385)."""
-    _host = staticmethod(comp_burst_ratio)
-    _entry = "fmk_burst_ratio_dev"
+    _op = "burst_ratio"
 
     def __init__(self, window: int, input_col: str):
         super().__init__(input_col, f"burst{window}")
         self.window = window
 
 
-class KurtosisTransform(_Rolling):
+class KurtosisTransform(_SeriesOp):
     """Rolling excess kurtosis (reference transforms.py:900-933: scipy's biased Fisher form under pandas' rolling.apply)."""
-    _host = staticmethod(rolling_kurtosis)
-    _entry = "fmk_rolling_kurtosis_dev"
+    _op = "rolling_kurtosis"
 
     def __init__(self, window: int = 32, input_col: str = "ret1"):
         super().__init__(input_col, f"kurt_{window}")
         self.window = window
 
 
-class TrendSlope(_Rolling):
+class TrendSlope(_SeriesOp):
     """The least-squares slope of ln(close) over the window as an angle in degrees (reference transforms.py:936-988: a Python loop
     around scipy's linregress)."""
-    _host = staticmethod(trend_slope)
-    _entry = "fmk_trend_slope_dev"
+    _op = "trend_slope"
 
     def __init__(self, window: int = 24, input_col: str = "close"):
         super().__init__(input_col, f"trend_slope_{window}")
         self.window = window
 
 
-class HurstExponent(_Rolling):
+class HurstExponent(_SeriesOp):
     """The aggregated-variance Hurst exponent over lags 1, 2, 4, 8 (reference transforms.py:1341-1397).  `window < 9` raises
     ValueError when the transform is applied; the reference raises TypeError out of polyfit there."""
-    _host = staticmethod(hurst_exponent)
-    _entry = "fmk_hurst_exponent_dev"
+    _op = "hurst_exponent"
 
     def __init__(self, window: int = 24, input_col: str = "ret1"):
         super().__init__(input_col, f"hurst{window}")
         self.window = window
 
-    def _dev(self, ts, y):
-        if 1 <= int(self.window) < HURST_MIN_WINDOW:
-            raise ValueError(HURST_WINDOW_MESSAGE)
-        return super()._dev(ts, y)
 
-
-class BiPowerVariation(_Rolling):
+class BiPowerVariation(_SeriesOp):
     """Bi-power variation: sqrt(pi / 2) times the sum of `window` products of consecutive absolute returns (reference
     transforms.py:1551-1602); the first output is at index `window`."""
-    _host = staticmethod(bipower_variation)
-    _entry = "fmk_bipower_variation_dev"
+    _op = "bipower_variation"
 
     def __init__(self, window: int = 12, input_col: str = "ret1"):
         super().__init__(input_col, f"bv_{window}")
         self.window = window
 
 
-class ApproximateEntropy(_Rolling):
+class ApproximateEntropy(_SeriesOp):
     """Rolling approximate entropy (reference transforms.py:1400-1457: pandas' rolling.apply around antropy.app_entropy with the
     Chebyshev metric and the tolerance `tolerance * std(window)`).  Refused arguments raise ValueError when the transform is
     applied (core/entropy.py)."""
-    _host = staticmethod(approximate_entropy)
-    _entry = "fmk_approximate_entropy_dev"
+    _op = "approximate_entropy"
 
     def __init__(self, window: int = 24, m: int = 2, tolerance: float = 0.2, input_col: str = "ret1"):
         super().__init__(input_col, f"apen{window}")
@@ -288,24 +253,21 @@ class ApproximateEntropy(_Rolling):
         self.m = m
         self.tolerance = tolerance
 
-    def _args(self):
-        return (self.m, self.tolerance)
-
-    def _c_args(self):
-        return (c_i64(int(self.m)), c_f64(float(self.tolerance)))
-
-    def _dev(self, ts, y):
-        check_entropy_arguments(self.window, self.m, self.tolerance)
-        return super()._dev(ts, y)
+    def _params(self):
+        return (self.window, self.m, self.tolerance)
 
 
-class EWMA(SISOTransform):
+class EWMA(_SeriesOp):
     """Exponentially weighted moving average (reference transforms.py:577-602).  backend="pd" is pandas' own
     `ewm(span=span).mean()`, as in the reference (it skips NaN where the kernel propagates it)."""
+    _op = "ewma"
 
     def __init__(self, span: int, input_col: str = None):
         super().__init__(input_col, f"ewma{span}")
         self.span = span
+
+    def _params(self):
+        return (self.span,)
 
     def _pd(self, x):
         outp = x[self.requires[0]].ewm(span=self.span).mean()
@@ -317,118 +279,68 @@ class EWMA(SISOTransform):
         self._validate_input(x)
         return self._pd(x) if backend == "pd" else self._hip(x)
 
-    def _hip(self, x):
-        return self._prepare_output_nb(x.index, ewma(self._prepare_input_nb(x), self.span))
 
-    def _dev(self, ts, y):
-        if not float(self.span) >= 1.0:
-            raise ValueError(SPAN_MESSAGE)
-        out = DeviceArray(ts.ctx, y.n, np.float64)
-        if y.n:
-            ts.ctx.call("fmk_ewma_dev", y.p, c_i64(y.n), c_f64(float(self.span)), out.p)
-        return out
-
-
-class RSIWilder(_Rolling):
+class RSIWilder(_SeriesOp):
     """Wilder's relative strength index (reference transforms.py:206-273).  Both backends are the kernel.  The reference's pandas
     backend is an arithmetic of its own: it gives 100 where there is no loss, the Numba kernel and this one give NaN there."""
-    _host = staticmethod(rsi_wilder)
-    _entry = "fmk_rsi_wilder_dev"
+    _op = "rsi_wilder"
 
     def __init__(self, window: int = 14, input_col: str = "close"):
         super().__init__(input_col, f"rsiw{window}")
         self.window = window
 
-    def _dev(self, ts, y):
-        if int(self.window) < 1:
-            raise ValueError(RSI_WINDOW_MESSAGE)
-        return super()._dev(ts, y)
 
-
-class BollingerPercentB(SISOTransform):
+class BollingerPercentB(_SeriesOp):
     """Bollinger %B (reference transforms.py:494-518).  Every backend is the kernel; the reference's `_pd` falls back to Numba."""
+    _op = "bollinger_percent_b"
 
     def __init__(self, window: int, num_std: float = 2., input_col: str = "close"):
         super().__init__(input_col, f"bollb{window}")
         self.window = window
         self.num_std = num_std
 
-    def _hip(self, x):
-        res = bollinger_percent_b(np.asarray(self._prepare_input_nb(x), dtype=np.float64), self.window, self.num_std)
-        return self._prepare_output_nb(x.index, res)
-
-    def _dev(self, ts, y):
-        if int(self.window) < 1:
-            raise ValueError(BOLLINGER_WINDOW_MESSAGE)
-        out = DeviceArray(ts.ctx, y.n, np.float64)
-        if y.n:
-            ts.ctx.call("fmk_bollinger_percent_b_dev", y.p, c_i64(y.n), c_i64(int(self.window)), c_f64(float(self.num_std)), out.p)
-        return out
+    def _params(self):
+        return (self.window, self.num_std)
 
 
-class FlowAcceleration(SISOTransform):
+class FlowAcceleration(_SeriesOp):
     """Flow acceleration (reference transforms.py:605-628).  Every backend is the kernel; the reference's `_pd` falls back to
     Numba."""
+    _op = "flow_acceleration"
 
     def __init__(self, window: int, recent_periods, input_col: str = "volume"):
         super().__init__(input_col, f"flowacc_{window}_{recent_periods}")
         self.window = window
         self.recent_periods = recent_periods
 
-    def _hip(self, x):
-        res = comp_flow_acceleration(np.asarray(self._prepare_input_nb(x), dtype=np.float64), self.window, self.recent_periods)
-        return self._prepare_output_nb(x.index, res)
-
-    def _dev(self, ts, y):
-        if int(self.recent_periods) < 0:
-            raise ValueError(RECENT_MESSAGE)
-        out = DeviceArray(ts.ctx, y.n, np.float64)
-        if y.n:
-            ts.ctx.call("fmk_flow_acceleration_dev", y.p, c_i64(y.n), c_i64(int(self.window)), c_i64(int(self.recent_periods)), out.p)
-        return out
+    def _params(self):
+        return (self.window, self.recent_periods)
 
 
-class _Lagged(SISOTransform):
-    """An elementwise function of x[t] and x[t - periods] (csrc/fmk_order.hip)."""
-    _host = None
-    _entry = ""
-    _message = ""
-
-    def _hip(self, x):
-        res = type(self)._host(np.asarray(self._prepare_input_nb(x), dtype=np.float64), self.periods)
-        return self._prepare_output_nb(x.index, res)
-
-    def _dev(self, ts, y):
-        if int(self.periods) < 0:
-            raise ValueError(self._message)
-        out = DeviceArray(ts.ctx, y.n, np.float64)
-        if y.n:
-            ts.ctx.call(self._entry, y.p, c_i64(y.n), c_i64(int(self.periods)), out.p)
-        return out
-
-
-class ROC(_Lagged):
+class ROC(_SeriesOp):
     """Rate of change in percent (reference transforms.py:155-177; both backends are the kernel, as the reference's `_pd` falls
     back to Numba)."""
-    _host = staticmethod(roc)
-    _entry = "fmk_roc_dev"
-    _message = PERIOD_MESSAGE
+    _op = "roc"
 
     def __init__(self, periods: int, input_col: str = "close"):
         super().__init__(input_col, f"roc{periods}")
         self.periods = periods
 
+    def _params(self):
+        return (self.periods,)
 
-class PctChange(_Lagged):
+
+class PctChange(_SeriesOp):
     """Percentage change over a lag (reference transforms.py:180-203).  backend="pd" is pandas' own `Series.pct_change`, as in the
     reference: it divides by a base <= 0 where the kernel gives NaN, and it returns the series under the input column's name."""
-    _host = staticmethod(pct_change)
-    _entry = "fmk_pct_change_dev"
-    _message = PERIODS_MESSAGE
+    _op = "pct_change"
 
     def __init__(self, window: int, input_col: str = "close"):
         super().__init__(input_col, f"pctc{window}")
         self.periods = window
+
+    def _params(self):
+        return (self.periods,)
 
     def _pd(self, x):
         return x[self.requires[0]].pct_change(self.periods)
