@@ -59,6 +59,8 @@ struct fmk_mail {
         int lds_probe;                     // k_fp_lds_order_probe
     } fp;
     struct { unsigned long long max; unsigned status; } vp;                                    // fmk_volprofile.hip
+    // fmk_volprofile_dev.hip (k_vpd_replay): ~(range << 40 | bar of the range) of the first all-zero profile (atomicMax), status bits
+    struct Vpd { unsigned long long zero_at; unsigned status; } vpd;
     struct Ohlcv {                         // fmk_ohlcv.hip
         int saw_long;                      // a bar longer than the small kernels take (also the pipelined step's host copy)
         int64_t span[3];                   // k_list_span: listed bars, first tick, last tick

@@ -465,6 +465,39 @@ int fmk_volume_profile_rolling(fmk_ctx *ctx, const int64_t *bar_ts, const double
     return down(ctx, pct, (const float *)d_pct, n_bars);
 }
 
+int fmk_volume_profile_developing(fmk_ctx *ctx, const double *highs, const double *lows, const int64_t *level_offsets,
+                                  const int32_t *price_levels, const float *buy_volumes, const float *sell_volumes, int64_t n_bars,
+                                  const int64_t *range_starts, const int64_t *range_ends, const int64_t *out_offsets,
+                                  int64_t n_ranges, int64_t n_bins, double price_tick, double va_pct, int64_t chunk_bars,
+                                  int32_t *poc, int32_t *hva, int32_t *lva, int64_t n_out)
+{
+    if (n_bars <= 0) return fmk_set_error(ctx, FMK_E_ARG, "Input arrays should have the same length and be non-empty.");
+    for (int64_t r = 0; r < n_ranges; ++r)                        // (every other rule is the _dev entry's)
+        if (range_starts[r] < range_ends[r] && (out_offsets[r] < 0 || out_offsets[r] + (range_ends[r] - range_starts[r]) > n_out))
+            return fmk_set_error(ctx, FMK_E_ARG, "volume_profile_developing: the outputs of range %lld lie outside the %lld elements given",
+                                 (long long)r, (long long)n_out);
+    const int64_t nl = level_offsets[n_bars];
+    DevBag bag(ctx);
+    int64_t *d_off;
+    double *d_hi, *d_lo;
+    int32_t *d_pl, *d_poc, *d_hva, *d_lva;
+    float *d_b, *d_s;
+    FMK_TRY(bag.up(highs, n_bars, &d_hi));
+    FMK_TRY(bag.up(lows, n_bars, &d_lo));
+    FMK_TRY(bag.up(level_offsets, n_bars + 1, &d_off));
+    FMK_TRY(bag.up(price_levels, nl, &d_pl));
+    FMK_TRY(bag.up(buy_volumes, nl, &d_b));
+    FMK_TRY(bag.up(sell_volumes, nl, &d_s));
+    FMK_TRY(bag.up((const int32_t *)poc, n_out, &d_poc));         // elements that no range covers keep what they hold
+    FMK_TRY(bag.up((const int32_t *)hva, n_out, &d_hva));
+    FMK_TRY(bag.up((const int32_t *)lva, n_out, &d_lva));
+    FMK_TRY(fmk_volume_profile_developing_dev(ctx, d_hi, d_lo, d_off, d_pl, d_b, d_s, n_bars, range_starts, range_ends, out_offsets,
+                                              n_ranges, n_bins, price_tick, va_pct, chunk_bars, d_poc, d_hva, d_lva));
+    FMK_TRY(down(ctx, poc, (const int32_t *)d_poc, n_out));
+    FMK_TRY(down(ctx, hva, (const int32_t *)d_hva, n_out));
+    return down(ctx, lva, (const int32_t *)d_lva, n_out);
+}
+
 }  // extern "C"
 
 extern "C" {

@@ -11,11 +11,8 @@
 //   bucket_price_levels (:206-275): one lane per bin adds its levels in level order (float32);
 //   comp_poc_hva_lva (:278-369): NumPy-pairwise float32 total, first argmax, the value-area walk by lane 0 with
 //   float64 scalars (Numba-typed semantics); calc_volume_percentage_above_poc (:372-400).
-#include "fmk_footprint.h"
+#include "fmk_vp.h"
 
-#define VP_MAX_LEVELS 8192                  // widest window whose histogram lives in LDS
-#define VP_MAX_LEVELS_GLOBAL (1 << 24)      // wider windows: histogram in global scratch
-#define VP_NO_RANGE (1ull << 62)            // in place of the widest window: a window without a level range (a NaN low or high)
 #define VP_NO_RANGE_MESSAGE "a window holds a NaN low or high, or its lows / highs over price_tick are not finite: no level range " \
                             "(the reference's int(round(nan)) raises here)"
 
@@ -72,10 +69,6 @@ __global__ __launch_bounds__(256) void k_vp_windows(const int64_t *__restrict__ 
         atomicMax(max_levels, (unsigned long long)L);
 }
 
-// status bits written to *status
-#define VP_BAD_LEVEL 1      // a footprint level outside its window's range
-#define VP_ONE_LEVEL 2      // bucketing a window that spans a single level (the reference raises there)
-
 template <bool GLOBAL>
 __global__ __launch_bounds__(256) void k_volume_profile(const int64_t *__restrict__ ts, const double *__restrict__ highs,
                                                         const double *__restrict__ lows,
@@ -109,123 +102,26 @@ __global__ __launch_bounds__(256) void k_volume_profile(const int64_t *__restric
         for (int k = lane; k < L; k += 64) { ab[k] = 0.f; as[k] = 0.f; }
         __builtin_amdgcn_wave_barrier();
         // ---- aggregate_footprint: bars in order, lanes across the (distinct) levels of a bar
-        bool bad = false;
-        // (the CSR offsets of up to 63 bars by one coalesced load, a bar's first 64 levels fetched while the previous bar is added)
-        for (int64_t t0 = s; t0 < e; t0 += 63) {
-            const int nbar = (int)(e - t0 < 63 ? e - t0 : 63);
-            const int64_t my_off = lane <= nbar ? off[t0 + lane] : 0;
-            int64_t r0 = fmk_readlane(my_off, 0), r1 = fmk_readlane(my_off, 1);
-            int lv = 0;
-            float bv = 0.f, sv = 0.f;
-            bool has = r0 + lane < r1;
-            if (has) { lv = levels[r0 + lane]; bv = buy[r0 + lane]; sv = sell[r0 + lane]; }
-            for (int q = 0; q < nbar; ++q) {
-                const int64_t c0 = r0, c1 = r1;
-                const int clv = lv;
-                const float cbv = bv, csv = sv;
-                const bool chas = has;
-                if (q + 1 < nbar) {                               // the next bar's first rows, in flight during the adds below
-                    r0 = r1; r1 = fmk_readlane(my_off, q + 2);
-                    has = r0 + lane < r1;
-                    if (has) { lv = levels[r0 + lane]; bv = buy[r0 + lane]; sv = sell[r0 + lane]; }
-                }
-                if (chas) {
-                    const int64_t idx = (int64_t)clv - minl;
-                    if (idx < 0 || idx >= L) bad = true;
-                    else { ab[idx] += cbv; as[idx] += csv; }      // float32 += float32, one add per level per bar
-                }
-                for (int64_t r = c0 + 64 + lane; r < c1; r += 64) {
-                    const int64_t idx = (int64_t)levels[r] - minl;
-                    if (idx < 0 || idx >= L) { bad = true; continue; }
-                    ab[idx] += buy[r];
-                    as[idx] += sell[r];
-                }
-                __builtin_amdgcn_wave_barrier();
-            }
-        }
+        const bool bad = vp_add_bars(off, levels, buy, sell, s, e, minl, L, ab, as, lane, [](int64_t) {});
         if (__ballot(bad) != 0 && lane == 0) atomicOr(status, VP_BAD_LEVEL);
         for (int k = lane; k < L; k += 64) ab[k] = ab[k] + as[k];  // total_volumes = buy + sell (float32)
         __builtin_amdgcn_wave_barrier();
         // ---- bucket_price_levels
         float *vol = ab;
         int np_ = L;
-        int64_t bw = 1, nbk = 0;
+        VpPrices pl{minl, maxl, 1, 0, false};
         if (n_bins >= 0) {
-            const int64_t range = maxl - minl;
-            bw = range / n_bins;
-            if (bw < 1) bw = 1;
-            if (bw % 2 == 0) bw += 1;
-            const int64_t n_edges = (range + bw + bw - 1) / bw;   // len(arange(min, max + bw, bw))
-            nbk = n_edges - 1;
-            if (n_edges < 2) { if (lane == 0) atomicOr(status, VP_ONE_LEVEL); continue; }
-            np_ = (int)(nbk + ((range / bw >= nbk) ? 1 : 0));     // + leftover bin iff the last level falls past the bins
-            for (int b = lane; b < np_; b += 64) {
-                const int64_t k0 = (int64_t)b * bw;
-                const int64_t k1 = (b == nbk) ? L : (k0 + bw < L ? k0 + bw : L);
-                float acc = 0.f;
-                for (int64_t k = k0; k < k1; ++k) acc += ab[k];   // float32 adds in level order (volume.py:262-270)
-                as[b] = acc;
-            }
-            __builtin_amdgcn_wave_barrier();
+            np_ = vp_bucket(ab, minl, maxl, n_bins, false, as, lane, pl);
+            if (np_ == 0) { if (lane == 0) atomicOr(status, VP_ONE_LEVEL); continue; }
             vol = as;
         }
         // ---- comp_poc_hva_lva
         const float total = fp_pairwise_f32(vol, np_, lane, stk);
-        float best = -INFINITY;
-        int best_i = 0x7FFFFFFF;
-        for (int k = lane; k < np_; k += 64) {
-            const float v = vol[k];
-            if (v > best || (v != v && best == best)) { best = v; best_i = k; }       // (np.argmax: the first NaN is the maximum)
-        }
-#pragma unroll
-        for (int x = 32; x > 0; x >>= 1) {
-            const float ob = __shfl_xor(best, x, 64);
-            const int oi = __shfl_xor(best_i, x, 64);
-            const bool on = ob != ob, bn = best != best;
-            const bool take = on ? (!bn || oi < best_i) : (!bn && (ob > best || (ob == best && oi < best_i)));
-            if (take) { best = ob; best_i = oi; }
-        }
-        if (best_i == 0x7FFFFFFF) best_i = 0;                     // empty guard: np.argmax -> 0
+        const int best_i = vp_argmax(vol, np_, lane);
         if (lane == 0) {
             const int n = np_;
-            auto pl = [&](int k) -> int32_t {
-                if (n_bins < 0) return (int32_t)(minl + k);
-                if (k < nbk) return (int32_t)(minl + (int64_t)k * bw + (bw - 1) / 2);     // (e_k + e_k+1 - 1) // 2
-                return (int32_t)maxl;
-            };
-            const int pi = best_i;
-            const int32_t poc_price = pl(pi);
-            const double va_thrs = (double)total * (va_pct / 100.0);
-            double cum = vol[pi];
-            int32_t hv = poc_price, lv = poc_price;
-            int up = pi + 1, down = pi - 1;
-            double cu = 0.0, cd = 0.0;
-            if (up < n) { cu = vol[up]; if (up + 1 < n) cu += vol[up + 1]; }
-            if (down >= 0) { cd = vol[down]; if (down - 1 >= 0) cd += vol[down - 1]; }
-            while (cum < va_thrs) {
-                if (cu > cd) {
-                    cum += cu;
-                    hv = pl(up + 1 < n - 1 ? up + 1 : n - 1);
-                    up += 2;
-                    cu = -1.0;
-                    if (up < n) { cu = vol[up]; if (up + 1 < n) cu += vol[up + 1]; }
-                } else if (cu < cd) {
-                    cum += cd;
-                    lv = pl(down - 1 > 0 ? down - 1 : 0);
-                    down -= 2;
-                    cd = -1.0;
-                    if (down >= 0) { cd = vol[down]; if (down - 1 >= 0) cd += vol[down - 1]; }
-                } else if (cu == cd && cd != -1.0) {
-                    cum += cu + cd;
-                    hv = pl(up + 1 < n - 1 ? up + 1 : n - 1);
-                    lv = pl(down - 1 > 0 ? down - 1 : 0);
-                    up += 2; down -= 2;
-                    cu = -1.0;
-                    if (up < n) { cu = vol[up]; if (up + 1 < n) cu += vol[up + 1]; }
-                    cd = -1.0;
-                    if (down >= 0) { cd = vol[down]; if (down - 1 >= 0) cd += vol[down - 1]; }
-                } else break;                                      // the reference's "stuck in loop" exit
-            }
+            int32_t poc_price, hv, lv;
+            vp_walk(vol, n, best_i, total, va_pct, pl, poc_price, hv, lv);
             float p = 0.f;
             if (!(total <= 0.f)) {                                 // calc_volume_percentage_above_poc (volume.py:378: `<= 0`, so a NaN total goes on)
                 double above = 0.0;
@@ -546,55 +442,10 @@ __global__ __launch_bounds__(64) void k_vp_poc_one(const int32_t *__restrict__ l
     __shared__ __attribute__((aligned(8))) int stk[FMK_PW_STK_F32];
     const int lane = fmk_lane();
     const float total = fmk_pairwise_f32([&](int i) { return vol[i]; }, n, lane, stk);   // np.sum of a float32 array
-    float best = -INFINITY;
-    int best_i = 0x7FFFFFFF;
-    for (int k = lane; k < n; k += 64) {
-        const float v = vol[k];
-        if (v > best || (v != v && best == best)) { best = v; best_i = k; }              // np.argmax: first maximum, the first NaN wins
-    }
-#pragma unroll
-    for (int x = 32; x > 0; x >>= 1) {
-        const float ob = __shfl_xor(best, x, 64);
-        const int oi = __shfl_xor(best_i, x, 64);
-        const bool on = ob != ob, bn = best != best;
-        const bool take = on ? (!bn || oi < best_i) : (!bn && (ob > best || (ob == best && oi < best_i)));
-        if (take) { best = ob; best_i = oi; }
-    }
-    if (best_i == 0x7FFFFFFF) best_i = 0;
+    const int pi = vp_argmax(vol, n, lane);                                                // np.argmax: first maximum, the first NaN wins
     if (lane != 0) return;
-    const int pi = best_i;
-    const int32_t poc_price = levels[pi];
-    const double va_thrs = (double)total * (va_pct / 100.0);
-    double cum = vol[pi];
-    int32_t hv = poc_price, lv = poc_price;
-    int up = pi + 1, down = pi - 1;
-    double cu = 0.0, cd = 0.0;
-    if (up < n) { cu = vol[up]; if (up + 1 < n) cu += vol[up + 1]; }
-    if (down >= 0) { cd = vol[down]; if (down - 1 >= 0) cd += vol[down - 1]; }
-    while (cum < va_thrs) {
-        if (cu > cd) {
-            cum += cu;
-            hv = levels[up + 1 < n - 1 ? up + 1 : n - 1];
-            up += 2;
-            cu = -1.0;
-            if (up < n) { cu = vol[up]; if (up + 1 < n) cu += vol[up + 1]; }
-        } else if (cu < cd) {
-            cum += cd;
-            lv = levels[down - 1 > 0 ? down - 1 : 0];
-            down -= 2;
-            cd = -1.0;
-            if (down >= 0) { cd = vol[down]; if (down - 1 >= 0) cd += vol[down - 1]; }
-        } else if (cu == cd && cd != -1.0) {
-            cum += cu + cd;
-            hv = levels[up + 1 < n - 1 ? up + 1 : n - 1];
-            lv = levels[down - 1 > 0 ? down - 1 : 0];
-            up += 2; down -= 2;
-            cu = -1.0;
-            if (up < n) { cu = vol[up]; if (up + 1 < n) cu += vol[up + 1]; }
-            cd = -1.0;
-            if (down >= 0) { cd = vol[down]; if (down - 1 >= 0) cd += vol[down - 1]; }
-        } else break;                                              // the reference's "stuck in loop" exit
-    }
+    int32_t poc_price, hv, lv;
+    vp_walk(vol, n, pi, total, va_pct, [levels](int k) { return levels[k]; }, poc_price, hv, lv);
     out3[0] = poc_price; out3[1] = hv; out3[2] = lv;
 }
 

@@ -1,10 +1,13 @@
-"""Rolling volume profile on the MI355X: drop-in for `VolumePro` / `volume_profile_rolling` of
-finmlkit/feature/core/volume.py (:12-131, :403-456).
+"""Rolling and developing volume profile on the MI355X: drop-in for `VolumePro` / `volume_profile_rolling` /
+`volume_profile_developing` of finmlkit/feature/core/volume.py (:12-131, :403-456, :459-569).
 
 The reference walks ragged `numba.typed.List`s of per-bar level arrays; here the footprints stay in the
 CSR layout the footprint kernel produces (`FootprintData.level_offsets` + `.flat`) and one wave per bar
 aggregates its window in LDS (csrc/fmk_volprofile.hip).  Ragged lists are accepted too (concatenated
 once on the host).  Numba-typed semantics: float32 level sums in the reference's order, float64 scalars.
+
+The developing (session-anchored) profile replays the bars of a range in chunks from snapshots of the float32 sums
+(csrc/fmk_volprofile_dev.hip); many ranges -- one per trading day -- go through one call.
 
 `comp_flow_acceleration` and `vpin` (:572-641) run on resident series as prefix-sum scans (csrc/fmk_runsum.hip).
 """
@@ -68,6 +71,82 @@ def volume_profile_rolling(ts, highs, lows, price_levels, buy_volumes, sell_volu
         "Input arrays should have the same length and be non-empty."
     off, pl, bv, sv = _to_csr(price_levels, buy_volumes, sell_volumes)
     return volume_profile_rolling_csr(ts, highs, lows, off, pl, bv, sv, window_size_sec, n_bins, price_tick, va_pct)
+
+
+def trim_trailing_zeros(price_levels: NDArray, volumes: NDArray) -> Tuple[NDArray, NDArray]:
+    """Reference volume.py:463-489, plain NumPy on the host: the volumes rounded to 8 decimals (in their own dtype), then the leading
+    and trailing entries that compare == 0 dropped from both arrays (a NaN or a negative entry stops the trim)."""
+    price_levels = np.asarray(price_levels)
+    volumes = np.round(np.asarray(volumes), 8)
+    left, right = 0, len(price_levels) - 1
+    while left <= right and volumes[left] == 0:
+        left += 1
+    while right >= left and volumes[right] == 0.0:
+        right -= 1
+    return price_levels[left:right + 1], volumes[left:right + 1]
+
+
+def volume_profile_developing_sessions_csr(highs: NDArray[np.float64], lows: NDArray[np.float64], level_offsets: NDArray[np.int64],
+                                           price_levels: NDArray[np.int32], buy_volumes: NDArray[np.float32],
+                                           sell_volumes: NDArray[np.float32], range_starts, range_ends, n_bins: Optional[int] = None,
+                                           price_tick: float = None, va_pct: float = 68.34,
+                                           chunk_bars: int = 0) -> Tuple[NDArray, NDArray, NDArray, NDArray]:
+    """The developing profile of many bar ranges [range_starts[r], range_ends[r]) in one call -> (out_offsets int64 [n_ranges + 1],
+    poc, hva, lva int32 in tick units): the rows out_offsets[r] .. out_offsets[r + 1] are range r's bars, and equal what a call with
+    that range alone returns.  Ranges may touch or overlap.  `chunk_bars`: bars a wave replays from one snapshot, 0 = automatic; no
+    bit of the result depends on it.  Contract and refusals: include/fmk.h."""
+    hi = np.ascontiguousarray(highs, dtype=np.float64)
+    lo = np.ascontiguousarray(lows, dtype=np.float64)
+    off = np.ascontiguousarray(level_offsets, dtype=np.int64)
+    nb = len(hi)
+    if not (len(lo) == nb == len(off) - 1) or nb == 0:
+        raise AssertionError("Input arrays should have the same length and be non-empty.")
+    if price_tick is None:
+        raise ValueError("price_tick is required")
+    pl = np.ascontiguousarray(price_levels, dtype=np.int32)
+    bv = np.ascontiguousarray(buy_volumes, dtype=np.float32)
+    sv = np.ascontiguousarray(sell_volumes, dtype=np.float32)
+    rs = np.ascontiguousarray(range_starts, dtype=np.int64).ravel()
+    re_ = np.ascontiguousarray(range_ends, dtype=np.int64).ravel()
+    if len(rs) != len(re_):
+        raise ValueError("range_starts and range_ends must have the same length")
+    out_off = np.zeros(len(rs) + 1, dtype=np.int64)
+    np.cumsum(np.maximum(re_ - rs, 0), out=out_off[1:])
+    n_out = int(out_off[-1])
+    poc, hva, lva = (np.zeros(n_out, dtype=np.int32) for _ in range(3))
+    ctx = _ffi.default_context()
+    rc = ctx.call("fmk_volume_profile_developing", ptr(hi), ptr(lo), ptr(off), ptr(pl), ptr(bv), ptr(sv), c_i64(nb), ptr(rs), ptr(re_),
+                  ptr(out_off), c_i64(len(rs)), c_i64(-1 if n_bins is None else int(n_bins)), c_f64(price_tick), c_f64(va_pct),
+                  c_i64(int(chunk_bars)), ptr(poc), ptr(hva), ptr(lva), c_i64(n_out), allow=(_ffi.E_LEVEL,))
+    if rc == _ffi.E_LEVEL:                                                   # (with the entry's own message: it names the bar)
+        raise ValueError(_ffi.lib().fmk_last_error(ctx.handle).decode(errors="replace"))
+    return out_off, poc, hva, lva
+
+
+def volume_profile_developing_csr(ts: NDArray[np.int64], highs: NDArray[np.float64], lows: NDArray[np.float64],
+                                  level_offsets: NDArray[np.int64], price_levels: NDArray[np.int32],
+                                  buy_volumes: NDArray[np.float32], sell_volumes: NDArray[np.float32], start_ts: int, end_ts: int,
+                                  n_bins: Optional[int] = None, price_tick: float = None, va_pct: float = 68.34,
+                                  chunk_bars: int = 0) -> Tuple[NDArray, NDArray, NDArray, NDArray]:
+    """`volume_profile_developing` on CSR footprints -> (ts[start:end] int64, poc, hva, lva int32 in tick units) of the bars
+    searchsorted(ts, start_ts) .. searchsorted(ts, end_ts, 'right').  Row k belongs to bar start + k."""
+    t = np.ascontiguousarray(ts, dtype=np.int64)
+    if not (len(t) == len(highs) == len(lows) == len(level_offsets) - 1) or len(t) == 0:
+        raise AssertionError("Input arrays should have the same length and be non-empty.")
+    s = int(np.searchsorted(t, start_ts))                                    # volume.py:517-518
+    e = int(np.searchsorted(t, end_ts, side="right"))
+    _, poc, hva, lva = volume_profile_developing_sessions_csr(highs, lows, level_offsets, price_levels, buy_volumes, sell_volumes, [s], [e],
+                                                              n_bins, price_tick, va_pct, chunk_bars)
+    return t[s:e], poc, hva, lva
+
+
+def volume_profile_developing(ts, highs, lows, price_levels, buy_volumes, sell_volumes, start_ts: int, end_ts: int,
+                              n_bins: int = None, price_tick: float = None, va_pct: float = 68.34):
+    """Reference signature (volume.py:493-496): ragged per-bar lists of level arrays."""
+    assert len(ts) == len(highs) == len(lows) == len(price_levels) == len(buy_volumes) == len(sell_volumes) > 0, \
+        "Input arrays should have the same length and be non-empty."
+    off, pl, bv, sv = _to_csr(price_levels, buy_volumes, sell_volumes)
+    return volume_profile_developing_csr(ts, highs, lows, off, pl, bv, sv, start_ts, end_ts, n_bins, price_tick, va_pct)
 
 
 def aggregate_footprint(ts, highs, lows, price_levels, buy_volumes, sell_volumes, start_ts: int, end_ts: int,
@@ -176,6 +255,29 @@ class VolumePro:
                                                         fp_data.price_tick, self.va_pct)
         to_price = lambda a: np.where(a * fp_data.price_tick == 0, np.nan, a * fp_data.price_tick)   # volume.py:77-85
         return to_price(poc), to_price(hva), to_price(lva), pct
+
+    def compute_developing(self, bars: pd.DataFrame, fp_data, session_edges=None):
+        """The developing profile, anchored at every session's first bar -> (bar timestamps, POC, HVA, LVA prices float64:
+        level * price_tick, nothing replaced by NaN), one row per bar of a session, sessions one after another.  `session_edges`:
+        ascending ns timestamps; session k holds the bars with edges[k] <= timestamp < edges[k + 1], a session without bars is
+        skipped.  None: one session over all bars."""
+        assert len(bars) == len(fp_data.bar_timestamps), "Bars and footprint data should have the same length."
+        if getattr(fp_data, "level_offsets", None) is not None and getattr(fp_data, "flat", None) is not None:
+            off = fp_data.level_offsets
+            pl, bv, sv = (fp_data.flat[k] for k in ("price_levels", "buy_volumes", "sell_volumes"))
+        else:
+            off, pl, bv, sv = _to_csr(fp_data.price_levels, fp_data.buy_volumes, fp_data.sell_volumes)
+        ts = np.ascontiguousarray(fp_data.bar_timestamps, dtype=np.int64)
+        if session_edges is None:
+            starts, ends = np.array([0]), np.array([len(ts)])
+        else:
+            at = np.searchsorted(ts, np.asarray(session_edges, dtype=np.int64), side="left")
+            starts, ends = at[:-1], at[1:]
+            starts, ends = starts[ends > starts], ends[ends > starts]
+        out_off, poc, hva, lva = volume_profile_developing_sessions_csr(bars.high.values, bars.low.values, off, pl, bv, sv, starts, ends,
+                                                                        self.n_bins, fp_data.price_tick, self.va_pct)
+        rows = np.concatenate([np.arange(s, e) for s, e in zip(starts, ends)]) if len(starts) else np.empty(0, np.int64)
+        return ts[rows], poc * fp_data.price_tick, hva * fp_data.price_tick, lva * fp_data.price_tick
 
     def compute_range(self, bars: pd.DataFrame, fp_data, start: Union[str, int, pd.Timestamp],
                       end: Union[str, int, pd.Timestamp]):

@@ -339,6 +339,46 @@ int fmk_volume_profile_rolling(fmk_ctx *ctx, const int64_t *bar_ts, const double
                                int64_t n_bins, double price_tick, double va_pct, int32_t *poc, int32_t *hva,
                                int32_t *lva, float *pct);
 
+/* volume_profile_developing (volume.py:493-569) on CSR footprints: the session-anchored profile.  For every range r of bars
+ * [range_starts[r], range_ends[r]) (host arrays of bar indices; the Python layer makes them from time stamps by searchsorted left of
+ * start_ts, right of end_ts) and every bar t of it, POC / HVA / LVA (int32, tick units) of everything traded from the range's first
+ * bar up to and including t.  Ranges are independent; they may touch or overlap.  THE CONTRACT:
+ *  1 level range   int(round(min(lows) / price_tick)) .. int(round(max(highs) / price_tick)) over ALL bars of the range, once (it
+ *                  looks ahead, as the reference does), half-even like the rolling entry.
+ *  2 accumulation  bars one after another, per level float32 `+=` for buy and for sell (a bar's levels are distinct); after every
+ *                  bar total = buy + sell in float32.
+ *  3 n_bins < 0    (n_bins=None) comp_poc_hva_lva on the whole dense range with the unrounded totals, no trim.
+ *  4 n_bins > 0    np.round(total, 8) evaluated in float32 (rint(v * 1e8f) / 1e8f, both operations rounded to float32); leading and
+ *                  trailing entries that compare == 0 are dropped (a NaN or a negative entry stops the trim); bucket_price_levels on
+ *                  the trimmed levels -- the layout changes from bar to bar as the trimmed range grows -- then comp_poc_hva_lva.
+ *  5 position      the outputs of bar t of range r go to element out_offsets[r] + (t - range_starts[r]) of d_poc / d_hva / d_lva; no
+ *                  other element is written.  (The reference indexes its range-long outputs with t itself, which fails for every
+ *                  range that does not begin at bar 0; t - start is the documented intent, and equals the reference on the arrays
+ *                  sliced from the range's first bar.)
+ *  6 one level     a trimmed profile of one level under bucketing comes back as its only (leftover) bin: POC = HVA = LVA = that level,
+ *                  as the interpreted reference hands it back behind its warning.  (The rolling entry refuses that case.)
+ *  7 all zero      every rounded total 0 under bucketing (an empty first bar): FMK_E_LEVEL for the whole call -- the reference raises
+ *                  ValueError, np.min of nothing; the message names the first such bar: lowest range, then lowest bar.  Without
+ *                  bucketing the call returns; the POC is the lowest level (the argmax of zeros is 0).
+ *  8 stages        total, argmax and walk as stated for fmk_comp_poc_hva_lva below.  There is no share above the POC.
+ * n_bins < 0: no bucketing, as in the rolling entry.  chunk_bars: 0 = chosen by the entry; the results do not depend on it in any bit
+ * (a range's bars are replayed in chunks of that many bars from snapshots of the float32 sums).
+ * FMK_E_ARG: an empty range (the reference: ValueError) or one that reaches outside the bars, price_tick not above 0, a NaN or
+ * infinite low or high inside a range (outside every range it is not looked at); FMK_E_LEVEL: a footprint level outside its range's
+ * level range, a range whose highest high lies below its lowest low, item 7; FMK_E_ZERODIV: n_bins == 0; FMK_E_CAPACITY: a range wider
+ * than 1 << 24 levels (up to 8192 the working set is in LDS, above in global scratch).
+ * The host-pointer twin takes n_out, the length of poc / hva / lva; elements that no range covers keep what they held. */
+int fmk_volume_profile_developing_dev(fmk_ctx *ctx, const double *d_highs, const double *d_lows, const int64_t *d_level_offsets,
+                                      const int32_t *d_price_levels, const float *d_buy_volumes, const float *d_sell_volumes,
+                                      int64_t n_bars, const int64_t *range_starts, const int64_t *range_ends,
+                                      const int64_t *out_offsets, int64_t n_ranges, int64_t n_bins, double price_tick, double va_pct,
+                                      int64_t chunk_bars, int32_t *d_poc, int32_t *d_hva, int32_t *d_lva);
+int fmk_volume_profile_developing(fmk_ctx *ctx, const double *highs, const double *lows, const int64_t *level_offsets,
+                                  const int32_t *price_levels, const float *buy_volumes, const float *sell_volumes, int64_t n_bars,
+                                  const int64_t *range_starts, const int64_t *range_ends, const int64_t *out_offsets,
+                                  int64_t n_ranges, int64_t n_bins, double price_tick, double va_pct, int64_t chunk_bars,
+                                  int32_t *poc, int32_t *hva, int32_t *lva, int64_t n_out);
+
 /* calc_volume_percentage_above_poc (volume.py:367-391) on ONE profile: share of the volume on levels above `poc_price`
  * (NumPy-pairwise float32 total, the levels above added in order in float64, float64 quotient = the Numba-typed function). */
 int fmk_calc_volume_percentage_above_poc_dev(fmk_ctx *ctx, const int32_t *d_price_levels, const float *d_volumes, int64_t n,
