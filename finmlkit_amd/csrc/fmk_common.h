@@ -268,6 +268,11 @@ static inline int fmk_rule_flow_acceleration(fmk_ctx *ctx, int64_t recent_period
     return fmk_rule_least(ctx, recent_periods, 0, "comp_flow_acceleration: recent_periods must not be negative.");
 }
 static inline int fmk_rule_vpin(fmk_ctx *ctx, int64_t window) { return fmk_rule_least(ctx, window, 0, "vpin: window must not be negative."); }
+// the bar clock (fmk_clock.hip): bar_duration_ewma asks fmk_rule_ewma; the reference's BarRate divides by zero at a zero window
+static inline int fmk_rule_bar_rate(fmk_ctx *ctx, int64_t window_ns)
+{
+    return fmk_rule_least(ctx, window_ns, 1, "bar_rate: the window must be at least one nanosecond.");
+}
 // the window statistics (fmk_shape.hip): hurst's lag 8 needs one difference (asked after fmk_rule_window)
 static inline int fmk_rule_hurst(fmk_ctx *ctx, int64_t window) { return fmk_rule_least(ctx, window, 9, "hurst_exponent: window must be at least 9."); }
 // the approximate entropy (fmk_entropy.hip): the order-(m + 1) embedding needs one vector; one tile's span and the table of

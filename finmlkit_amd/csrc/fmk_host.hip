@@ -787,4 +787,74 @@ int fmk_approximate_entropy(fmk_ctx *ctx, const double *x, int64_t n, int64_t wi
                        [=](const double *d_x, double *d_o) { return fmk_approximate_entropy_dev(ctx, d_x, n, window, m, tolerance, d_o); });
 }
 
+// the bar clock, run lengths and the opening range (fmk_clock.hip)
+int fmk_bar_duration(fmk_ctx *ctx, const int64_t *ts, int64_t n, int64_t periods, double *out)
+{
+    FMK_TRY(fmk_series_check(ctx, "bar_duration", n));
+    DevBag bag(ctx);
+    int64_t *d_ts;
+    double *d_o;
+    FMK_TRY(bag.up(ts, n, &d_ts));
+    FMK_TRY(bag.out(n, &d_o));
+    FMK_TRY(fmk_bar_duration_dev(ctx, d_ts, n, periods, d_o));
+    return down(ctx, out, (const double *)d_o, n);
+}
+
+int fmk_bar_duration_ewma(fmk_ctx *ctx, const int64_t *ts, int64_t n, double span, double *out)
+{
+    FMK_TRY(fmk_rule_ewma(ctx, span));
+    FMK_TRY(fmk_series_check(ctx, "bar_duration_ewma", n));
+    DevBag bag(ctx);
+    int64_t *d_ts;
+    double *d_o;
+    FMK_TRY(bag.up(ts, n, &d_ts));
+    FMK_TRY(bag.out(n, &d_o));
+    FMK_TRY(fmk_bar_duration_ewma_dev(ctx, d_ts, n, span, d_o));
+    return down(ctx, out, (const double *)d_o, n);
+}
+
+int fmk_bar_rate(fmk_ctx *ctx, const int64_t *ts, int64_t n, double window_sec, int64_t window_ns, double *out)
+{
+    FMK_TRY(fmk_rule_bar_rate(ctx, window_ns));
+    FMK_TRY(fmk_series_check(ctx, "bar_rate", n));
+    DevBag bag(ctx);
+    int64_t *d_ts;
+    double *d_o;
+    FMK_TRY(bag.up(ts, n, &d_ts));
+    FMK_TRY(bag.out(n, &d_o));
+    FMK_TRY(fmk_bar_rate_dev(ctx, d_ts, n, window_sec, window_ns, d_o));
+    return down(ctx, out, (const double *)d_o, n);
+}
+
+int fmk_dir_run_len(fmk_ctx *ctx, const double *x, int64_t n, int8_t *out)
+{
+    FMK_TRY(fmk_series_check(ctx, "dir_run_len", n));
+    DevBag bag(ctx);
+    double *d_x;
+    int8_t *d_o;
+    FMK_TRY(bag.up(x, n, &d_x));
+    FMK_TRY(bag.out(n, &d_o));
+    FMK_TRY(fmk_dir_run_len_dev(ctx, d_x, n, d_o));
+    return down(ctx, out, (const int8_t *)d_o, n);
+}
+
+int fmk_orb_break(fmk_ctx *ctx, const int64_t *ts, const double *high, const double *low, const double *close, int64_t n,
+                  uint8_t *orb_long, uint8_t *orb_short)
+{
+    FMK_TRY(fmk_series_check(ctx, "orb_break", n));
+    DevBag bag(ctx);
+    int64_t *d_ts;
+    double *d_h, *d_l, *d_c;
+    uint8_t *d_lg, *d_sh;
+    FMK_TRY(bag.up(ts, n, &d_ts));
+    FMK_TRY(bag.up(high, n, &d_h));
+    FMK_TRY(bag.up(low, n, &d_l));
+    FMK_TRY(bag.up(close, n, &d_c));
+    FMK_TRY(bag.out(n, &d_lg));
+    FMK_TRY(bag.out(n, &d_sh));
+    FMK_TRY(fmk_orb_break_dev(ctx, d_ts, d_h, d_l, d_c, n, d_lg, d_sh));
+    FMK_TRY(down(ctx, orb_long, (const uint8_t *)d_lg, n));
+    return down(ctx, orb_short, (const uint8_t *)d_sh, n);
+}
+
 }  // extern "C"

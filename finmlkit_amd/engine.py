@@ -15,6 +15,7 @@ import numpy as np
 from . import _ffi
 from ._ffi import (DIRECTIONAL_FIELDS, FOOTPRINT_BAR_FIELDS, FOOTPRINT_FLAT_FIELDS, Context, DeviceArray,
                    DirectionalOut, FootprintOut, c_f64, c_i64, c_vp)
+from .feature.core import clock
 from .feature.series_ops import OPS, resident
 
 DENSE_GAP_MOD = 100_000_000          # mean gap 50 ms, no empty 1-min bar
@@ -489,6 +490,34 @@ class DeviceTrades:
         """approximate_entropy (feature/core/entropy.py; reference transforms.py:1400-1457) of a resident float64 series; ValueError
         for the arguments that function refuses."""
         return resident(self.ctx, OPS["approximate_entropy"], (y,), window, m, tolerance)
+
+    # the bar clock, run lengths and the opening range (csrc/fmk_clock.hip).  ts=None: the tape's own stamps; a DeviceArray of bar
+    # stamps (int64 nanoseconds, e.g. from gather_ts) may be given instead
+    def bar_duration(self, periods: int = 1, ts: Optional[DeviceArray] = None) -> DeviceArray:
+        """Seconds between row i and row i - periods (reference transforms.py:1511-1548), NaN where there is no such row."""
+        return clock.resident(self.ctx, clock.CLOCK_OPS["bar_duration"], (self.ts if ts is None else ts,), int(periods))[0]
+
+    def bar_duration_ewma(self, span=20, ts: Optional[DeviceArray] = None) -> DeviceArray:
+        """ewma of the bar durations, NaN at row 0 (reference transforms.py:1460-1508); ValueError when span < 1."""
+        span = clock.rule_span(span)
+        return clock.resident(self.ctx, clock.CLOCK_OPS["bar_duration_ewma"], (self.ts if ts is None else ts,), span)[0]
+
+    def bar_rate(self, window_sec: float, ts: Optional[DeviceArray] = None) -> DeviceArray:
+        """Rows per hour over the closed window of window_sec seconds that ends at each row (reference transforms.py:1210-1270);
+        ValueError for a window below one nanosecond."""
+        w = clock.window_ns(window_sec)
+        return clock.resident(self.ctx, clock.CLOCK_OPS["bar_rate"], (self.ts if ts is None else ts,), float(window_sec), w)[0]
+
+    def dir_run_len(self, y: DeviceArray) -> DeviceArray:
+        """The length of the run of equal signs each row of a resident float64 series ends (reference transforms.py:1605-1664) -> an
+        int8 array."""
+        return clock.resident(self.ctx, clock.CLOCK_OPS["dir_run_len"], (y,))[0]
+
+    def orb_break(self, high: DeviceArray, low: DeviceArray, close: DeviceArray, ts: Optional[DeviceArray] = None):
+        """Opening-range breakouts per UTC day (reference transforms.py:1122-1207) of three resident float64 series -> (orb_long,
+        orb_short), two uint8 arrays.  Strictly increasing stamps."""
+        return clock.resident(self.ctx, clock.CLOCK_OPS["orb_break"], (self.ts if ts is None else ts, high, low, close),
+                              unequal=clock.ORB_RESIDENT_SHAPE_MESSAGE)
 
     # ------------------------------------------------------------------ event sampling
     def cusum_filter(self, threshold, series: Optional[DeviceArray] = None) -> DeviceArray:

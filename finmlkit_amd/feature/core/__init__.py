@@ -1,7 +1,9 @@
 """The core feature functions; `adx_core` is exported here as well as from `.trend`, and the window statistics of `.shape` and
-`.entropy`."""
+`.entropy`, and the bar-clock, run-length and opening-range features of `.clock`."""
+from .clock import bar_duration, bar_duration_ewma, bar_rate, dir_run_len, orb_break
 from .entropy import approximate_entropy
 from .shape import bipower_variation, hurst_exponent, rolling_kurtosis, trend_slope
 from .trend import adx_core
 
-__all__ = ["adx_core", "approximate_entropy", "bipower_variation", "hurst_exponent", "rolling_kurtosis", "trend_slope"]
+__all__ = ["adx_core", "approximate_entropy", "bar_duration", "bar_duration_ewma", "bar_rate", "bipower_variation", "dir_run_len",
+           "hurst_exponent", "orb_break", "rolling_kurtosis", "trend_slope"]

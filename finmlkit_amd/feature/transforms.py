@@ -8,7 +8,10 @@ and `ADX` (reference transforms.py:577-602, :206-273, :711-751, :991-1030), and 
 statistics `KurtosisTransform`, `TrendSlope`, `HurstExponent` and `BiPowerVariation` (reference transforms.py:900-933, :936-988,
 :1341-1397, :1551-1602; there pandas' rolling.apply on either backend, here the kernels of csrc/fmk_shape.hip), and the rolling
 approximate entropy `ApproximateEntropy` (reference transforms.py:1400-1457; there pandas' rolling.apply around
-`antropy.app_entropy`, here the kernel of csrc/fmk_entropy.hip, which needs no `antropy`).
+`antropy.app_entropy`, here the kernel of csrc/fmk_entropy.hip, which needs no `antropy`), and the bar clock, run lengths and the
+opening range `BarDuration`, `BarDurationEWMA`, `BarRate`, `DirRunLen` and `ORBBreak` (reference transforms.py:1511-1548, :1460-1508,
+:1210-1270, :1605-1664, :1122-1207; there pandas' diff, ewm and time-window rolling, a sequential loop and a Python loop per day, here
+the kernels of csrc/fmk_clock.hip).
 
 Counterparts of finmlkit/feature/transforms.py:89-117 (ReturnT), :308-332 (EWMST) and the
 pipeline part of finmlkit/feature/kit.py:Compose (:630-720), enough to run the QuickStart flow
@@ -26,6 +29,7 @@ import pandas as pd
 
 from .. import _ffi
 from .._ffi import DeviceArray, c_f64, c_i64
+from .core import clock
 from .core.structural_break.cusum import cusum_test_rolling
 from .core.correlation import rolling_price_volume_correlation
 from .core.momentum import LENGTH_MESSAGE, stoch_k
@@ -509,6 +513,123 @@ class PriceVolumeCorrelation(MISOTransform):
         cols = self._prepare_input_nb(x)
         close, volume = (np.asarray(cols[c], dtype=np.float64) for c in self.requires[:2])
         return self._prepare_output_nb(x.index, rolling_price_volume_correlation(close, volume, self.window))
+
+
+class _ClockTransform(SISOTransform):
+    """A transform that reads the index and not the input column (reference: "only needed for timestamp extraction").  The Series it
+    returns is named `out_name`, without the input column, as the reference's; `output_name` is the SISO composition.  The index
+    must be a DatetimeIndex (the reference's message) and monotonic increasing: the reference sorts, here the caller does."""
+    _index_message = ""
+
+    def __init__(self, input_col: str, out_name: str):
+        super().__init__(input_col, out_name)
+        self.out_name = out_name
+
+    def _stamps(self, x: pd.DataFrame):
+        if not isinstance(x.index, pd.DatetimeIndex):
+            raise ValueError(self._index_message)
+        if not x.index.is_monotonic_increasing:
+            raise ValueError(f"{type(self).__name__}: the index must be monotonic increasing; sort the frame first.")
+        return x.index.values.astype("datetime64[ns]").astype(np.int64)
+
+    def _host(self, ts):
+        raise NotImplementedError
+
+    def _hip(self, x):
+        return pd.Series(self._host(self._stamps(x)), index=x.index, name=self.out_name)
+
+
+class BarDuration(_ClockTransform):
+    """Seconds between a bar and the bar `periods` rows before it (reference transforms.py:1511-1548: pandas' diff of the index)."""
+    _index_message = "Input DataFrame must have a DatetimeIndex for BarDurationEWMA calculation"      # the reference's, as it stands
+
+    def __init__(self, periods=1, input_col: str = "close"):
+        super().__init__(input_col, f"dur_{periods}bar")
+        self.periods = periods
+
+    def _host(self, ts):
+        return clock.bar_duration(ts, self.periods)
+
+    def _dev(self, ts, y):
+        return clock.resident(ts.ctx, clock.CLOCK_OPS["bar_duration"], (ts,), int(self.periods))[0]
+
+
+class BarDurationEWMA(_ClockTransform):
+    """Exponentially weighted mean of the bar durations (reference transforms.py:1460-1508: pandas' ewm(span, adjust=True).mean());
+    `span < 1` raises ValueError when the transform is applied."""
+    _index_message = "Input DataFrame must have a DatetimeIndex for BarDurationEWMA calculation"
+
+    def __init__(self, span: int = 20, input_col: str = "close"):
+        super().__init__(input_col, f"dur_ewma{span}")
+        self.span = span
+
+    def _host(self, ts):
+        return clock.bar_duration_ewma(ts, self.span)
+
+    def _dev(self, ts, y):
+        return clock.resident(ts.ctx, clock.CLOCK_OPS["bar_duration_ewma"], (ts,), clock.rule_span(self.span))[0]
+
+
+class BarRate(_ClockTransform):
+    """Bars per hour over the closed time window that ends at each bar (reference transforms.py:1210-1270: pandas' time-window
+    rolling sum, closed='both').  A window below one nanosecond raises ValueError when the transform is applied; the reference
+    divides by zero there."""
+    _index_message = "Input DataFrame must have a DatetimeIndex for BarRate calculation"
+
+    def __init__(self, window: pd.Timedelta, input_col: str = "close"):
+        window_sec = window.total_seconds()
+        window_min = window_sec / 60.
+        super().__init__(input_col, "bars_per_hour" if window_min.is_integer() else f"rate_{window_min}m")
+        self.window_sec = window_sec
+
+    def _host(self, ts):
+        return clock.bar_rate(ts, self.window_sec)
+
+    def _dev(self, ts, y):
+        w = clock.window_ns(self.window_sec)
+        return clock.resident(ts.ctx, clock.CLOCK_OPS["bar_rate"], (ts,), float(self.window_sec), w)[0]
+
+
+class DirRunLen(SISOTransform):
+    """The length of the run of same-sign returns each bar ends, int8 (reference transforms.py:1605-1664: a sequential loop)."""
+
+    def __init__(self, input_col: str = "ret1"):
+        super().__init__(input_col, "dir_run_len")
+
+    def _hip(self, x):
+        return self._prepare_output_nb(x.index, clock.dir_run_len(self._prepare_input_nb(x)))
+
+    def _dev(self, ts, y):
+        return clock.resident(ts.ctx, clock.CLOCK_OPS["dir_run_len"], (y,))[0]
+
+
+class ORBBreak(MISOTransform):
+    """Opening-range breakouts inside a UTC day (reference transforms.py:1122-1207): two bool Series, `orb_long` and `orb_short`; the
+    columns are (high, low, close).  The index must be a DatetimeIndex (the reference's message), monotonic increasing (the reference
+    sorts, here the caller does) and unique (the reference marks every row of a duplicated stamp)."""
+
+    def __init__(self, input_cols: list[str] = None):
+        if input_cols is None:
+            input_cols = ["high", "low", "close"]
+        super().__init__(input_cols, "orb_long")
+        self.produces = ["orb_long", "orb_short"]
+
+    @property
+    def output_name(self):
+        return self.produces
+
+    def _hip(self, x):
+        if not isinstance(x.index, pd.DatetimeIndex):
+            raise ValueError("Input DataFrame must have a DatetimeIndex for ORB calculation")
+        if not x.index.is_monotonic_increasing:
+            raise ValueError("ORBBreak: the index must be monotonic increasing; sort the frame first.")
+        if not x.index.is_unique:
+            raise ValueError("ORBBreak: the index must be unique.")
+        ts = x.index.values.astype("datetime64[ns]").astype(np.int64)
+        cols = self._prepare_input_nb(x)
+        high, low, close = (np.asarray(cols[c], dtype=np.float64) for c in self.requires[:3])
+        lg, sh = clock.orb_break(ts, high, low, close)
+        return (pd.Series(lg, index=x.index, name=self.produces[0]), pd.Series(sh, index=x.index, name=self.produces[1]))
 
 
 class SIMOTransform:

@@ -632,6 +632,42 @@ int fmk_bipower_variation(fmk_ctx *ctx, const double *x, int64_t n, int64_t wind
 int fmk_approximate_entropy_dev(fmk_ctx *ctx, const double *d_x, int64_t n, int64_t window, int64_t m, double tolerance, double *d_out);
 int fmk_approximate_entropy(fmk_ctx *ctx, const double *x, int64_t n, int64_t window, int64_t m, double tolerance, double *out);
 
+/* ---- bar-clock, run-length and opening-range features (csrc/fmk_clock.hip): the reference's BarDuration, BarDurationEWMA,
+ * BarRate, DirRunLen and ORBBreak transforms (transforms.py:1511-1548, :1460-1508, :1210-1270, :1605-1664, :1122-1207) on series of
+ * n elements.  ts: int64 nanoseconds, non-decreasing (unsorted stamps: undefined, as for comp_lagged_returns).
+ *   bar_duration:      out[i] = (double)(ts[i] - ts[i - periods]) / 1e9 where 0 <= i - periods < n, NaN elsewhere; any periods
+ *                      (pandas' diff).  The reference's bits.
+ *   bar_duration_ewma: out[0] = NaN; from element 1 on ewma's recursion over the durations d[t] = (double)(ts[t] - ts[t-1]) / 1e9,
+ *                      seeded (d[1], 1) at element 1: u = d[t] + (1 - alpha) * u, v = 1 + (1 - alpha) * v, out = u / v, alpha =
+ *                      2 / (span + 1).  A device-wide scan like ewma: within 1e-9 relative of pandas' ewm(span, adjust=True).mean().
+ *   bar_rate:          lb(i) = the first j with ts[j] >= ts[i] - window_ns (on int64); out[i] = (double)(i - lb(i) + 1) / window_sec
+ *                      * 3600.0.  window_ns is pd.Timedelta(seconds=window_sec).value, computed by the caller.  The reference's
+ *                      bits (rolling(window, closed='both').sum() / window_sec * 3600), duplicate stamps included.
+ *   dir_run_len:       s = sign(x) (-0.0 is zero, +-inf is +-1, NaN is unequal to everything).  out[0] = 0; for i >= 1 out[i] = 0
+ *                      where s[i] == 0, else i - h(i) + 1 with h(i) the last j <= i that starts a run: j == 1, s[j] != s[j-1] or
+ *                      s[j] NaN.  Stored as the low 8 bits (int8): a run of 128 reads -128, one of 256 reads 0.
+ *   orb_break:         day(i) = floor(ts[i] / 86 400e9); s(i) = the first row of i's day.  Where ts[s] - day * 86 400e9 < 60e9 and
+ *                      i - s >= 4: orb_long[i] = close[i] > max(high[s .. s+3]), orb_short[i] = close[i] < min(low[s .. s+3]), max
+ *                      and min skipping NaN (all four NaN: no signal); 0 elsewhere.  uint8 outputs.  Strictly increasing stamps.
+ * dir_run_len and orb_break run the last-head scan of csrc/fmk_lasthead.h (three launches, 4 bytes of scratch per 2048 elements).
+ * FMK_E_ARG, checked before a device is touched and before any pointer is looked at: span < 1, window_ns < 1, n >= 2^31. */
+int fmk_bar_duration_dev(fmk_ctx *ctx, const int64_t *d_ts, int64_t n, int64_t periods, double *d_out);
+int fmk_bar_duration(fmk_ctx *ctx, const int64_t *ts, int64_t n, int64_t periods, double *out);
+int fmk_bar_duration_ewma_dev(fmk_ctx *ctx, const int64_t *d_ts, int64_t n, double span, double *d_out);
+int fmk_bar_duration_ewma(fmk_ctx *ctx, const int64_t *ts, int64_t n, double span, double *out);
+int fmk_bar_rate_dev(fmk_ctx *ctx, const int64_t *d_ts, int64_t n, double window_sec, int64_t window_ns, double *d_out);
+int fmk_bar_rate(fmk_ctx *ctx, const int64_t *ts, int64_t n, double window_sec, int64_t window_ns, double *out);
+int fmk_dir_run_len_dev(fmk_ctx *ctx, const double *d_x, int64_t n, int8_t *d_out);
+int fmk_dir_run_len(fmk_ctx *ctx, const double *x, int64_t n, int8_t *out);
+int fmk_orb_break_dev(fmk_ctx *ctx, const int64_t *d_ts, const double *d_high, const double *d_low, const double *d_close, int64_t n,
+                      uint8_t *d_orb_long, uint8_t *d_orb_short);
+int fmk_orb_break(fmk_ctx *ctx, const int64_t *ts, const double *high, const double *low, const double *close, int64_t n,
+                  uint8_t *orb_long, uint8_t *orb_short);
+/* The tile sizes of these kernels, for callers that place work at tile edges: out4[0] elements per workgroup of the scans
+ * (bar_duration_ewma, dir_run_len, orb_break), [1] tiles per trip of their aggregate scan, [2] rows per workgroup of bar_rate, [3] the
+ * stamps bar_rate stages in LDS (a longer slice is searched in global memory).  Needs no context and no device. */
+int fmk_clock_geometry(int64_t *out4);
+
 /* ---- labels and sample weights on the tick tape: finmlkit/label/tbm.py, label/weights.py ------------------------
  * triple_barrier (tbm.py:11-158) on the raw tape.  Per event: label (side labels -1 / +1; meta labels 0 / 1 when d_side is given),
  * index of the first barrier touch, the return there and the max return / barrier ratio.  Labels, touch indices, returns and ratios
