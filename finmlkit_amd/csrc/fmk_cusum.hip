@@ -39,28 +39,17 @@
 #define FF_ITEMS 8
 #define FF_TILE (FF_THREADS * FF_ITEMS)
 
-// last non-NaN value of the block's threads in thread order (NaN: none): exclusive value + block aggregate
-__device__ __forceinline__ double ff_block_exclusive(double mine, double *lds /*[4]*/, double *block_total)
-{
-    const int lane = fmk_lane(), w = threadIdx.x >> 6;
-    double inc = mine;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const double o = __shfl_up(inc, d, 64);
-        if (lane >= d && isnan(inc)) inc = o;
-    }
-    if (lane == 63) lds[w] = inc;
-    __syncthreads();
-    double pre = NAN;
-    for (int k = 0; k < w; ++k) pre = isnan(lds[k]) ? pre : lds[k];
-    double tot = NAN;
-    for (int k = 0; k < 4; ++k) tot = isnan(lds[k]) ? tot : lds[k];
-    *block_total = tot;
-    double prev = __shfl_up(inc, 1, 64);
-    if (lane == 0) prev = NAN;
-    __syncthreads();
-    return isnan(prev) ? pre : prev;
-}
+#define FF_AGG_UNIT 1024        // tile aggregates per trip of the one-workgroup scan
+
+// "the last non-NaN value" (NaN: none) as a monoid of fmk_wgscan.h, where the workgroup scan of k_ff_apply and the scan of the tile
+// aggregates come from
+namespace {
+struct FfLast : FmkScalarDpp<FfLast, double> {
+    using T = double;
+    static __device__ __forceinline__ double identity() { return NAN; }
+    static __device__ __forceinline__ double combine(double first, double then) { return isnan(then) ? first : then; }
+};
+}  // namespace
 
 // tile_last[b] = the tile's last non-NaN value (NaN: none); *first_valid = index of the stream's first non-NaN.
 // Only the LAST valid value of the tile is needed here, i.e. the value at the largest valid index: an argmax, so the loads are
@@ -141,35 +130,6 @@ __global__ __launch_bounds__(1024) void k_ff_count(const int *__restrict__ tile_
     }
 }
 
-__global__ __launch_bounds__(1024) void k_ff_scan_tiles(double *tile_last, int64_t tiles)
-{
-    __shared__ double ws[16];
-    __shared__ double run;
-    if (threadIdx.x == 0) run = NAN;
-    __syncthreads();
-    const int lane = fmk_lane(), w = threadIdx.x >> 6;
-    for (int64_t b = 0; b < tiles; b += 1024) {
-        const int64_t i = b + threadIdx.x;
-        const double v = i < tiles ? tile_last[i] : NAN;
-        double inc = v;
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) {
-            const double o = __shfl_up(inc, d, 64);
-            if (lane >= d && isnan(inc)) inc = o;
-        }
-        if (lane == 63) ws[w] = inc;
-        __syncthreads();
-        double pre = run;
-        for (int k = 0; k < w; ++k) pre = isnan(ws[k]) ? pre : ws[k];
-        double prev = __shfl_up(inc, 1, 64);
-        if (lane == 0) prev = NAN;
-        if (i < tiles) tile_last[i] = isnan(prev) ? pre : prev;
-        __syncthreads();
-        if (threadIdx.x == 1023) run = isnan(inc) ? pre : inc;
-        __syncthreads();
-    }
-}
-
 __global__ __launch_bounds__(FF_THREADS) void k_ff_apply(double *__restrict__ x, int64_t n,
                                                          const double *__restrict__ tile_pre)
 {
@@ -184,8 +144,7 @@ __global__ __launch_bounds__(FF_THREADS) void k_ff_apply(double *__restrict__ x,
         last = isnan(v[k]) ? last : v[k];
     }
     double tot;
-    double cur = ff_block_exclusive(last, lds, &tot);
-    if (isnan(cur)) cur = tile_pre[blockIdx.x];
+    double cur = FfLast::combine(tile_pre[blockIdx.x], fmk_wg_exclusive<FfLast, FF_THREADS / 64>(last, lds, &tot));
 #pragma unroll
     for (int k = 0; k < FF_ITEMS; ++k) {
         const int64_t i = i0 + k;
@@ -580,7 +539,7 @@ extern "C" int fmk_cusum_bar_indexer_dev(fmk_ctx *ctx, const int64_t *d_ts, cons
         first = (int64_t)f.first;
         all_nan = f.first == big;
         if (!all_nan && f.nan_count != first) {                // NaNs after the first valid entry: fill them (logic.py:187-189)
-            k_ff_scan_tiles<<<1, 1024, 0, ctx->stream>>>(tile_last, tiles);
+            k_fmk_agg_scan<FfLast, FF_AGG_UNIT><<<1, FF_AGG_UNIT, 0, ctx->stream>>>(tile_last, tiles, nullptr);
             FMK_LAUNCH_CHECK(ctx);
             k_ff_apply<<<(unsigned)tiles, FF_THREADS, 0, ctx->stream>>>(d_sigma, n, tile_last);
             FMK_LAUNCH_CHECK(ctx);

@@ -65,6 +65,14 @@ __device__ __forceinline__ T fmk_dpp_iscan(T v, T ident, Op op)
     return v;
 }
 
+// The dpp() of a scalar monoid M (fmk_wgscan.h): the value moves as VIA, one of the types fmk_dpp is overloaded for (uint32_t goes
+// through int); lanes without a source receive M::identity().
+template <class M, typename T, typename VIA = T>
+struct FmkScalarDpp {
+    template <int CTRL, int ROW_MASK>
+    static __device__ __forceinline__ T dpp(const T &v) { return (T)fmk_dpp<CTRL, ROW_MASK>((VIA)M::identity(), (VIA)v); }
+};
+
 // value of lane 63 broadcast to the wave (SGPRs)
 __device__ __forceinline__ int fmk_last_lane(int v) { return __builtin_amdgcn_readlane(v, 63); }
 __device__ __forceinline__ int64_t fmk_last_lane(int64_t v)

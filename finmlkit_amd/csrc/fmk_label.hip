@@ -24,6 +24,7 @@
 
 #include "fmk_common.h"
 #include "fmk_log.h"
+#include "fmk_wgscan.h"
 
 #define LB_BLOCK 1024            // ticks per level-1 table entry
 #define LB_FAN 64                // level-1 entries per level-2 entry (one lane each)
@@ -396,48 +397,31 @@ __global__ __launch_bounds__(256) void k_lc_tile_sums(const int *__restrict__ di
     if (threadIdx.x == 0) tile_sum[blockIdx.x] = sw[0] + sw[1] + sw[2] + sw[3];
 }
 
-// exclusive scan of the tile sums in place (one workgroup)
-__global__ __launch_bounds__(1024) void k_lc_tile_scan(unsigned *t, int64_t m)
-{
-    __shared__ unsigned ws[16];
-    __shared__ unsigned run;
-    if (threadIdx.x == 0) run = 0;
-    __syncthreads();
-    const int lane = fmk_lane(), w = threadIdx.x >> 6;
-    for (int64_t b = 0; b < m; b += 1024) {
-        const int64_t i = b + threadIdx.x;
-        const unsigned v = i < m ? t[i] : 0;
-        const unsigned iv = fmk_wave_iscan(v);
-        if (lane == 63) ws[w] = iv;
-        __syncthreads();
-        unsigned o = run;
-        for (int k = 0; k < w; ++k) o += ws[k];
-        if (i < m) t[i] = o + iv - v;
-        __syncthreads();
-        if (threadIdx.x == 1023) run = o + iv;
-        __syncthreads();
-    }
-}
+// the uint32 sum as a monoid of fmk_wgscan.h: the exclusive scan of the tile sums (one workgroup, LC_AGG_UNIT per trip) and the
+// workgroup scan of k_lc_apply come from there
+#define LC_AGG_UNIT 1024
+namespace {
+struct LcSum : FmkScalarDpp<LcSum, unsigned, int> {
+    using T = unsigned;
+    static __device__ __forceinline__ unsigned identity() { return 0; }
+    static __device__ __forceinline__ unsigned combine(unsigned first, unsigned then) { return first + then; }
+};
+}  // namespace
 
-// concurrency[j] = int16(inclusive prefix of diff)
+// concurrency[j] = int16(inclusive prefix of diff), one workgroup scan per row of 256 ticks
 __global__ __launch_bounds__(256) void k_lc_apply(const int *__restrict__ diff, int64_t n, const unsigned *__restrict__ tile_off,
                                                   int16_t *__restrict__ out)
 {
     __shared__ unsigned ws[4];
-    const int lane = fmk_lane(), w = threadIdx.x >> 6;
     const int64_t base = (int64_t)blockIdx.x * LC_TILE;
     unsigned run = tile_off[blockIdx.x];
     for (int r = 0; r < LC_TILE / 256; ++r) {
         const int64_t j = base + r * 256 + threadIdx.x;
         const unsigned v = j < n ? (unsigned)diff[j] : 0;
-        const unsigned iv = fmk_wave_iscan(v);
-        if (lane == 63) ws[w] = iv;
-        __syncthreads();
-        unsigned o = run;
-        for (int k = 0; k < w; ++k) o += ws[k];
-        run += ws[0] + ws[1] + ws[2] + ws[3];
-        if (j < n) out[j] = (int16_t)(uint16_t)(o + iv);
-        __syncthreads();
+        unsigned tot;
+        const unsigned ex = fmk_wg_exclusive<LcSum, 4>(v, ws, &tot);
+        if (j < n) out[j] = (int16_t)(uint16_t)(run + LcSum::combine(ex, v));
+        run += tot;
     }
 }
 
@@ -474,7 +458,7 @@ extern "C" int fmk_label_concurrency_dev(fmk_ctx *ctx, const int64_t *d_event_id
     if (le == hipSuccess) {
         k_lc_mark<<<(unsigned)fmk_ceil_div(n_events, 256), 256, 0, ctx->stream>>>(d_event_idx, d_touch_idx, n_events, n, diff, mail);
         k_lc_tile_sums<<<(unsigned)tiles, 256, 0, ctx->stream>>>(diff, n, tile);
-        k_lc_tile_scan<<<1, 1024, 0, ctx->stream>>>(tile, tiles);
+        k_fmk_agg_scan<LcSum, LC_AGG_UNIT><<<1, LC_AGG_UNIT, 0, ctx->stream>>>(tile, tiles, nullptr);
         k_lc_apply<<<(unsigned)tiles, 256, 0, ctx->stream>>>(diff, n, tile, d_concurrency);
         le = hipGetLastError();
     }

@@ -1,6 +1,8 @@
 // fmk_lasthead.h -- the device-wide "index of the last head at or before me" scan: h(i) = the largest j <= i whose flag is set, or
 // LH_NONE.  A running maximum over flagged indices (fmk_clock.hip: dir_run_len's run starts, orb_break's day starts; DESIGN.md
-// section 7i).  Three launches on the context's stream in the manner of fmk_recur_core.h, no workgroup waits for another:
+// section 7i).  Three launches on the context's stream in the manner of fmk_recur_core.h, no workgroup waits for another.  The workgroup
+// scan and the aggregate scan are this file's own, not those of fmk_wgscan.h: on those, dir_run_len took 0.003 ms more per 1e8 elements
+// (0.412 -> 0.415 ms, in k_lh_aggscan and k_lh_apply; profiles/wgscan_refactor_timing.json).
 //   k_lh_tiles    every thread loads its LH_ITEMS consecutive elements and keeps the last flagged index among them; the workgroup's
 //                 maximum goes to one int per tile (LH_NONE: no head in the whole tile).
 //   k_lh_aggscan  one workgroup: the tile values become the running maximum over the tiles before each (exclusive), LH_AGG_UNIT

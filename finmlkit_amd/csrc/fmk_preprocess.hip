@@ -127,7 +127,7 @@ extern "C" int fmk_merge_split_trades_dev(fmk_ctx *ctx, const int64_t *d_ts, con
     FMK_LAUNCH_CHECK(ctx);
     k_merge_count<<<(unsigned)tiles, 256, 0, ctx->stream>>>(flags, n, tile_off);
     FMK_LAUNCH_CHECK(ctx);
-    k_scan_tile_scan<<<1, 1024, 0, ctx->stream>>>(tile_off, tiles, tile_off + tiles);
+    k_fmk_agg_scan<ScanSum, FMK_SCAN_AGG_UNIT><<<1, FMK_SCAN_AGG_UNIT, 0, ctx->stream>>>(tile_off, tiles, tile_off + tiles);
     FMK_LAUNCH_CHECK(ctx);
     int64_t m;
     FMK_TRY(fmk_read_back(ctx, &m, tile_off + tiles, 8));
@@ -159,7 +159,9 @@ __device__ __forceinline__ int sv_move(const double *price, int64_t i)
     return dp > 0.0 ? 1 : -1;
 }
 
-// last non-zero move of the block's threads in thread order: exclusive value for this thread + block aggregate
+// last non-zero move of the block's threads in thread order: exclusive value for this thread + block aggregate.  This scan and
+// k_side_scan_tiles below are not those of fmk_wgscan.h: on those, the scan of the tile aggregates (4 bytes each there, 1 here) took
+// 0.73 instead of 0.66 ms per 1e9 ticks and the tick rule 0.05 to 0.18 ms more of its 4.1 (profiles/wgscan_refactor_timing.json)
 __device__ __forceinline__ int sv_block_exclusive(int mine, int *lds /*[4]*/, int *block_total)
 {
     const int lane = fmk_lane(), w = threadIdx.x >> 6;

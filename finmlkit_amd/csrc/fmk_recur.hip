@@ -18,8 +18,8 @@
 //                the tile's elements do to the state that enters it.  Elements before the seed are the identity, the seed element is
 //                the constant map to the seed value, so every call starts from a zero state.  The workgroup that holds the seed
 //                index sums the seed (in index order, one lane adding) and leaves it in the scratch for the third launch.
-//   k_rc_aggscan one workgroup; reads and rewrites the tile maps in place (8 (K + 1) B per tile, RC_AGG_UNIT maps per trip): the
-//                exclusive scan, map t becoming the composition of the maps 0 .. t - 1.
+//   k_fmk_agg_scan (fmk_wgscan.h) one workgroup; reads and rewrites the tile maps in place (8 (K + 1) B per tile, RC_AGG_UNIT maps per
+//                trip): the exclusive scan, map t becoming the composition of the maps 0 .. t - 1.
 //   k_rc_apply   reads the inputs again (8 B per element and series) and writes the output (8 B per element): the state that enters a
 //                thread is the scanned tile map composed with the maps of the threads before it; from there the thread steps through
 //                its elements with the reference's own expression.  Only that carried-in state is not the reference's arithmetic.

@@ -1,11 +1,13 @@
 // fmk_recur_core.h -- the scan core of the first-order recurrences s[t] = a * s[t-1] + b[t] with one constant a on K channels
-// (fmk_recur.hip, fmk_runsum.hip; DESIGN.md sections 7e and 7f): the maps and their composition, the workgroup scan, the 8-element
-// loads and stores, the seed sum and the three launches.  A specification (see fmk_recur.hip) says what the elements are.
+// (fmk_recur.hip, fmk_runsum.hip; DESIGN.md sections 7e and 7f): the maps and their composition (a monoid of fmk_wgscan.h, where the
+// workgroup scan and the second launch, RC_AGG_UNIT tile maps per trip, come from), the 8-element loads and stores, the seed sum and
+// the three launches.  A specification (see fmk_recur.hip) says what the elements are.
 #pragma once
 #include <math.h>
 
 #include "fmk_common.h"
 #include "fmk_dpp.h"
+#include "fmk_wgscan.h"
 
 #define RC_THREADS 256
 #define RC_ITEMS 8                   // consecutive elements per thread: four 16-byte loads per series
@@ -42,41 +44,22 @@ __device__ __forceinline__ RcMap<K> rc_compose(const RcMap<K> &f, const RcMap<K>
     return r;
 }
 
-template <int CTRL, int ROW_MASK, int K>
-__device__ __forceinline__ RcMap<K> rc_dpp(const RcMap<K> &m)
-{
-    RcMap<K> r;
-    r.a = fmk_dpp<CTRL, ROW_MASK>(1.0, m.a);
-#pragma unroll
-    for (int k = 0; k < K; ++k) r.b[k] = fmk_dpp<CTRL, ROW_MASK>(0.0, m.b[k]);
-    return r;
-}
-
-// The maps of the workgroup's 256 threads in thread order: returns the composition of the threads before this one, *total = of all.
-// Lanes without a source compose with the identity, which is exact.  Two barriers: may be called again at once.
+// the composition of RcMap<K> as a monoid of fmk_wgscan.h
 template <int K>
-__device__ __forceinline__ RcMap<K> rc_block_exclusive(const RcMap<K> &mine, RcMap<K> *lds /* [4] */, RcMap<K> *total)
-{
-    const int lane = fmk_lane(), w = threadIdx.x >> 6;
-    RcMap<K> inc = mine;
-    inc = rc_compose(rc_dpp<FMK_DPP_ROW_SHR(1), 0xF>(inc), inc);
-    inc = rc_compose(rc_dpp<FMK_DPP_ROW_SHR(2), 0xF>(inc), inc);
-    inc = rc_compose(rc_dpp<FMK_DPP_ROW_SHR(4), 0xF>(inc), inc);
-    inc = rc_compose(rc_dpp<FMK_DPP_ROW_SHR(8), 0xF>(inc), inc);
-    inc = rc_compose(rc_dpp<FMK_DPP_ROW_BCAST15, 0xA>(inc), inc);
-    inc = rc_compose(rc_dpp<FMK_DPP_ROW_BCAST31, 0xC>(inc), inc);
-    if (lane == 63) lds[w] = inc;
-    __syncthreads();
-    RcMap<K> pre = rc_identity<K>();
-    for (int k = 0; k < w; ++k) pre = rc_compose(pre, lds[k]);
-    RcMap<K> tot = lds[0];
+struct RcMonoid {
+    using T = RcMap<K>;
+    static __device__ __forceinline__ T identity() { return rc_identity<K>(); }
+    static __device__ __forceinline__ T combine(const T &first, const T &then) { return rc_compose(first, then); }
+    template <int CTRL, int ROW_MASK>
+    static __device__ __forceinline__ T dpp(const T &m)
+    {
+        T r;
+        r.a = fmk_dpp<CTRL, ROW_MASK>(1.0, m.a);
 #pragma unroll
-    for (int k = 1; k < RC_THREADS / 64; ++k) tot = rc_compose(tot, lds[k]);
-    *total = tot;
-    const RcMap<K> prev = rc_dpp<FMK_DPP_WAVE_SHR1, 0xF>(inc);      // lane 0: the identity
-    __syncthreads();
-    return rc_compose(pre, prev);
-}
+        for (int k = 0; k < K; ++k) r.b[k] = fmk_dpp<CTRL, ROW_MASK>(0.0, m.b[k]);
+        return r;
+    }
+};
 
 // ---- the thread's 8 consecutive elements.  whole: every element of the workgroup's tile exists and none of them is element 0
 // (uniform over the workgroup); the other tiles read element by element with range checks (0.0 for what is not there).
@@ -204,27 +187,8 @@ __global__ __launch_bounds__(RC_THREADS) void k_rc_tiles(S sp, int64_t n, RcMap<
     typename S::In in;
     const RcMap<K> m = rc_thread_map(sp, blockIdx.x, n, sv, in);
     RcMap<K> tot;
-    (void)rc_block_exclusive(m, wl, &tot);
+    (void)fmk_wg_exclusive<RcMonoid<K>, RC_THREADS / 64>(m, wl, &tot);
     if (threadIdx.x == 0) tile_map[blockIdx.x] = tot;
-}
-
-// second launch, one workgroup: maps[t] <- the composition of maps[0 .. t - 1], RC_AGG_UNIT maps per trip, the next trip's loaded
-// ahead of the scan (a trip writes below the next one's maps only)
-template <int K>
-__global__ __launch_bounds__(RC_THREADS) void k_rc_aggscan(RcMap<K> *maps, int64_t m)
-{
-    __shared__ RcMap<K> wl[RC_THREADS / 64];
-    RcMap<K> run = rc_identity<K>();
-    RcMap<K> nxt = (int64_t)threadIdx.x < m ? maps[threadIdx.x] : rc_identity<K>();
-    for (int64_t b = 0; b < m; b += RC_AGG_UNIT) {
-        const int64_t i = b + threadIdx.x;
-        const RcMap<K> v = nxt;
-        nxt = i + RC_AGG_UNIT < m ? maps[i + RC_AGG_UNIT] : rc_identity<K>();
-        RcMap<K> tot;
-        const RcMap<K> ex = rc_block_exclusive(v, wl, &tot);
-        if (i < m) maps[i] = rc_compose(run, ex);
-        run = rc_compose(run, tot);
-    }
 }
 
 // Two optional members of a specification (fmk_runsum.hip).  NOUT > 1: emit(s, in, j, r) gives NOUT values per element, series c of
@@ -250,7 +214,7 @@ __global__ __launch_bounds__(RC_THREADS) void k_rc_apply(S sp, int64_t n, const 
     typename S::In in;
     const RcMap<K> m = rc_thread_map(sp, blockIdx.x, n, sv, in);
     RcMap<K> tot;
-    const RcMap<K> ex = rc_block_exclusive(m, wl, &tot);
+    const RcMap<K> ex = fmk_wg_exclusive<RcMonoid<K>, RC_THREADS / 64>(m, wl, &tot);
     const RcMap<K> pre = tile_pre[blockIdx.x];                       // applied to the zero state: its b
     double s[K];
 #pragma unroll
@@ -312,7 +276,7 @@ int rc_scan(fmk_ctx *ctx, const S &sp, int64_t n, double *d_out, double before)
     double *seedv = (double *)(maps + tiles);
     k_rc_tiles<S><<<(unsigned)tiles, RC_THREADS, 0, ctx->stream>>>(sp, n, maps, seedv);
     FMK_LAUNCH_CHECK(ctx);
-    k_rc_aggscan<S::K><<<1, RC_THREADS, 0, ctx->stream>>>(maps, tiles);
+    k_fmk_agg_scan<RcMonoid<S::K>, RC_AGG_UNIT><<<1, RC_AGG_UNIT, 0, ctx->stream>>>(maps, tiles, nullptr);
     FMK_LAUNCH_CHECK(ctx);
     k_rc_apply<S><<<(unsigned)tiles, RC_THREADS, 0, ctx->stream>>>(sp, n, maps, seedv, d_out);
     FMK_LAUNCH_CHECK(ctx);

@@ -1,15 +1,26 @@
 // fmk_scan.h -- device-wide exclusive scan of int64 (reduce-then-scan, three launches).
 //   k_scan_tile_sums : one 256-thread block per 4096-element tile -> tile total
-//   k_scan_tile_scan : ONE 1024-thread block scans the tile totals in place (B/4096 elements)
+//   k_fmk_agg_scan   : ONE 1024-thread block scans the tile totals in place (B/4096 elements), FMK_SCAN_AGG_UNIT per trip
 //   k_scan_apply     : per tile: block scan of the elements + tile offset, in place
+// The workgroup scan and the second launch are those of fmk_wgscan.h with the monoid ScanSum.
 // Used for CSR offsets of the footprint output (B elements) -- tiny next to the tick streams.
 #pragma once
 
 #include "fmk_common.h"
+#include "fmk_wgscan.h"
 
 #define FMK_SCAN_THREADS 256
 #define FMK_SCAN_ROWS 16
 #define FMK_SCAN_TILE (FMK_SCAN_THREADS * FMK_SCAN_ROWS)
+#define FMK_SCAN_AGG_UNIT 1024       // tile totals per trip of the aggregate scan
+
+namespace {
+struct ScanSum : FmkScalarDpp<ScanSum, int64_t> {
+    using T = int64_t;
+    static __device__ __forceinline__ int64_t identity() { return 0; }
+    static __device__ __forceinline__ int64_t combine(int64_t first, int64_t then) { return first + then; }
+};
+}  // namespace
 
 static __global__ __launch_bounds__(FMK_SCAN_THREADS) void k_scan_tile_sums(const int64_t *__restrict__ in, int64_t n,
                                                                      int64_t *__restrict__ tile_sum)
@@ -28,50 +39,20 @@ static __global__ __launch_bounds__(FMK_SCAN_THREADS) void k_scan_tile_sums(cons
     if (threadIdx.x == 0) tile_sum[blockIdx.x] = sw[0] + sw[1] + sw[2] + sw[3];
 }
 
-// exclusive scan in place; total written to *total
-static __global__ __launch_bounds__(1024) void k_scan_tile_scan(int64_t *t, int64_t m, int64_t *total)
-{
-    __shared__ int64_t ws[16];
-    __shared__ int64_t run;
-    if (threadIdx.x == 0) run = 0;
-    __syncthreads();
-    const int lane = fmk_lane(), w = threadIdx.x >> 6;
-    for (int64_t b = 0; b < m; b += 1024) {
-        int64_t i = b + threadIdx.x;
-        int64_t v = i < m ? t[i] : 0;
-        int64_t iv = fmk_wave_iscan(v);
-        if (lane == 63) ws[w] = iv;
-        __syncthreads();
-        int64_t o = run;
-        for (int k = 0; k < w; ++k) o += ws[k];
-        if (i < m) t[i] = o + iv - v;
-        __syncthreads();
-        if (threadIdx.x == 1023) run = o + iv;
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) *total = run;
-}
-
-// out[j] = tile_off[tile] + exclusive prefix within the tile; out[n] = total when j == n-1 is seen
+// out[j] = tile_off[tile] + exclusive prefix within the tile, one workgroup scan per row of FMK_SCAN_THREADS elements
 static __global__ __launch_bounds__(FMK_SCAN_THREADS) void k_scan_apply(const int64_t *__restrict__ in, int64_t n,
                                                                  const int64_t *__restrict__ tile_off,
                                                                  int64_t *__restrict__ out)
 {
-    __shared__ int64_t ws[4];
-    const int lane = fmk_lane(), w = threadIdx.x >> 6;
+    __shared__ int64_t ws[FMK_SCAN_THREADS / 64];
     const int64_t base = (int64_t)blockIdx.x * FMK_SCAN_TILE;
     int64_t run = tile_off[blockIdx.x];
     for (int r = 0; r < FMK_SCAN_ROWS; ++r) {
-        int64_t j = base + r * FMK_SCAN_THREADS + threadIdx.x;
-        int64_t v = j < n ? in[j] : 0;
-        int64_t iv = fmk_wave_iscan(v);
-        if (lane == 63) ws[w] = iv;
-        __syncthreads();
-        int64_t o = run;
-        for (int k = 0; k < w; ++k) o += ws[k];
-        run += ws[0] + ws[1] + ws[2] + ws[3];
-        if (j < n) out[j] = o + iv - v;
-        __syncthreads();
+        const int64_t j = base + r * FMK_SCAN_THREADS + threadIdx.x;
+        int64_t tot;
+        const int64_t ex = fmk_wg_exclusive<ScanSum, FMK_SCAN_THREADS / 64>(j < n ? in[j] : 0, ws, &tot);
+        if (j < n) out[j] = run + ex;
+        run += tot;
     }
 }
 
@@ -86,12 +67,11 @@ static inline int fmk_exclusive_scan_i64(fmk_ctx *ctx, const int64_t *d_in, int6
     }
     const int64_t tiles = fmk_ceil_div(n, FMK_SCAN_TILE);
     void *scr;
-    FMK_TRY(fmk_scratch(ctx, (size_t)(tiles + 1) * 8, &scr));
+    FMK_TRY(fmk_scratch(ctx, (size_t)tiles * 8, &scr));
     int64_t *tile = (int64_t *)scr;
     k_scan_tile_sums<<<(unsigned)tiles, FMK_SCAN_THREADS, 0, ctx->stream>>>(d_in, n, tile);
     FMK_LAUNCH_CHECK(ctx);
-    int64_t *total = write_total_at_n ? d_out + n : tile + tiles;
-    k_scan_tile_scan<<<1, 1024, 0, ctx->stream>>>(tile, tiles, total);
+    k_fmk_agg_scan<ScanSum, FMK_SCAN_AGG_UNIT><<<1, FMK_SCAN_AGG_UNIT, 0, ctx->stream>>>(tile, tiles, write_total_at_n ? d_out + n : nullptr);
     FMK_LAUNCH_CHECK(ctx);
     k_scan_apply<<<(unsigned)tiles, FMK_SCAN_THREADS, 0, ctx->stream>>>(d_in, n, tile, d_out);
     FMK_LAUNCH_CHECK(ctx);

@@ -21,6 +21,7 @@
 #include "fmk_log.h"
 #include "fmk_exp.h"
 #include "fmk_dpp.h"
+#include "fmk_wgscan.h"
 
 // ---------------------------------------------------------------------------------------
 // comp_lagged_returns
@@ -373,50 +374,31 @@ __device__ __forceinline__ double ew_sigma(double V, double V2, double Sy, doubl
 }
 
 
-__device__ __forceinline__ EwMap ew_shfl_up(const EwMap &m, int d)
-{
-    EwMap r;
-    r.a = __shfl_up(m.a, d, 64); r.a2 = __shfl_up(m.a2, d, 64);
-    r.bV = __shfl_up(m.bV, d, 64); r.bV2 = __shfl_up(m.bV2, d, 64);
-    r.bSy = __shfl_up(m.bSy, d, 64); r.bSyy = __shfl_up(m.bSyy, d, 64);
-    return r;
-}
-
-template <int CTRL, int ROW_MASK>
-__device__ __forceinline__ EwMap ew_dpp(const EwMap &m)
-{
-    return EwMap{fmk_dpp<CTRL, ROW_MASK>(1.0, m.a), fmk_dpp<CTRL, ROW_MASK>(1.0, m.a2), fmk_dpp<CTRL, ROW_MASK>(0.0, m.bV),
-                 fmk_dpp<CTRL, ROW_MASK>(0.0, m.bV2), fmk_dpp<CTRL, ROW_MASK>(0.0, m.bSy), fmk_dpp<CTRL, ROW_MASK>(0.0, m.bSyy)};
-}
-
-// inclusive scan of maps across the 256 threads of a block (thread order = tick order);
-// returns the EXCLUSIVE prefix for this thread, *block_total = composition of all threads
-template <int NW = 4>
-__device__ __forceinline__ EwMap ew_block_exclusive(const EwMap &mine, EwMap *lds /*[NW]*/, EwMap *block_total)
-{
-    const int lane = fmk_lane(), w = threadIdx.x >> 6;
-    EwMap inc = mine;
-    // ordered scan over the lanes on the DPP path (the order of fmk_dpp_iscan; lanes without a source compose with the identity,
-    // which is exact).  The shuffle version cost 84 ds_bpermute per 512 ticks.
-    inc = ew_compose(ew_dpp<FMK_DPP_ROW_SHR(1), 0xF>(inc), inc);
-    inc = ew_compose(ew_dpp<FMK_DPP_ROW_SHR(2), 0xF>(inc), inc);
-    inc = ew_compose(ew_dpp<FMK_DPP_ROW_SHR(4), 0xF>(inc), inc);
-    inc = ew_compose(ew_dpp<FMK_DPP_ROW_SHR(8), 0xF>(inc), inc);
-    inc = ew_compose(ew_dpp<FMK_DPP_ROW_BCAST15, 0xA>(inc), inc);
-    inc = ew_compose(ew_dpp<FMK_DPP_ROW_BCAST31, 0xC>(inc), inc);
-    if (lane == 63) lds[w] = inc;
-    __syncthreads();
-    EwMap pre = ew_identity();
-    for (int k = 0; k < w; ++k) pre = ew_compose(pre, lds[k]);
-    EwMap tot = lds[0];
-    for (int k = 1; k < NW; ++k) tot = ew_compose(tot, lds[k]);
-    *block_total = tot;
-    // exclusive prefix of this thread = (waves before) o (lanes before in my wave)
-    EwMap prev = ew_shfl_up(inc, 1);
-    if (lane == 0) prev = ew_identity();
-    __syncthreads();
-    return ew_compose(pre, prev);
-}
+// the composition of EwMap as a monoid of fmk_wgscan.h: the workgroup scan of the tick maps (thread order = tick order) comes from
+// there, an ordered scan over the lanes on the DPP path (the shuffle version cost 84 ds_bpermute per 512 ticks)
+struct EwMonoid {
+    using T = EwMap;
+    static __device__ __forceinline__ EwMap identity() { return ew_identity(); }
+    static __device__ __forceinline__ EwMap combine(const EwMap &first, const EwMap &then) { return ew_compose(first, then); }
+    template <int CTRL, int ROW_MASK>
+    static __device__ __forceinline__ EwMap dpp(const EwMap &m)
+    {
+        if constexpr (CTRL == FMK_DPP_WAVE_SHR1) {
+            // An exception to the monoid contract of fmk_wgscan.h (every field through fmk_dpp): the one-lane shift behind the scan is
+            // six shuffles.  As DPP moves it cost k_ew_apply<2> and k_ew_onepass_d<1|2> 2 to 27 VGPRs (profiles/wgscan_refactor_isa.txt),
+            // and k_ew_apply is built for five waves per SIMD.
+            EwMap r;
+            r.a = __shfl_up(m.a, 1, 64); r.a2 = __shfl_up(m.a2, 1, 64);
+            r.bV = __shfl_up(m.bV, 1, 64); r.bV2 = __shfl_up(m.bV2, 1, 64);
+            r.bSy = __shfl_up(m.bSy, 1, 64); r.bSyy = __shfl_up(m.bSyy, 1, 64);
+            if (fmk_lane() == 0) r = ew_identity();
+            return r;
+        } else {
+            return EwMap{fmk_dpp<CTRL, ROW_MASK>(1.0, m.a), fmk_dpp<CTRL, ROW_MASK>(1.0, m.a2), fmk_dpp<CTRL, ROW_MASK>(0.0, m.bV),
+                         fmk_dpp<CTRL, ROW_MASK>(0.0, m.bV2), fmk_dpp<CTRL, ROW_MASK>(0.0, m.bSy), fmk_dpp<CTRL, ROW_MASK>(0.0, m.bSyy)};
+        }
+    }
+};
 
 // The thread's 8 consecutive ticks straight from memory, 16 bytes per load (4 + 4 instructions; every 128-byte line is shared
 // by two lanes): no LDS.  A transposing tile in LDS (round 1) cost 36.8 KB per workgroup -- four workgroups per CU -- and
@@ -543,7 +525,7 @@ __global__ __launch_bounds__(EW_THREADS) void k_ew_tile_maps(const int64_t *__re
     double yl[EW_ITEMS], al[EW_ITEMS];
     const EwMap m = ew_thread_ticks<MODE>(ts, y, blockIdx.x, n, half_life, yl, al);
     EwMap tot;
-    (void)ew_block_exclusive(m, lds, &tot);
+    (void)fmk_wg_exclusive<EwMonoid, EW_THREADS / 64>(m, lds, &tot);
     if (threadIdx.x == 0) tile_map[blockIdx.x] = tot;
 }
 
@@ -558,7 +540,7 @@ __global__ __launch_bounds__(EW_THREADS) void k_ew_group_maps(const EwMap *__res
     const int64_t i = (int64_t)blockIdx.x * EW_THREADS + threadIdx.x;
     EwMap v = i < m ? maps[i] : ew_identity();
     EwMap tot;
-    (void)ew_block_exclusive(v, lds, &tot);
+    (void)fmk_wg_exclusive<EwMonoid, EW_THREADS / 64>(v, lds, &tot);
     if (threadIdx.x == 0) group_map[blockIdx.x] = tot;
 }
 
@@ -569,7 +551,7 @@ __global__ __launch_bounds__(EW_THREADS) void k_ew_group_apply(EwMap *__restrict
     const int64_t i = (int64_t)blockIdx.x * EW_THREADS + threadIdx.x;
     EwMap v = i < m ? maps[i] : ew_identity();
     EwMap tot;
-    EwMap ex = ew_block_exclusive(v, lds, &tot);
+    EwMap ex = fmk_wg_exclusive<EwMonoid, EW_THREADS / 64>(v, lds, &tot);
     if (group_pre) ex = ew_compose(group_pre[blockIdx.x], ex);
     if (i < m) maps[i] = ex;
 }
@@ -656,7 +638,7 @@ __global__ __launch_bounds__(EW_THREADS, 5) void k_ew_apply(const int64_t *__res
     double yl[EW_ITEMS], al[EW_ITEMS];
     const EwMap m = ew_thread_ticks<MODE>(ts, y, blockIdx.x, n, half_life, yl, al);
     EwMap tot;
-    EwMap ex = ew_block_exclusive(m, lds, &tot);
+    EwMap ex = fmk_wg_exclusive<EwMonoid, EW_THREADS / 64>(m, lds, &tot);
     ex = ew_compose(tile_pre[blockIdx.x], ex);
     double V, V2, Sy, Syy;
     ew_enter(ex, state_in, V, V2, Sy, Syy);
@@ -743,12 +725,12 @@ __device__ __forceinline__ EwMap ew_fetch(const unsigned long long *rec)
 // lane 0 holds the NEWEST map, lane 63 the oldest: the composition oldest first, wave-uniform
 __device__ __forceinline__ EwMap ew_wave_compose_newest_first(EwMap x)
 {
-    x = ew_compose(x, ew_dpp<FMK_DPP_ROW_SHR(1), 0xF>(x));
-    x = ew_compose(x, ew_dpp<FMK_DPP_ROW_SHR(2), 0xF>(x));
-    x = ew_compose(x, ew_dpp<FMK_DPP_ROW_SHR(4), 0xF>(x));
-    x = ew_compose(x, ew_dpp<FMK_DPP_ROW_SHR(8), 0xF>(x));
-    x = ew_compose(x, ew_dpp<FMK_DPP_ROW_BCAST15, 0xA>(x));
-    x = ew_compose(x, ew_dpp<FMK_DPP_ROW_BCAST31, 0xC>(x));
+    x = ew_compose(x, EwMonoid::dpp<FMK_DPP_ROW_SHR(1), 0xF>(x));
+    x = ew_compose(x, EwMonoid::dpp<FMK_DPP_ROW_SHR(2), 0xF>(x));
+    x = ew_compose(x, EwMonoid::dpp<FMK_DPP_ROW_SHR(4), 0xF>(x));
+    x = ew_compose(x, EwMonoid::dpp<FMK_DPP_ROW_SHR(8), 0xF>(x));
+    x = ew_compose(x, EwMonoid::dpp<FMK_DPP_ROW_BCAST15, 0xA>(x));
+    x = ew_compose(x, EwMonoid::dpp<FMK_DPP_ROW_BCAST31, 0xC>(x));
     return EwMap{fmk_last_lane(x.a), fmk_last_lane(x.a2), fmk_last_lane(x.bV), fmk_last_lane(x.bV2), fmk_last_lane(x.bSy), fmk_last_lane(x.bSyy)};
 }
 
@@ -811,7 +793,7 @@ __global__ __launch_bounds__(THREADS, OCC) void k_ew_onepass_d(const int64_t *__
     double yl[EW_ITEMS], al[EW_ITEMS];
     const EwMap m = ew_thread_ticks<MODE, THREADS>(ts, y, tile, n, half_life, yl, al);
     EwMap tot;
-    EwMap ex = ew_block_exclusive<THREADS / 64>(m, lds, &tot);
+    EwMap ex = fmk_wg_exclusive<EwMonoid, THREADS / 64>(m, lds, &tot);
     if (threadIdx.x < 64) {
         EwMap excl = ew_identity();
         ew_publish(D.A + 12 * tile, D.tagA + tile, tot, lane);
@@ -838,7 +820,7 @@ __global__ __launch_bounds__(EW_THREADS) void k_ew_total(const EwMap *__restrict
         const int64_t i = b + threadIdx.x;
         EwMap v = i < m ? maps[i] : ew_identity();
         EwMap tot;
-        (void)ew_block_exclusive(v, lds, &tot);
+        (void)fmk_wg_exclusive<EwMonoid, EW_THREADS / 64>(v, lds, &tot);
         run = ew_compose(run, tot);
     }
     if (threadIdx.x == 0) {

@@ -195,6 +195,47 @@ def test_cusum_sigma_is_filled_lazily(orc, monkeypatch, lead, hole):
             assert _last_tier()[0] == 1
 
 
+FF_TILE = 2048            # ticks per tile of the sigma forward fill (FF_TILE, csrc/fmk_cusum.hip)
+TRIP = 1024               # tile aggregates per trip of its one-workgroup scan (FF_AGG_UNIT)
+
+
+@pytest.mark.parametrize("case", ["hole_over_the_edge", "leading_nans_over_the_edge"])
+def test_cusum_sigma_fill_carry_crosses_a_trip_of_the_tile_scan(orc, monkeypatch, case):
+    """TRIP + 3 tiles: the scan of the tiles' last valid sigma takes a second trip.  hole_over_the_edge: sigma is valid at one index
+    of tile TRIP - 2 with a value of its own (lam = 2 * 4e-4 wherever it is filled in), NaN from there through tile TRIP, valid again
+    from tile TRIP + 1 on: the value crosses the trip edge.  leading_nans_over_the_edge: NaN from tick 0 through tile TRIP, so the first
+    valid index lies in trip 1 and "none" crosses.  Closes and the filled sigma as the reference leaves them, filled up front and lazily."""
+    from finmlkit_amd.bar.logic import _cusum_bar_indexer
+    monkeypatch.setenv("FMK_CUSUM_CHAIN_MIN_CHUNKS", "2")
+    n = TRIP * FF_TILE + 2 * FF_TILE + 5
+    ts, px = _stream(orc, n, 29, vol=2e-6, same_ts=0.25)
+    sigma = np.full(n, 1e-7)
+    if case == "hole_over_the_edge":
+        h = (TRIP - 2) * FF_TILE + 1000
+        sigma[(TRIP - 2) * FF_TILE:h] = np.nan
+        sigma[h] = 4e-4
+        sigma[h + 1:(TRIP + 1) * FF_TILE] = np.nan
+        lr = np.diff(np.log(px), prepend=np.log(px[0]))
+        lr[h:(TRIP + 1) * FF_TILE] *= 50.0                        # a busy stretch: a threshold of 8e-4 closes other bars than the floor
+        px = px[0] * np.exp(np.cumsum(lr))
+    else:
+        sigma[:(TRIP + 1) * FF_TILE + 3] = np.nan
+    want, wfilled = orc._cusum_bar_indexer(ts, px, sigma, 5e-4, 2.0, return_sigma=True)
+    if case == "hole_over_the_edge":
+        assert (wfilled[h:(TRIP + 1) * FF_TILE] == 4e-4).all() and not np.isnan(wfilled).any()
+        other = sigma.copy()
+        other[h] = 1e-7                                            # the filled value matters
+        assert not np.array_equal(orc._cusum_bar_indexer(ts, px, other, 5e-4, 2.0), want)
+    else:
+        assert np.isnan(wfilled[:(TRIP + 1) * FF_TILE + 3]).all() and not np.isnan(wfilled[(TRIP + 1) * FF_TILE + 3:]).any()
+    for lazy in ("0", "1"):
+        monkeypatch.setenv("FMK_CUSUM_LAZY_FILL", lazy)
+        s = sigma.copy()
+        got = _cusum_bar_indexer(ts, px, s, 5e-4, 2.0)
+        np.testing.assert_array_equal(got, want, err_msg=f"lazy {lazy}")
+        np.testing.assert_array_equal(s, wfilled, err_msg=f"lazy {lazy}")
+
+
 def test_cusum_chain_walk_falls_back(orc, monkeypatch):
     """Decisions that block sums cannot settle at every tick (forced: margins scaled by 1e12), a non-finite return (a zero
     price) and a tape whose thresholds are reached often (the budget of opened chunks) all hand the call to the fixed point:

@@ -415,6 +415,34 @@ def test_footprints_bars_of_many_levels(orc, w, amounts):
         assert (lev > 2048).any()
 
 
+SCAN_TILE = 4096          # bars per tile of the offsets' exclusive scan (FMK_SCAN_TILE, csrc/fmk_scan.h)
+TRIP = 1024               # tile totals per trip of its one-workgroup scan (FMK_SCAN_AGG_UNIT)
+
+
+def test_footprint_offsets_scan_takes_a_second_trip():
+    """fmk_comp_bar_footprints_size_dev on TRIP tiles + 4097 bars of 1 .. 3 levels on a tick grid: the scan of the tile totals carries
+    its running sum into a second trip, and the total comes out of that trip.  The bars are built as tests/_vp_ref.csr builds them
+    (prices are level * tick, a bar of c levels has its high c - 1 levels above its low), so the expected counts are the drawn c and the
+    offsets their exclusive cumulative sum; _vp_ref.csr itself takes Python lists per bar and is not called at this size."""
+    import ctypes as C
+    from finmlkit_amd import _ffi
+    from finmlkit_amd._ffi import DeviceArray, c_f64, c_i64
+    nb, tick = TRIP * SCAN_TILE + SCAN_TILE + 1, 0.5
+    rng = np.random.default_rng(31)
+    low = rng.integers(1000, 1100, nb)
+    counts = rng.integers(1, 4, nb)
+    want = np.zeros(nb + 1, np.int64)
+    want[1:] = np.cumsum(counts)
+    ctx = _ffi.default_context()
+    lows, highs = DeviceArray.from_host(ctx, low * tick), DeviceArray.from_host(ctx, (low + counts - 1) * tick)
+    off = DeviceArray(ctx, nb + 1, np.int64)
+    tot, mx = c_i64(), c_i64()
+    ctx.call("fmk_comp_bar_footprints_size_dev", lows.p, highs.p, c_i64(nb), c_f64(tick), off.p, C.byref(tot), C.byref(mx))
+    got = off.to_host()
+    np.testing.assert_array_equal(got, want)
+    assert got[nb] == counts.sum() and tot.value == counts.sum() and mx.value == 3
+
+
 @pytest.mark.parametrize("amounts", ["dyadic", "full"])
 def test_footprints_exact_level_class_edges(orc, amounts):
     """Bars whose level count sits exactly on and one beyond every class edge of the wave kernel (128, 256, 512, 768, 1 024, 1 536,

@@ -75,6 +75,36 @@ def test_tick_rule_vs_oracle(orc, n):
     np.testing.assert_array_equal(comp_trade_side_vector(px), orc.comp_trade_side_vector(px))
 
 
+SV_TILE = 2048            # ticks per tile of the tick rule (SV_TILE, csrc/fmk_preprocess.hip)
+TRIP = 1024               # tile aggregates per trip of its one-workgroup scan (the width of k_side_scan_tiles)
+
+
+@pytest.mark.parametrize("case", ["move_before_the_edge", "one_move", "flat"])
+def test_tick_rule_carry_crosses_a_trip_of_the_tile_scan(orc, case):
+    """TRIP + 2 tiles: the scan of the tile aggregates takes a second trip, and what crosses its edge is
+    move_before_the_edge: the last significant move (a down move) lies in tile TRIP - 2, the price is flat through tiles TRIP - 1 and
+    TRIP, and moves resume in tile TRIP + 1; one_move: the only move is at tick 1, so the carry of trip 0 serves every later tile;
+    flat: no move at all, the identity crosses and every side is 0."""
+    from finmlkit_amd.bar.utils import comp_trade_side_vector
+    n = TRIP * SV_TILE + SV_TILE + 1
+    px = np.full(n, 100.0)
+    if case == "move_before_the_edge":
+        k = (TRIP - 2) * SV_TILE + 700                      # the first flat tick, in tile TRIP - 2
+        px[:k - 1] = 100.0 + np.cumsum(np.random.default_rng(7).choice([-0.01, 0.0, 0.0, 0.01], k - 1))
+        px[k - 1:] = px[k - 2] - 0.01
+        px[n - 1] += 0.01                                   # the one tick of tile TRIP + 1
+    elif case == "one_move":
+        px[1:] = 100.01
+    want = orc.comp_trade_side_vector(px)
+    if case == "move_before_the_edge":
+        assert (want[k - 1:n - 1] == -1).all() and want[n - 1] == 1
+    elif case == "one_move":
+        assert want[0] == 0 and (want[1:] == 1).all()
+    else:
+        assert not want.any()
+    np.testing.assert_array_equal(comp_trade_side_vector(px), want)
+
+
 def test_tradesdata_preprocess_golden():
     """TradesData(preprocess=True) end to end == the reference's own object (ms timestamps, shuffled rows, duplicated
     ids, an id gap across two minutes; maker flags / tick rule; proc_res rounding)."""
