@@ -4,19 +4,21 @@
 // tolerances of tests/golden/shape.json and its NaN positions exactly.  DESIGN.md section 7c3.
 //
 // A window that reads a NaN or an infinity gives NaN (pandas' rolling turns +-inf into NaN and wants a full window).  With w the window:
-//   kurtosis  t >= w - 1 over x[t-w+1 .. t]: m = sum / w, m2 = sum((x-m)^2) / w, m4 = sum(((x-m)^2)^2) / w, out = m4 / (m2 * m2) - 3
-//             (0 / 0 = NaN on a constant window)
+//   kurtosis  t >= w - 1 over x[t-w+1 .. t]: m = sum / w, m2 = sum((x-m)^2) / w, m4 = sum(((x-m)^2)^2) / w, out = m4 / (m2 * m2) - 3;
+//             NaN where the w elements all compare equal (whatever fl(sum / w) is: a held price has no kurtosis), and 0 / 0 = NaN
 //   slope     t >= w - 1 over y = ln x (x finite and > 0, NaN otherwise): out = atan(sum((p - (w-1)/2) * (y_p - mean y)) /
 //             (w (w^2 - 1) / 12)) * (180 / pi), p = 0 .. w-1 (0 / 0 = NaN at w = 1)
 //   hurst     t >= w - 1, w >= 9: for k in 1, 2, 4, 8 the population variance v_k of the w - k sums of k consecutive elements of
 //             x[t-w+2 .. t]; tau_k = sqrt(v_k); all four > 0: (-1.5 ln tau_1 - 0.5 ln tau_2 + 0.5 ln tau_4 + 1.5 ln tau_8) / (5 ln 2),
-//             NaN otherwise.  x[t-w+1] enters no sum and still has to be finite.
+//             NaN otherwise, and NaN where for some k the w - k staged sums D_k all compare equal (tau_k is 0 for the numbers held
+//             here, whatever the rounded mean leaves).  x[t-w+1] enters no sum and still has to be finite.
 //   bipower   t >= w over x[t-w .. t]: out = sqrt(pi / 2) * sum_{j = t-w+1 .. t} |x[j]| * |x[j-1]|
 // Schedule: the lockstep window walk of fmk_window.h.  The loader makes every non-finite element NaN while it stages, so plain NaN
 // propagation through the sums gives the NaN outputs.  Kurtosis, slope and hurst walk twice (sums, then sums about the lane's own
 // means) and stage twice only when the span takes more than one slab; bipower walks once over products formed at staging.  A lane
 // counts the elements it has taken for an output: the walk delivers a window's elements in ascending order, so the count is the
-// position in the window (the slope's weight, and which of hurst's sums are whole yet).
+// position in the window (the slope's weight, and which of hurst's sums are whole yet).  Kurtosis and hurst compare, in the first
+// walk, every word they take with the window's last one, which the lane reads for itself: the words themselves, never deviations.
 #include <limits.h>
 
 #include "fmk_common.h"
@@ -73,9 +75,19 @@ __global__ __launch_bounds__(SHAPE_BLOCK) void k_kurtosis(ShapeArgs a)
     auto load = [x, lo](int64_t i) { return shape_finite(x[lo + i]); };
 
     double s[SHAPE_OPL], m[SHAPE_OPL], q[SHAPE_OPL];                 // the sum, then the sum of d^4; the mean; the sum of d^2
+    double last[SHAPE_OPL];                                          // the window's last element (first walk only)
+    int same[SHAPE_OPL];                                             // elements of the window == the last (a NaN never is)
 #pragma unroll
-    for (int r = 0; r < SHAPE_OPL; ++r) s[r] = 0.0;
-    fmk_window_walk<SHAPE_BLOCK, SHAPE_OPL>(shape_lds, tl.span, a.window, a.slab, true, load, [&](int r, double v) { s[r] += v; });
+    for (int r = 0; r < SHAPE_OPL; ++r) {
+        const int64_t t = tl.t0 + r * SHAPE_BLOCK + threadIdx.x;
+        s[r] = 0.0;
+        last[r] = t < tl.t1 ? load(t - lo) : 0.0;
+        same[r] = 0;
+    }
+    fmk_window_walk<SHAPE_BLOCK, SHAPE_OPL>(shape_lds, tl.span, a.window, a.slab, true, load, [&](int r, double v) {
+        s[r] += v;
+        same[r] += v == last[r];
+    });
     const double w = (double)a.window;
 #pragma unroll
     for (int r = 0; r < SHAPE_OPL; ++r) { m[r] = s[r] / w; s[r] = 0.0; q[r] = 0.0; }
@@ -89,7 +101,8 @@ __global__ __launch_bounds__(SHAPE_BLOCK) void k_kurtosis(ShapeArgs a)
         const int64_t t = tl.t0 + r * SHAPE_BLOCK + threadIdx.x;
         if (t >= tl.t1) continue;
         const double m2 = q[r] / w, m4 = s[r] / w;
-        a.out[t] = m4 / (m2 * m2) - 3.0;                             // 0 / 0 on a constant window
+        // all equal: no kurtosis; 0 / 0 where the squares underflow
+        a.out[t] = same[r] != (int)a.window ? m4 / (m2 * m2) - 3.0 : NAN;
     }
 }
 
@@ -146,7 +159,9 @@ __global__ __launch_bounds__(SHAPE_BLOCK) void k_bipower(ShapeArgs a, double sca
 
 // The walk is over the window's last w - 1 elements; word i holds the sums ending at x[i], and d1 also carries x[i-1]'s finiteness:
 // every window that walks word i reads x[i-1] too, and the one that starts its walk at i has x[i-1] as the element that enters no sum.
-__global__ __launch_bounds__(SHAPE_BLOCK) void k_hurst(ShapeArgs a)
+// Five waves per SIMD is what 32 KiB of LDS per workgroup allows; asking for it keeps the first walk's last words and counts within
+// 96 VGPRs.
+__global__ __launch_bounds__(SHAPE_BLOCK) __attribute__((amdgpu_waves_per_eu(5))) void k_hurst(ShapeArgs a)
 {
     extern __shared__ HurstWord hurst_lds[];
     const int64_t walk = a.window - 1;
@@ -169,8 +184,15 @@ __global__ __launch_bounds__(SHAPE_BLOCK) void k_hurst(ShapeArgs a)
     double s1[HURST_OPL], s2[HURST_OPL], s4[HURST_OPL], s8[HURST_OPL];   // the sums, then the sums of squared deviations
     double m1[HURST_OPL], m2[HURST_OPL], m4[HURST_OPL], m8[HURST_OPL];
     int cnt[HURST_OPL];                                              // words taken: lag k's sums are whole from the k-th word on
+    HurstWord last[HURST_OPL];                                       // the window's last word, which every lag takes (first walk only)
+    int e1[HURST_OPL], e2[HURST_OPL], e4[HURST_OPL], e8[HURST_OPL];  // the D_k of the window == the last one (a NaN never is)
 #pragma unroll
-    for (int r = 0; r < HURST_OPL; ++r) { s1[r] = 0.0; s2[r] = 0.0; s4[r] = 0.0; s8[r] = 0.0; cnt[r] = 0; }
+    for (int r = 0; r < HURST_OPL; ++r) {
+        const int64_t t = tl.t0 + r * SHAPE_BLOCK + threadIdx.x;
+        s1[r] = 0.0; s2[r] = 0.0; s4[r] = 0.0; s8[r] = 0.0; cnt[r] = 0;
+        e1[r] = 0; e2[r] = 0; e4[r] = 0; e8[r] = 0;
+        last[r] = load(t < tl.t1 ? t - lo : 0);
+    }
     fmk_window_walk<SHAPE_BLOCK, HURST_OPL>(hurst_lds, tl.span, walk, a.slab, true, load, [&](int r, HurstWord h) {
         const int c = cnt[r];
         const double t2 = s2[r] + h.d2, t4 = s4[r] + h.d4, t8 = s8[r] + h.d8;
@@ -178,9 +200,14 @@ __global__ __launch_bounds__(SHAPE_BLOCK) void k_hurst(ShapeArgs a)
         s2[r] = c >= 1 ? t2 : s2[r];
         s4[r] = c >= 3 ? t4 : s4[r];
         s8[r] = c >= 7 ? t8 : s8[r];
+        e1[r] += h.d1 == last[r].d1;
+        e2[r] += c >= 1 && h.d2 == last[r].d2;
+        e4[r] += c >= 3 && h.d4 == last[r].d4;
+        e8[r] += c >= 7 && h.d8 == last[r].d8;
         cnt[r] = c + 1;
     });
     const double w = (double)a.window;
+    const int iw = (int)a.window;
 #pragma unroll
     for (int r = 0; r < HURST_OPL; ++r) {
         m1[r] = s1[r] / (w - 1.0); m2[r] = s2[r] / (w - 2.0); m4[r] = s4[r] / (w - 4.0); m8[r] = s8[r] / (w - 8.0);
@@ -202,7 +229,8 @@ __global__ __launch_bounds__(SHAPE_BLOCK) void k_hurst(ShapeArgs a)
         if (t >= tl.t1) continue;
         const double u1 = sqrt(s1[r] / (w - 1.0)), u2 = sqrt(s2[r] / (w - 2.0)), u4 = sqrt(s4[r] / (w - 4.0)), u8 = sqrt(s8[r] / (w - 8.0));
         double o = NAN;
-        if (u1 > 0.0 && u2 > 0.0 && u4 > 0.0 && u8 > 0.0)            // a NaN fails the comparison
+        const bool varies = e1[r] != iw - 1 && e2[r] != iw - 2 && e4[r] != iw - 4 && e8[r] != iw - 8;   // no lag's sums all equal
+        if (varies && u1 > 0.0 && u2 > 0.0 && u4 > 0.0 && u8 > 0.0)  // a NaN fails the comparison
             o = (-1.5 * log(u1) - 0.5 * log(u2) + 0.5 * log(u4) + 1.5 * log(u8)) / (5.0 * M_LN2);
         a.out[t] = o;
     }

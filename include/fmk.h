@@ -599,14 +599,18 @@ int fmk_price_volume_corr(fmk_ctx *ctx, const double *price, const double *volum
 /* ---- window statistics of finmlkit/feature/transforms.py on a float64 series of n elements -> float64 array of n elements
  * (csrc/fmk_shape.hip): KurtosisTransform (:900-933), TrendSlope (:936-988), HurstExponent (:1341-1397), BiPowerVariation (:1551-1602).
  * Every window is recomputed on its own.  A window that reads a NaN or an infinity gives NaN; window > n gives NaN everywhere.
- *   kurtosis  t >= window - 1 over x[t-window+1 .. t]: m4 / (m2 * m2) - 3 of the biased central moments (NaN where m2 == 0).
+ *   kurtosis  t >= window - 1 over x[t-window+1 .. t]: m4 / (m2 * m2) - 3 of the biased central moments; NaN where the window's
+ *             elements all compare equal (==), whatever the rounded mean is, and where m2 == 0.
  *   slope     t >= window - 1: the least-squares slope of ln x on 0 .. window-1 as an angle, atan(slope) * 180 / pi; a price that is
  *             not finite and > 0 gives NaN; window 1 gives NaN.
  *   hurst     t >= window - 1, window >= 9: with tau_k the population standard deviation of the window - k sums of k consecutive
  *             elements of x[t-window+2 .. t], k = 1, 2, 4, 8: the least-squares slope of ln tau_k on ln k where all four are > 0,
- *             NaN otherwise (everywhere at window 9).  x[t-window+1] enters no sum and must be finite all the same.
+ *             NaN otherwise (everywhere at window 9), and NaN where for some k those window - k sums, as held in float64 (a tree,
+ *             oldest first inside a pair), all compare equal.  x[t-window+1] enters no sum and must be finite all the same.
  *   bipower   t >= window over x[t-window .. t]: sqrt(pi / 2) * the sum of |x[j]| * |x[j-1]|, j = t-window+1 .. t.
- * The reference's values within the tolerances of tests/golden/shape.json, its NaN positions exactly.
+ * The reference's values within the tolerances of tests/golden/shape.json, its NaN positions exactly --
+ * except, on purpose, that a window without a statistic (a held price: the two NaN rules above) gives NaN where the reference may
+ * return rounding noise; elsewhere the exact value within the per-family tolerances of tests/golden/shape_degenerate.json.
  * FMK_E_ARG, checked before a device is touched and before any pointer is looked at: window < 1 (the reference returns all NaN or
  * zeros there), hurst with window < 9 (the reference raises TypeError), n >= 2^31. */
 int fmk_rolling_kurtosis_dev(fmk_ctx *ctx, const double *d_x, int64_t n, int64_t window, double *d_out);

@@ -10,6 +10,9 @@ With w the window; a window that reads a NaN or an infinity gives NaN:
     hurst     t >= w-1, w >= 9: tau_k = sqrt(population variance of the w-k sums of k consecutive elements of x[t-w+2 .. t]),
               k = 1, 2, 4, 8; all > 0: (-1.5 ln tau_1 - 0.5 ln tau_2 + 0.5 ln tau_4 + 1.5 ln tau_8) / (5 ln 2), else NaN
     bipower   t >= w over x[t-w .. t]: sqrt(pi / 2) * sum(|x[j]| * |x[j-1]|, j = t-w+1 .. t)
+A window without a statistic gives NaN: kurtosis where the w elements all compare equal (==, so +0 and -0 are equal), hurst where for
+some k the w - k sums of k elements, as they are held in float64, all compare equal.  The elements and sums themselves are compared,
+not their deviations from a rounded mean, which would leave m2 = delta^2 or tau_k = delta on a held 99.55.
 The sums of k elements are formed as a tree ((a + b) + (c + d)) + ..., oldest first inside a pair, the way the kernel's loader forms
 them; the logarithm of a price is libm's (math.log), which the kernel restates."""
 import hashlib
@@ -48,7 +51,46 @@ def mantissa_returns(n, seed):
     return np.where(rng.integers(0, 2, n) == 1, k, -k)
 
 
-GENERATORS = {"grid_walk": grid_walk, "dyadic_returns": dyadic_returns, "mantissa_returns": mantissa_returns}
+def grid_normal(n, seed, base, denom):
+    """base + k / denom with k a seeded bell-shaped integer of standard deviation 101 (the sum of four uniform draws: integer
+    arithmetic and one correctly rounded division, so every machine regenerates the same bits): prices like 100 + round(z, 2)."""
+    k = np.random.default_rng(seed).integers(-87, 88, (n, 4)).sum(axis=1)
+    return base + k / float(denom)
+
+
+def held_series(n, seed, base, denom, runs=()):
+    """grid_normal values, each held for a seeded run of 1 .. 140 elements, cut to n; then every (start, length) of `runs` holds
+    x[start] for `length` elements (a run laid where the walk changes hands)."""
+    lens = np.random.default_rng(seed + 1).integers(1, 141, n)
+    x = np.repeat(grid_normal(n, seed, base, denom), lens)[:n].copy()
+    for start, length in runs:
+        x[start:start + length] = x[start]
+    return x
+
+
+def levels(n, seed, base, denom, count):
+    """base + k / denom, k seeded and uniform on 0 .. count - 1."""
+    return base + np.random.default_rng(seed).integers(0, count, n) / float(denom)
+
+
+def constant(n, value):
+    return np.full(n, float(value))
+
+
+def one_odd(n, value, pos, odd):
+    """A constant series with one other element."""
+    x = np.full(n, float(value))
+    x[pos] = odd
+    return x
+
+
+def periodic(n, values):
+    return np.resize(np.asarray(values, np.float64), n)
+
+
+GENERATORS = {"grid_walk": grid_walk, "dyadic_returns": dyadic_returns, "mantissa_returns": mantissa_returns,
+              "grid_normal": grid_normal, "held_series": held_series, "levels": levels, "constant": constant, "one_odd": one_odd,
+              "periodic": periodic}
 
 
 def generate(source):
@@ -99,6 +141,8 @@ def _tree(e):
 def _scalar_window(fn, win, w):
     """One output from the w (bipower: w + 1) elements of its window, all finite."""
     if fn == "kurtosis":
+        if all(v == win[-1] for v in win):                             # a held value has no kurtosis, whatever fl(sum / w) is
+            return NAN
         s = 0.0
         for v in win:
             s = s + v
@@ -127,6 +171,8 @@ def _scalar_window(fn, win, w):
         logs = []
         for k in LAGS:
             d = [_tree(win[j + 1:j + k + 1]) for j in range(w - k)]
+            if all(v == d[-1] for v in d):                             # tau_k is 0 for the sums as they are held
+                return NAN
             s = 0.0
             for v in d:
                 s = s + v
@@ -169,9 +215,11 @@ def _vector(fn, x, w):
     with np.errstate(all="ignore"):
         if fn in ("kurtosis", "slope"):
             v = _finite(x) if fn == "kurtosis" else _log_prices(x)
-            s = np.zeros(m)
+            s, differs = np.zeros(m), np.zeros(m, bool)
             for p in range(w):
                 s = s + v[p:p + m]
+                if fn == "kurtosis":
+                    differs |= v[p:p + m] != v[w - 1:w - 1 + m]         # against the window's last element; a NaN differs
             mean = s / fw
             if fn == "kurtosis":
                 q2, q4 = np.zeros(m), np.zeros(m)
@@ -181,7 +229,7 @@ def _vector(fn, x, w):
                     q2 = q2 + d2
                     q4 = q4 + d2 * d2
                 m2, m4 = q2 / fw, q4 / fw
-                out[first:] = m4 / (m2 * m2) - 3.0
+                out[first:] = np.where(differs, m4 / (m2 * m2) - 3.0, np.nan)
             else:
                 acc, centre = np.zeros(m), (fw - 1.0) / 2.0
                 for p in range(w):
@@ -204,10 +252,12 @@ def _vector(fn, x, w):
             d8 = ((e[7] + e[6]) + (e[5] + e[4])) + d4
             words = (d1, d2, d4, d8)
             sums = [np.zeros(m) for _ in LAGS]
+            varies = [np.zeros(m, bool) for _ in LAGS]                 # some D_k of the window != its last one (a NaN differs)
             for p in range(w - 1):                                     # output j walks words j + 1 .. j + w - 1
                 for c, k in enumerate(LAGS):
                     if p >= k - 1:
                         sums[c] = sums[c] + words[c][p + 1:p + 1 + m]
+                        varies[c] |= words[c][p + 1:p + 1 + m] != words[c][w - 1:w - 1 + m]
             means = [sums[c] / (fw - k) for c, k in enumerate(LAGS)]
             sq = [np.zeros(m) for _ in LAGS]
             for p in range(w - 1):
@@ -216,7 +266,7 @@ def _vector(fn, x, w):
                         dev = words[c][p + 1:p + 1 + m] - means[c]
                         sq[c] = sq[c] + dev * dev
             tau = [np.sqrt(sq[c] / (fw - k)) for c, k in enumerate(LAGS)]
-            good = (tau[0] > 0) & (tau[1] > 0) & (tau[2] > 0) & (tau[3] > 0)
+            good = (tau[0] > 0) & (tau[1] > 0) & (tau[2] > 0) & (tau[3] > 0) & varies[0] & varies[1] & varies[2] & varies[3]
             safe = [np.where(good, t, 1.0) for t in tau]
             logs = [np.array([math.log(v) for v in t.tolist()]) for t in safe]
             h = (-1.5 * logs[0] - 0.5 * logs[1] + 0.5 * logs[2] + 1.5 * logs[3]) / (5.0 * math.log(2.0))
