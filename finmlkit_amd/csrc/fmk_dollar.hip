@@ -31,6 +31,7 @@
 #include <stdlib.h>
 
 #include "fmk_common.h"
+#include "../../include/fmk_diag.h"
 #include <type_traits>
 
 struct DD { double hi, lo; };
@@ -721,10 +722,17 @@ int fmk_dollar_exact(fmk_ctx *ctx, const double *d_price, const void *d_amount, 
 // (every decision certain), 1 closed form + exact tier, 2 closed form + exact tier on a stream with increments >= thr (stretch walk),
 // 3 the serial walk (the fill half of a count-then-fill pair answers from the cache and leaves the value alone)
 static int g_dl_last_path = -1;
-static int g_dl_onepass = 0;           // the closed form of the last call came from the one-pass kernel (fmk_dollar_onepass.h)
+static int g_dl_onepass = 0;           // the closed form the last call computed: 1 the one-pass kernel (fmk_dollar_onepass.h), 2 dl_run, 0 neither
+static int g_dl_cached = 0;            // the last call was the fill half of a count-then-fill pair, answered from the cache
 extern "C" int fmk_diag_dollar_last(int64_t *path)
 {
     *path = g_dl_last_path;
+    return FMK_OK;
+}
+extern "C" int fmk_diag_dollar_source(int64_t *closed_form, int64_t *cached)
+{
+    *closed_form = g_dl_onepass;
+    *cached = g_dl_cached;
     return FMK_OK;
 }
 
@@ -734,8 +742,10 @@ extern "C" int fmk_dollar_bar_indexer_dev(fmk_ctx *ctx, const double *d_price, c
 {
     if (n <= 0) return fmk_set_error(ctx, FMK_E_ARG, "threshold indexer: empty input");
     // the closed form needs thr > 0 and non-negative increments; anything else takes the serial walk
+    g_dl_cached = 0;
     if (!(threshold > 0.0) || getenv("FMK_THRESHOLD_SERIAL")) {
         g_dl_last_path = 3;
+        g_dl_onepass = 0;
         return fmk_threshold_serial(ctx, 1, d_price, d_amount, amount_is_f64, n, threshold, d_close_idx, capacity,
                                     n_idx, n_uncertified);
     }
@@ -746,10 +756,12 @@ extern "C" int fmk_dollar_bar_indexer_dev(fmk_ctx *ctx, const double *d_price, c
     if (!hit) {
         int rc = amount_is_f64 ? dl1_run<true>(ctx, d_price, d_amount, n, threshold, c)
                                : dl1_run<false>(ctx, d_price, d_amount, n, threshold, c);
-        g_dl_onepass = rc == FMK_OK;
-        if (rc == 1)
+        g_dl_onepass = rc == FMK_OK ? 1 : 0;
+        if (rc == 1) {
             rc = amount_is_f64 ? dl_run<true>(ctx, d_price, d_amount, n, threshold, c)
                                : dl_run<false>(ctx, d_price, d_amount, n, threshold, c);
+            if (rc == FMK_OK) g_dl_onepass = 2;
+        }
         if (rc == 1) {
             g_dl_last_path = 3;
             return fmk_threshold_serial(ctx, 1, d_price, d_amount, amount_is_f64, n, threshold, d_close_idx, capacity,
@@ -759,7 +771,7 @@ extern "C" int fmk_dollar_bar_indexer_dev(fmk_ctx *ctx, const double *d_price, c
         g_dl_last_path = 0;
         c.ctx = ctx; c.amount = d_amount; c.price = d_price; c.n = n; c.thr = threshold; c.is_f64 = amount_is_f64;
         ctx->idx_key[1][0] = d_amount; ctx->idx_key[1][1] = d_price; ctx->idx_stale[1] = 0;
-    }
+    } else g_dl_cached = 1;
     // test knob (read per call): FMK_DL_FORCE_EXACT_TIER=1 runs the exact tier even when the closed form is already certain
     const char *fv = getenv("FMK_DL_FORCE_EXACT_TIER");
     const int force_sim = fv ? atoi(fv) : 0;

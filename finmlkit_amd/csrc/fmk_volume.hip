@@ -31,6 +31,7 @@
 #include <stdlib.h>
 
 #include "fmk_common.h"
+#include "../../include/fmk_diag.h"
 
 #define VOL_END 0xFFFFFFFFu
 // threads per workgroup of k_vol_level0.  The workgroup's LDS (53.3 KB: three per CU) does not depend on it, so this sets
@@ -535,6 +536,47 @@ void fmk_volume_trim(fmk_ctx *ctx)
 }
 
 static int vol_certify(fmk_ctx *ctx, const void *a, int is_f64, int64_t n, double thr, VolCache &c);
+
+// what the ladder of the last fmk_volume_bar_indexer[_dev] call of this process did (tests; include/fmk_diag.h:
+// fmk_diag_volume_last).  Host bookkeeping only: nothing here decides anything.
+static struct VolDiag {
+    int tier;
+    unsigned tried;
+    int codes[FMK_VOL_TIER_COUNT];
+    double est_len, mean_len;
+    int64_t listed;
+} g_vol_diag = {FMK_VOL_TIER_NONE, 0u, {0}, NAN, NAN, 0};
+static void vol_diag_reset()
+{
+    g_vol_diag.tier = FMK_VOL_TIER_NONE;
+    g_vol_diag.tried = 0u;
+    for (int t = 0; t < FMK_VOL_TIER_COUNT; ++t) g_vol_diag.codes[t] = 0;
+    g_vol_diag.est_len = g_vol_diag.mean_len = NAN;
+    g_vol_diag.listed = 0;
+}
+// the return code of tier t, passed through: FMK_OK answers, 1 .. 4 decline (errors are the call's, not a tier's)
+static int vol_note(int t, int rc)
+{
+    if (rc == FMK_OK) g_vol_diag.tier = t;
+    else if (rc >= 1 && rc <= 4) { g_vol_diag.tried |= 1u << t; g_vol_diag.codes[t] = rc; }
+    return rc;
+}
+// the sample pass and the total pass answer nothing: only a decline (2: a negative / NaN amount) is kept
+static void vol_note_pass(int t, int rc)
+{
+    if (rc != FMK_OK) (void)vol_note(t, rc);
+}
+extern "C" int fmk_diag_volume_last(int64_t *tier, int64_t *tried, int64_t *codes, double *est_len, double *mean_len,
+                                    int64_t *listed)
+{
+    *tier = g_vol_diag.tier;
+    *tried = (int64_t)g_vol_diag.tried;
+    for (int t = 0; t < FMK_VOL_TIER_COUNT; ++t) codes[t] = g_vol_diag.codes[t];
+    *est_len = g_vol_diag.est_len;
+    *mean_len = g_vol_diag.mean_len;
+    *listed = g_vol_diag.listed;
+    return FMK_OK;
+}
 
 #include "fmk_volume_exact.h"     // the exact-sum tier (round 4): k_vx_level0, k_vx_emit, vx_run
 
@@ -1434,6 +1476,7 @@ static int vol_certify(fmk_ctx *ctx, const void *a, int is_f64, int64_t n, doubl
     int64_t listed;
     FMK_TRY(fmk_read_back(ctx, &listed, c.d_list, 8));
     c.unc = listed;
+    g_vol_diag.listed = listed;
     if (listed == 0 || ctx->fast_threshold) return FMK_OK;
     if (listed > VOL_LIST_CAP) return 3;
     FMK_HIP(ctx, hipMemsetAsync(d_mis, 0, sizeof *d_mis, ctx->stream));
@@ -1587,9 +1630,12 @@ extern "C" int fmk_volume_bar_indexer_dev(fmk_ctx *ctx, const void *d_amount, in
 {
     if (n <= 0) return fmk_set_error(ctx, FMK_E_ARG, "threshold indexer: empty input");
     const bool serial = !(threshold > 0.0) || n >= ((int64_t)1 << 31) - 4096 || getenv("FMK_THRESHOLD_SERIAL");
-    if (serial)
+    vol_diag_reset();
+    if (serial) {
+        g_vol_diag.tier = FMK_VOL_TIER_SERIAL;
         return fmk_threshold_serial(ctx, 0, nullptr, d_amount, amount_is_f64, n, threshold, d_close_idx, capacity,
                                     n_idx, n_uncertified);
+    }
     FMK_HIP(ctx, hipSetDevice(ctx->device));
     VolCache &c = vol_cache(ctx);
     const bool hit = c.ctx == ctx && !ctx->idx_stale[0] && c.amount == d_amount && c.n == n && c.thr == threshold &&
@@ -1603,7 +1649,9 @@ extern "C" int fmk_volume_bar_indexer_dev(fmk_ctx *ctx, const void *d_amount, in
         int rcs = amount_is_f64 ? vol_chase<true>(ctx, d_amount, n, threshold, c, true, &est_total, false, ns)
                                 : vol_chase<false>(ctx, d_amount, n, threshold, c, true, &est_total, false, ns);
         if (rcs && rcs != 2) return rcs;
+        vol_note_pass(FMK_VOL_PASS_SAMPLE, rcs);
         const double est_len = est_total > 0.0 ? (double)ns * threshold / est_total : 1e300;
+        g_vol_diag.est_len = est_len;
         int rc = 1;
         // the exact-sum tier first (fmk_volume_exact.h): every window certifies that its float64 sums are exact, so there is no
         // tie zone to replay; entry tables for the first 1024 / 2048 ticks of 4096-tick blocks.  A window that does not certify or
@@ -1612,36 +1660,43 @@ extern "C" int fmk_volume_bar_indexer_dev(fmk_ctx *ctx, const void *d_amount, in
             // table span W >= the longest bar; the estimate is the MEAN length of the head of the stream, so each class leaves room
             // (x 1.6 / x 1.3) and a bar that is longer after all sends the call to the next class (flag, then one more attempt)
             if (est_len < 640.0)
-                rc = amount_is_f64 ? vx_run<true, 3072, 1024, 512, false>(ctx, d_amount, n, threshold, c)
-                                   : vx_run<false, 3072, 1024, 512, false>(ctx, d_amount, n, threshold, c);
+                rc = vol_note(FMK_VOL_TIER_EXACT_1024,
+                              amount_is_f64 ? vx_run<true, 3072, 1024, 512, false>(ctx, d_amount, n, threshold, c)
+                                            : vx_run<false, 3072, 1024, 512, false>(ctx, d_amount, n, threshold, c));
             // (a (3840, 1280) class with 640 threads -- a third of the rows per tick -- was measured: 7.3 against 6.3 ms at 865-tick bars;
             //  256 threads with twice the ticks per thread: no better)
             if (rc == 1 && est_len < 1150.0)
-                rc = amount_is_f64 ? vx_run<true, 2560, 1536, 512, false>(ctx, d_amount, n, threshold, c)
-                                   : vx_run<false, 2560, 1536, 512, false>(ctx, d_amount, n, threshold, c);
+                rc = vol_note(FMK_VOL_TIER_EXACT_1536,
+                              amount_is_f64 ? vx_run<true, 2560, 1536, 512, false>(ctx, d_amount, n, threshold, c)
+                                            : vx_run<false, 2560, 1536, 512, false>(ctx, d_amount, n, threshold, c));
             if (rc == 1)
-                rc = amount_is_f64 ? vx_run<true, 4096, 2048, 512, true>(ctx, d_amount, n, threshold, c)
-                                   : vx_run<false, 4096, 2048, 512, true>(ctx, d_amount, n, threshold, c);
+                rc = vol_note(FMK_VOL_TIER_EXACT_2048,
+                              amount_is_f64 ? vx_run<true, 4096, 2048, 512, true>(ctx, d_amount, n, threshold, c)
+                                            : vx_run<false, 4096, 2048, 512, true>(ctx, d_amount, n, threshold, c));
             if (rc == 4) rc = 1;                                    // does not certify: the tiers below
         }
         if (rc == 1 && est_len < 1800.0)
-            rc = amount_is_f64 ? vol_run<true, 2048>(ctx, d_amount, n, threshold, c)
-                               : vol_run<false, 2048>(ctx, d_amount, n, threshold, c);
+            rc = vol_note(FMK_VOL_TIER_LDS_2048, amount_is_f64 ? vol_run<true, 2048>(ctx, d_amount, n, threshold, c)
+                                                               : vol_run<false, 2048>(ctx, d_amount, n, threshold, c));
         if (rc == 1) {
             // a bar longer than 2048 ticks (or expected).  The exact mean bar length from the total volume decides the tier
             double total = 0.0;
             int rc2 = amount_is_f64 ? vol_chase<true>(ctx, d_amount, n, threshold, c, true, &total)
                                     : vol_chase<false>(ctx, d_amount, n, threshold, c, true, &total);
             if (rc2 && rc2 != 2) return rc2;
-            if (rc2 == 2 || rcs == 2)
+            vol_note_pass(FMK_VOL_PASS_TOTAL, rc2);
+            if (rc2 == 2 || rcs == 2) {
+                g_vol_diag.tier = FMK_VOL_TIER_SERIAL;
                 return fmk_threshold_serial(ctx, 0, nullptr, d_amount, amount_is_f64, n, threshold, d_close_idx, capacity,
                                             n_idx, n_uncertified);
+            }
             const double mean_len = total > 0.0 ? (double)n * threshold / total : 1e300;
+            g_vol_diag.mean_len = mean_len;
             bool prefix_ok = true;          // the table tiers build in c.work too: after one of them the prefix is gone
             if (est_len >= 1800.0 && mean_len < 1400.0) {    // the sample misled: short bars after all
                 prefix_ok = false;
-                rc = amount_is_f64 ? vol_run<true, 2048>(ctx, d_amount, n, threshold, c)
-                                   : vol_run<false, 2048>(ctx, d_amount, n, threshold, c);
+                rc = vol_note(FMK_VOL_TIER_LDS_2048_TOTAL, amount_is_f64 ? vol_run<true, 2048>(ctx, d_amount, n, threshold, c)
+                                                                         : vol_run<false, 2048>(ctx, d_amount, n, threshold, c));
             }
             // bars beyond the 2048-tick LDS tables: global tables up to ~64K ticks (26 ms at 1e9 ticks whatever the length;
             // the 4096-tick LDS tables this used to try first cost 33 ms), the chain walk beyond
@@ -1652,22 +1707,28 @@ extern "C" int fmk_volume_bar_indexer_dev(fmk_ctx *ctx, const void *d_amount, in
                     if (rc2) return rc2;
                     prefix_ok = true;
                 }
-                rc = vol_global_tables(ctx, d_amount, amount_is_f64, n, threshold, c, mean_len);
+                rc = vol_note(FMK_VOL_TIER_GLOBAL, vol_global_tables(ctx, d_amount, amount_is_f64, n, threshold, c, mean_len));
             }
             if (rc == 1)     // few, long bars: walk the chain with wave-parallel searches (total pass's prefix if still there)
-                rc = amount_is_f64 ? vol_chase<true>(ctx, d_amount, n, threshold, c, false, nullptr, prefix_ok)
-                                   : vol_chase<false>(ctx, d_amount, n, threshold, c, false, nullptr, prefix_ok);
+                rc = vol_note(FMK_VOL_TIER_CHAIN,
+                              amount_is_f64 ? vol_chase<true>(ctx, d_amount, n, threshold, c, false, nullptr, prefix_ok)
+                                            : vol_chase<false>(ctx, d_amount, n, threshold, c, false, nullptr, prefix_ok));
         }
         if (rc == 2 || rc == 3) rc = 1;
-        if (rc == 1)     // negative volumes, or a fragile decision whose replay disagrees
+        if (rc == 1) {   // negative volumes, or a fragile decision whose replay disagrees
+            g_vol_diag.tier = FMK_VOL_TIER_SERIAL;
             return fmk_threshold_serial(ctx, 0, nullptr, d_amount, amount_is_f64, n, threshold, d_close_idx, capacity,
                                         n_idx, n_uncertified);
+        }
         if (rc) return rc;
         c.ctx = ctx; c.amount = d_amount; c.n = n; c.thr = threshold; c.is_f64 = amount_is_f64;
         ctx->idx_key[0][0] = d_amount; ctx->idx_key[0][1] = nullptr; ctx->idx_stale[0] = 0;
-    }
+    } else g_vol_diag.tier = FMK_VOL_TIER_CACHED;
+    // (in the default mode no tier returns FMK_OK with c.unc > 0 -- vol_certify leaves 0 or returns 3, the exact-sum classes set 0 --
+    //  so this is the fill of a count made in the fast mode: tier SERIAL, nothing tried)
     if (c.unc > 0 && !ctx->fast_threshold) {      // see fmk_dollar_bar_indexer_dev
         c.ctx = nullptr;
+        g_vol_diag.tier = FMK_VOL_TIER_SERIAL;
         return fmk_threshold_serial(ctx, 0, nullptr, d_amount, amount_is_f64, n, threshold, d_close_idx, capacity, n_idx,
                                     n_uncertified);
     }

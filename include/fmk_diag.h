@@ -52,8 +52,42 @@ int fmk_diag_h2d_rate(fmk_ctx *ctx, size_t bytes, int mode, double *gbps);
 int fmk_diag_cusum_last(int64_t *tier, int64_t *opened, int64_t *status);
 /* Which path answered the last fmk_dollar_bar_indexer[_dev] call of this process: 0 the closed form alone (every decision certain),
  * 1 closed form + exact tier, 2 the same on a stream with increments >= threshold (block trades: the stretch walk of
- * fmk_dollar_exact.hip), 3 the serial walk, 4 a cached result. */
+ * fmk_dollar_exact.hip), 3 the serial walk.  include/fmk.h makes count (d_close_idx == NULL) and fill the two phases of ONE
+ * operation, so the fill half that answers from the cache leaves the value alone: after the pair it is the path that computed
+ * the closes (there is no path 4; fmk_diag_dollar_source says whether the last call was such a fill). */
 int fmk_diag_dollar_last(int64_t *path);
+/* The closed form behind the last fmk_dollar_bar_indexer[_dev] call of this process: *closed_form 1 the one-pass look-back kernel
+ * (csrc/fmk_dollar_onepass.h), 2 the two-pass kernels (dl_run, after the one-pass declined), 0 neither (the serial walk from the
+ * start, or both declined); it is the form the call COMPUTED, also where the exact tier or the serial walk then replaced its
+ * closes.  *cached 1: the call was the fill half of a count-then-fill pair and copied the count call's closes (then
+ * *closed_form still names the form that produced them), 0: it computed. */
+int fmk_diag_dollar_source(int64_t *closed_form, int64_t *cached);
+/* The ladder of the last fmk_volume_bar_indexer[_dev] call of this process (csrc/fmk_volume.hip), in the order it is climbed. */
+enum fmk_vol_tier {
+    FMK_VOL_TIER_NONE = -1,           /* no call yet, or the call failed before a tier answered */
+    FMK_VOL_TIER_EXACT_1024 = 0,      /* exact-sum class (S, W) = (3072, 1024)  (csrc/fmk_volume_exact.h) */
+    FMK_VOL_TIER_EXACT_1536 = 1,      /* exact-sum class (2560, 1536) */
+    FMK_VOL_TIER_EXACT_2048 = 2,      /* exact-sum class (4096, 2048) */
+    FMK_VOL_TIER_LDS_2048 = 3,        /* the 2048-tick LDS tables, chosen by the sample's estimate */
+    FMK_VOL_TIER_LDS_2048_TOTAL = 4,  /* the same tables after the total pass ("the sample misled") */
+    FMK_VOL_TIER_GLOBAL = 5,          /* the global tables */
+    FMK_VOL_TIER_CHAIN = 6,           /* the chain walk */
+    FMK_VOL_TIER_SERIAL = 7,          /* the serial walk (fmk_threshold.hip) */
+    FMK_VOL_TIER_CACHED = 8,          /* the fill half of a count-then-fill pair: the count call's closes, nothing tried */
+    FMK_VOL_PASS_SAMPLE = 9,          /* never answer; in the tried mask when the pass over the first 2^19 ticks ... */
+    FMK_VOL_PASS_TOTAL = 10,          /* ... or the total pass met a negative / NaN amount (code 2) */
+    FMK_VOL_TIER_COUNT = 11
+};
+/* *tier: the fmk_vol_tier that answered.  *tried: bit (1 << t) for every tier t that was tried and DECLINED (the answering tier is
+ * not in it); codes[t] (FMK_VOL_TIER_COUNT entries) its return code -- 1 next tier, 2 bad amounts, 3 a replay disagrees (vol_certify:
+ * k_vol_verify finds another close than the tier listed, or more decisions are listed than the list holds; from the global tables
+ * also: settling the fragile ticks would cost more than the serial walk), 4 a window does not certify -- and 0 for every other tier.
+ * One serial walk has no declining tier in front of it: a count call made in the fast mode (fmk_ctx_set_fast_threshold) that left
+ * uncertified decisions, filled in the default mode -- the fill reports FMK_VOL_TIER_SERIAL with an empty mask.  *est_len: the mean bar
+ * length the sample pass estimated (ns * thr / sum of the first ns = min(n, 2^19) amounts), *mean_len: n * thr / total of the total
+ * pass; NaN where the ladder did not compute one.  *listed: the fragile decisions the last tier that certified by replay listed on
+ * the chain BEFORE the replay (0: none, or no such tier ran). */
+int fmk_diag_volume_last(int64_t *tier, int64_t *tried, int64_t *codes, double *est_len, double *mean_len, int64_t *listed);
 /* order-flow redo since the last call: {(bar, column) pairs redone in tick order, 512-term tiles walked, tiles added term by term,
  * pairs of column 0 .. 6 (buy / sell volume, buy / sell dollars, spread, signed volume, signed dollars)} */
 int fmk_diag_dir_redo(fmk_ctx *ctx, int64_t *out10);

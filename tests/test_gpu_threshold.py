@@ -8,6 +8,26 @@ from tests import _golden as G
 
 pytestmark = pytest.mark.gpu
 
+from tests._tier_tapes import (BAD, CHAIN, E1024, E1536, E2048, GLOBAL, LDS, NOCERT, P_SAMPLE, P_TOTAL, REPLAY, SERIAL,  # noqa: E402
+                               estimates)
+
+
+def _volume_count_call(d_amount, thr):
+    """One count call (null output) of fmk_volume_bar_indexer_dev on a device column and what fmk_diag_volume_last says about it: the
+    NumPy-facing functions are a count call plus its fill, and the fill only reports the cache."""
+    import ctypes as C
+    from finmlkit_amd import _ffi
+    from tests._tier_tapes import read_volume_diag
+    m, unc = C.c_int64(), C.c_int64()
+    d_amount.ctx.call("fmk_volume_bar_indexer_dev", d_amount.p, C.c_int(1 if d_amount.dtype == np.float64 else 0), C.c_int64(d_amount.n),
+                      C.c_double(thr), None, C.c_int64(0), C.byref(m), C.byref(unc))
+    return dict(read_volume_diag(_ffi.lib()), count=m.value)
+
+
+def _way(d):
+    """(tier, {declining tier: code}) of a diagnostic"""
+    return d["tier"], {t: c for t, c in enumerate(d["codes"]) if c}
+
 
 def test_threshold_indexers_golden(orc):
     from finmlkit_amd.bar.logic import _dollar_bar_indexer, _volume_bar_indexer
@@ -38,7 +58,8 @@ def test_threshold_vs_oracle(orc, n, f64):
     if f64:
         am = np.random.default_rng(6).lognormal(-1, 1.3, n)
     mean_v = float(np.mean(am))
-    # 3000 ticks/bar: beyond the 2048-tick table span -> the 4096-tick tables; longer: wave-parallel chain walk
+    # 3 .. 1200 ticks/bar: the exact-sum classes (float32 sizes) or the 2048-tick LDS tables (lognormal float64 sizes); 3000 .. 70 000:
+    # beyond the 2048-tick table span -> the global tables; 400 000 and more: the wave-parallel chain walk
     for bar_ticks in (3, 50, 1200, 3000, 5000, 70_000, 400_000, 10**9):
         vthr = mean_v * bar_ticks
         np.testing.assert_array_equal(_volume_bar_indexer(am, vthr), orc._volume_bar_indexer(am, vthr),
@@ -66,6 +87,14 @@ def test_threshold_serial_walk_forced(orc, monkeypatch):
     t = engine.DeviceTrades.from_numpy(ts, px, am)
     t.volume_bar_index(float(np.mean(am)) * 300)
     assert t.last_uncertified == 0
+    # the serial walk answered both, without a tier tried or a closed form computed (count call and fill alike)
+    from finmlkit_amd import _ffi
+    from tests._tier_tapes import read_dollar_diag, read_volume_diag
+    d = read_volume_diag(_ffi.lib())
+    assert _way(d) == (SERIAL, {}) and np.isnan(d["est_len"]), d
+    assert _way(_volume_count_call(t.amount, float(np.mean(am)) * 300)) == (SERIAL, {})
+    t.dollar_bar_index(float(np.mean(am)) * 300 * float(px[0]))
+    assert read_dollar_diag(_ffi.lib()) == dict(path=3, closed_form=0, cached=0)
 
 
 def test_threshold_device_resident(orc):
@@ -124,11 +153,14 @@ def test_threshold_knife_edge_is_exact_by_default(orc):
 @pytest.mark.parametrize("seed,sigma,f64,L", [(1, 1.0, True, 3500), (3, 0.5, False, 8000), (4, 2.5, True, 6000),
                                              (5, 1.0, True, 20000), (6, 3.0, True, 12000), (7, 1.0, True, 40000)])
 def test_volume_bars_of_thousands_of_ticks_continuous_amounts(orc, seed, sigma, f64, L):
-    """Mean bar lengths between the LDS tables (<= 4096 ticks) and the chain walk: the global jump tables of
+    """Mean bar lengths between the LDS tables (<= 2048 ticks) and the chain walk (>= 65 536): the global jump tables of
     fmk_volume.hip (k_vg_nxt / k_vg_level0).  Lognormal amounts, so prefix-sum differences are NOT the reference's
     sequential sums and the certification is live; whales (bars of one tick among the long ones); streams shorter than
     one table span; a threshold that is some tick's sequential running sum to the last bit (decision 1 on a knife edge:
-    listed by the kernels, replayed by k_vol_verify, and redone serially when the replay disagrees)."""
+    listed by the kernels, replayed by k_vol_verify, and redone serially when the replay disagrees).  Every call gets as far as the
+    global tables (est_len and mean_len are ~L: no LDS tier is tried); the mean-length thresholds are answered by them."""
+    from finmlkit_amd import _ffi
+    from finmlkit_amd._ffi import DeviceArray
     from finmlkit_amd.bar.logic import _volume_bar_indexer
     rng = np.random.default_rng(seed)
     for n in (1_200_000, 70_001, 5_000):
@@ -139,11 +171,24 @@ def test_volume_bars_of_thousands_of_ticks_continuous_amounts(orc, seed, sigma, 
         edge = float(np.cumsum(am.astype(np.float64))[min(n - 1, L)])
         for t in (thr, edge):
             np.testing.assert_array_equal(_volume_bar_indexer(am, t), orc._volume_bar_indexer(am, t), err_msg=f"n={n} thr={t!r}")
+            d = _volume_count_call(DeviceArray.from_host(_ffi.default_context(), am), t)
+            print(f"n={n} thr={t!r}: tier {d['tier']} tried {d['tried']:#x} est_len {d['est_len']:.0f} mean_len {d['mean_len']:.0f}")
+            # est_len >= 1800 and 1400 <= mean_len < 65 536 on the host: the total pass, then the global tables, and nothing in front.
+            # The mean-length threshold is answered by them; the knife edge (and seed 6, whose amounts of 1e5 and more widen the tie
+            # zone of every block they sit in) may also end in the global tables' own code 3 and the serial walk.
+            est, mean = estimates(am, t)
+            assert est >= 1800.0 and 1400.0 <= mean < 65536.0, (est, mean)
+            if t == thr and seed != 6:
+                assert _way(d) == (GLOBAL, {}), d
+            else:
+                assert _way(d) in ((GLOBAL, {}), (SERIAL, {GLOBAL: REPLAY})), d
 
 
 def test_volume_long_bars_negative_amounts_take_the_serial_walk(orc):
     """Prefix sums must not decrease for any of the parallel tiers: a negative (or NaN) amount anywhere sends the input to
     the serial walk, whatever the bar length (the prefix pass of the long-bar tiers used not to look)."""
+    from finmlkit_amd import _ffi
+    from finmlkit_amd._ffi import DeviceArray
     from finmlkit_amd.bar.logic import _volume_bar_indexer
     rng = np.random.default_rng(11)
     for n, L in ((400_000, 5000), (400_000, 90_000), (3_000, 5000)):
@@ -151,6 +196,10 @@ def test_volume_long_bars_negative_amounts_take_the_serial_walk(orc):
         am[n // 2] = -3.0 * am[n // 2] - 50.0
         thr = float(np.abs(am).mean()) * L
         np.testing.assert_array_equal(_volume_bar_indexer(am, thr), orc._volume_bar_indexer(am, thr), err_msg=f"n={n} L={L}")
+        # n < 2^19: the sample pass reads the whole tape and meets the amount (est_len ~ L >= 1800: no table tier is tried), the total
+        # pass meets it again and hands the call to the serial walk
+        d = _volume_count_call(DeviceArray.from_host(_ffi.default_context(), am), thr)
+        assert _way(d) == (SERIAL, {P_SAMPLE: BAD, P_TOTAL: BAD}) and d["est_len"] >= 1800.0, d
 
 
 def test_volume_exact_mode_certifies_on_the_chain_only(orc):
@@ -189,7 +238,9 @@ def test_volume_decimal_lots_round_threshold(orc, f64):
     """Decimal lots with a round threshold: sums of 0.1, 0.2, ... hit the threshold EXACTLY in one summation order and
     miss it by an ulp in another (100 x 0.1 is 9.99999999999998 in tick order).  An exact tie of the parallel evaluation
     is therefore certain only for exactly-summable streams (multiples of 2^-20: the kernels check); here every such tie
-    must be listed and replayed -- on all tiers (bar lengths 50 .. 200 000 ticks)."""
+    must be listed and replayed -- on every tier that replays (bar lengths 50 .. 200 000 ticks): the parallel mode is answered by
+    the 2048-tick LDS tables (float64 tenths, after an exact-sum class refused its certificate; float32 tenths are multiples of
+    their own ulp and stay on the exact-sum classes), the global tables and the chain walk, in that order of thresholds."""
     from finmlkit_amd import _ffi, engine
     from finmlkit_amd.bar.logic import _volume_bar_indexer
     rng = np.random.default_rng(31)
@@ -203,6 +254,7 @@ def test_volume_decimal_lots_round_threshold(orc, f64):
         np.testing.assert_array_equal(_volume_bar_indexer(am, thr), want, err_msg=f"thr={thr}")
         ctx.set_fast_threshold(True)
         try:
+            d = _volume_count_call(t.amount, thr)
             fast = t.volume_bar_index(thr).to_host()
             unc = t.last_uncertified
         finally:
@@ -210,6 +262,10 @@ def test_volume_decimal_lots_round_threshold(orc, f64):
         reported += unc > 0
         if not np.array_equal(fast, want):
             assert unc > 0, f"thr={thr}: the parallel result differs from the reference without a reported decision"
+        # the parallel mode never replays, so the ladder is fixed by est_len = thr / 0.5 and the certificate alone
+        way = {25.0: (LDS, {E1024: 4}) if f64 else (E1024, {}), 500.0: (LDS, {E1536: 4}) if f64 else (E1536, {}),
+               1500.0: (GLOBAL, {}), 2500.0: (GLOBAL, {}), 10_000.0: (GLOBAL, {}), 100_000.0: (CHAIN, {})}[thr]
+        assert d["tier"] == way[0] and d["tried"] == sum(1 << k for k in way[1]) and all(d["codes"][k] == v for k, v in way[1].items()), (thr, d)
     if f64:
         assert reported >= 3, f"exact ties of decimal lots should be reported: {reported} of 6 thresholds"
 
@@ -238,17 +294,27 @@ def test_volume_integer_lots_ties_are_certain(orc):
 def test_volume_dyadic_lots_threshold_one_ulp_off_the_grid(orc):
     """Dyadic lots whose bars add up to EXACTLY the grid value just below the threshold: prefix + thr rounds to the grid, so
     the decision looks like an exact tie although the reference's `cum >= thr` is false (tools/fuzz_parity.py seed 778 case
-    121).  Ties count as certain only when the threshold is on the amounts' grid too.  All tiers: short, 4096-tick and
-    chain-walk bars."""
+    121).  Ties count as certain only when the threshold is on the amounts' grid too.  Bars of ~10 and ~700 ticks (the exact-sum
+    classes of 1024 and 1536 ticks, where the certificate makes every threshold's decision the reference's) and of ~2 950 and
+    ~22 000 ticks (both reach the global tables: no bar of this tape is long enough for the chain walk)."""
+    from finmlkit_amd import _ffi
+    from finmlkit_amd._ffi import DeviceArray
     from finmlkit_amd.bar.logic import _volume_bar_indexer
     rng = np.random.default_rng(33)
     n = 600_000
     am = (rng.integers(1, 65, n) * 0.125).astype(np.float32)
+    d_am = DeviceArray.from_host(_ffi.default_context(), am)
     for base in (40.0, 2840.5, 12_000.25, 90_000.0):
         for thr in (np.nextafter(base, np.inf), np.nextafter(base, -np.inf), base):
             got = _volume_bar_indexer(am, float(thr))
             want = orc._volume_bar_indexer(am, float(thr))
             np.testing.assert_array_equal(got, want, err_msg=f"thr={thr!r}")
+            d = _volume_count_call(d_am, float(thr))
+            rung = {40.0: E1024, 2840.5: E1536, 12_000.25: GLOBAL, 90_000.0: GLOBAL}[base]
+            if rung == GLOBAL:
+                assert _way(d) in ((GLOBAL, {}), (SERIAL, {GLOBAL: REPLAY})), (thr, d)
+            else:
+                assert d["tier"] == rung and d["tried"] == 0 and d["listed"] == 0, (thr, d)
     # the two neighbours of a grid value give different closes wherever a bar hits it exactly
     up, dn = orc._volume_bar_indexer(am, float(np.nextafter(2840.5, np.inf))), orc._volume_bar_indexer(am, 2840.5)
     assert not np.array_equal(up, dn)
@@ -268,11 +334,17 @@ def test_volume_decimal_lots_many_ties_stay_on_the_parallel_path(orc):
     want = orc._volume_bar_indexer(am, 25.0)
     ctx.set_fast_threshold(True)
     try:
+        d_fast = _volume_count_call(t.amount, 25.0)
         t.volume_bar_index(25.0)
         listed = t.last_uncertified
     finally:
         ctx.set_fast_threshold(False)
     assert listed > 4096, f"the construction should tie on thousands of closes: {listed}"
+    # est_len = 50: the (3072, 1024) class refuses float64 tenths their certificate, the 2048-tick LDS tables answer.  The parallel
+    # mode lists the ties on the chain; the default mode settles every fragile tick inside k_vol_level0 and lists none
+    assert _way(d_fast) == (LDS, {E1024: NOCERT}) and d_fast["listed"] == listed, d_fast
+    d = _volume_count_call(t.amount, 25.0)
+    assert _way(d) == (LDS, {E1024: NOCERT}) and d["listed"] == 0, d
     t.volume_bar_index(25.0); ctx.sync()
     t0 = time.perf_counter()
     got = t.volume_bar_index(25.0).to_host()
@@ -372,9 +444,10 @@ def _fast_mode(t, thr):
 
 def test_volume_chain_walk_reports_a_close_forced_onto_the_last_tick_of_a_block(orc):
     """tools/fuzz_volume.py seed 97015 case 2997 (the stream is the fixture: 36 689 lognormal float64 amounts, threshold = their
-    correctly rounded total, which the reference's sequential sum stays one part in 1e15 below: no bar).  The chain walk picks the
-    crossing block by double-double block totals and, when the plain in-block sums do not cross, closes on the block's last tick --
-    without listing the decision: the parallel mode answered one bar and reported nothing."""
+    correctly rounded total, which the reference's sequential sum stays one part in 1e15 below: no bar).  The chain walk picked the
+    crossing block by double-double block totals and, when the plain in-block sums did not cross, closed on the block's last tick --
+    without listing the decision: the parallel mode answered one bar and reported nothing.  (With est_len = mean_len = 36 689 the tape
+    is the global tables' today; tests/test_gpu_threshold_tiers.py pins its way through the ladder.)"""
     from finmlkit_amd import engine
     d = np.load(os.path.join(G.GOLDEN_DIR, "volume_total_tie_case.npz"))
     a, thr = d["a"], float(d["thr"])
@@ -392,7 +465,8 @@ def test_volume_chain_walk_reports_a_close_forced_onto_the_last_tick_of_a_block(
 @pytest.mark.parametrize("seed", range(12))
 def test_volume_threshold_at_the_rounded_total(orc, seed):
     """The same situation from seeds: thresholds at NumPy's (pairwise) total of the stream, where the exact sum, the pairwise sum and
-    the reference's sequential sum disagree in the last bits; lengths that put the stream on the chain walk and on the global tables."""
+    the reference's sequential sum disagree in the last bits; lengths that put the stream on the chain walk (mean_len >= 65 536), on
+    the global tables (1 800 .. 65 536) and on the 2048-tick LDS tables (below): the ladder gets as far as that rung on every seed."""
     from finmlkit_amd import engine
     rng = np.random.default_rng(9700 + seed)
     n = int(rng.choice([5_000, 36_689, 70_001, 200_000]))
@@ -406,6 +480,18 @@ def test_volume_threshold_at_the_rounded_total(orc, seed):
     assert t.last_uncertified == 0
     fast, unc = _fast_mode(t, thr)
     assert np.array_equal(fast, want) or unc > 0
+    d = _volume_count_call(t.amount, thr)
+    est, mean = estimates(a, thr)                                   # host sums (n < 2^19: the sample is the whole tape, est == mean)
+    assert min(abs(est - x) for x in (1150.0, 1500.0, 1800.0, 65536.0)) > 1e-6 * est
+    print(f"seed {seed}: n={n} k={k} est_len {est:.0f} tier {d['tier']} tried {d['tried']:#x}")
+    assert abs(d["est_len"] - est) <= 1e-9 * est, d
+    front = {} if est >= 1500.0 else {E1024 if est < 640.0 else E1536 if est < 1150.0 else E2048: NOCERT}   # lognormal float64: no certificate
+    if est < 1800.0:        # the LDS tables answer, or hand on (a bar beyond 2048 ticks: 1, a replay that disagrees: 3)
+        assert (d["tier"] == LDS and _way(d)[1] == front) or (d["codes"][LDS] in (1, 3) and all(d["codes"][t] == c for t, c in front.items())), d
+    elif mean < 65536.0:    # the global tables answer, or their replay / the chain walk's disagrees and the serial walk answers
+        assert _way(d) in ((GLOBAL, {}), (SERIAL, {GLOBAL: REPLAY}), (CHAIN, {GLOBAL: 1}), (SERIAL, {GLOBAL: 1, CHAIN: REPLAY})), d
+    else:
+        assert _way(d) in ((CHAIN, {}), (SERIAL, {CHAIN: REPLAY})), d
 
 
 @pytest.mark.parametrize("big", [1e9, 1e12])
