@@ -79,6 +79,11 @@ struct fmk_mail {
         int64_t ts_ends[2];                // k_lb_precheck: ts[0], ts[n-1] (the tape's tick rate)
         int64_t last[2];                   // host copy only: schedule (0 direct, 1 tables) and events of this context's last call
     } label;
+    struct Trend {                         // fmk_trend.hip
+        unsigned long long work;           // k_trend: next event of the persistent grid
+        long long skipped;                 // k_trend: events whose longest span does not fit, or all of whose spans are NaN
+        long long bad;                     // k_trend: event indices outside the series (the call fails)
+    } trend;
     struct Brk {                           // fmk_break.hip
         int nonpos;                        // k_brk_log: an element <= 0
         unsigned long long pairs, skipped; // k_brk_pairs: (t, n) pairs walked, pairs the den <= 1e-16 test dropped
@@ -275,6 +280,13 @@ static inline int fmk_rule_bar_rate(fmk_ctx *ctx, int64_t window_ns)
 }
 // the window statistics (fmk_shape.hip): hurst's lag 8 needs one difference (asked after fmk_rule_window)
 static inline int fmk_rule_hurst(fmk_ctx *ctx, int64_t window) { return fmk_rule_least(ctx, window, 9, "hurst_exponent: window must be at least 9."); }
+// trend scanning (fmk_trend.hip): a line through fewer than three points has no t-value
+static inline int fmk_rule_trend(fmk_ctx *ctx, int64_t min_len, int64_t max_len, int64_t step)
+{
+    FMK_TRY(fmk_rule_least(ctx, min_len, 3, "trend_scanning: min_len must be at least 3."));
+    if (max_len < min_len) return fmk_set_error(ctx, FMK_E_ARG, "trend_scanning: max_len must not be less than min_len.");
+    return fmk_rule_least(ctx, step, 1, "trend_scanning: step must be at least 1.");
+}
 // the approximate entropy (fmk_entropy.hip): the order-(m + 1) embedding needs one vector; one tile's span and the table of
 // logarithms have to fit in LDS; the kernels are instantiated per m
 #define FMK_APEN_MAX_M 4

@@ -534,6 +534,36 @@ int fmk_triple_barrier(fmk_ctx *ctx, const int64_t *ts, const double *close_, in
     return FMK_OK;
 }
 
+int fmk_trend_scanning(fmk_ctx *ctx, const double *y, int64_t n, const int64_t *event_idx, int64_t n_events, int64_t min_len,
+                       int64_t max_len, int64_t step, int8_t *labels, double *t_value, int64_t *touch_idx, double *ret,
+                       int64_t *n_skipped)
+{
+    FMK_TRY(fmk_rule_trend(ctx, min_len, max_len, step));
+    if (n_events < 0 || n < 0) return fmk_set_error(ctx, FMK_E_ARG, "negative dimensions are not allowed");
+    if (n_skipped) *n_skipped = 0;
+    if (n_events == 0) return FMK_OK;
+    if (n == 0) return fmk_set_error(ctx, FMK_E_ARG, "trend_scanning: event indices outside the (empty) series");
+    DevBag bag(ctx);
+    double *d_y, *d_t, *d_ret;
+    int64_t *d_ev, *d_touch, *d_skip;
+    int8_t *d_lab;
+    FMK_TRY(bag.up(y, n, &d_y));
+    FMK_TRY(bag.up(event_idx, n_events, &d_ev));
+    FMK_TRY(bag.out(n_events, &d_lab));
+    FMK_TRY(bag.out(n_events, &d_t));
+    FMK_TRY(bag.out(n_events, &d_touch));
+    FMK_TRY(bag.out(n_events, &d_ret));
+    FMK_TRY(bag.out(1, &d_skip));
+    FMK_TRY(fmk_memset(ctx, d_skip, 0, sizeof(int64_t)));
+    FMK_TRY(fmk_trend_scanning_dev(ctx, d_y, n, d_ev, n_events, min_len, max_len, step, d_lab, d_t, d_touch, d_ret, d_skip));
+    FMK_TRY(down(ctx, labels, d_lab, n_events));
+    FMK_TRY(down(ctx, t_value, d_t, n_events));
+    FMK_TRY(down(ctx, touch_idx, d_touch, n_events));
+    FMK_TRY(down(ctx, ret, d_ret, n_events));
+    FMK_TRY(down(ctx, n_skipped, d_skip, 1));
+    return FMK_OK;
+}
+
 int fmk_label_concurrency(fmk_ctx *ctx, const int64_t *event_idx, const int64_t *touch_idx, int64_t n_events, int64_t n,
                           int16_t *concurrency)
 {

@@ -582,6 +582,29 @@ class DeviceTrades:
                       c_f64(min_close_time_sec), c_f64(min_ret), out[0].p, out[1].p, out[2].p, out[3].p, skipped.p)
         return out + (skipped,)
 
+    def trend_scanning(self, event_idx: DeviceArray, min_len: int, max_len: int, step: int = 1,
+                       series: Optional[DeviceArray] = None):
+        """trend_scanning (label/trend_scanning.py, DESIGN.md section 7j) on a resident float64 series (default: the price column);
+        events are an int64 DeviceArray, as `cusum_filter` returns them.  -> (labels int8, t_value float64, touch_idx int64,
+        ret float64, n_skipped): n_skipped is a device int64 counting the events whose longest span runs past the end of the series
+        or all of whose spans hold a NaN (label 0, NaN, touch_idx = event_idx).  touch_idx is what `label_concurrency` and
+        `label_weights` take."""
+        from .label.trend_scanning import check_arguments
+        y = self.price if series is None else series
+        if y.dtype != np.float64:
+            raise TypeError(f"trend_scanning: the series must be float64, not {y.dtype}")
+        if event_idx.dtype != np.int64:
+            raise TypeError(f"trend_scanning: the event indices must be int64, not {event_idx.dtype}")
+        min_len, max_len, step = check_arguments(y.n, None, min_len, max_len, step)
+        ne = event_idx.n
+        out = (DeviceArray(self.ctx, ne, np.int8), DeviceArray(self.ctx, ne, np.float64), DeviceArray(self.ctx, ne, np.int64),
+               DeviceArray(self.ctx, ne, np.float64))
+        skipped = DeviceArray(self.ctx, 1, np.int64)
+        skipped.zero()
+        self.ctx.call("fmk_trend_scanning_dev", y.p, c_i64(y.n), event_idx.p, c_i64(ne), c_i64(min_len), c_i64(max_len),
+                      c_i64(step), out[0].p, out[1].p, out[2].p, out[3].p, skipped.p)
+        return out + (skipped,)
+
     def label_concurrency(self, event_idx: DeviceArray, touch_idx: DeviceArray) -> DeviceArray:
         """The concurrency column of average_uniqueness (label/weights.py:31-38): int16 per tick."""
         if touch_idx.n != event_idx.n:

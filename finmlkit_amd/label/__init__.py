@@ -1,7 +1,8 @@
 """Labels and sample weights on the raw tick tape, computed on the MI355X (drop-in for finmlkit/label)."""
 from .kit import SampleWeights, TBMLabel
 from .tbm import triple_barrier
+from .trend_scanning import trend_scanning
 from .weights import average_uniqueness, class_balance_weights, return_attribution, time_decay
 
-__all__ = ["triple_barrier", "average_uniqueness", "return_attribution", "time_decay", "class_balance_weights", "TBMLabel",
-           "SampleWeights"]
+__all__ = ["triple_barrier", "trend_scanning", "average_uniqueness", "return_attribution", "time_decay", "class_balance_weights",
+           "TBMLabel", "SampleWeights"]

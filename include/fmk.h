@@ -692,6 +692,27 @@ int fmk_triple_barrier(fmk_ctx *ctx, const int64_t *ts, const double *close_, in
                        const double *targets, const int8_t *side, int64_t n_events, double bottom_mult, double top_mult,
                        double vertical_barrier_sec, double min_close_time_sec, double min_ret, int8_t *labels, int64_t *touch_idx,
                        double *ret, double *max_rb_ratio, int64_t *n_skipped);
+/* trend_scanning (Lopez de Prado, Machine Learning for Asset Managers, ch. 5; the reference's label/trend_scanning.py is an empty
+ * placeholder, so the definition is this project's: DESIGN.md "trend scanning") on any float64 series y of n elements.  From an event
+ * t0, span L covers y[t0 .. t0+L-1] for L = min_len, min_len + step, ... <= max_len.  With d_j = y[t0+j] - y[t0], S1 = sum d_j,
+ * Sx = sum j*d_j, S2 = sum d_j^2: Sxx = L(L^2-1)/12, Sxy = Sx - (L-1)/2*S1, Syy = S2 - S1^2/L, u = 1 - Sxy^2/(Sxx*Syy) and
+ * t(L) = Sxy / sqrt(Sxx*Syy) * sqrt((L-2)/u), the t-value of the slope of the least-squares line through the span.  In this order:
+ * a NaN in the span (or an infinity: the sums become NaN) -> t(L) is NaN and the span is never chosen; S2 == 0 (a constant span) ->
+ * 0.0; u <= 2^-26 (an exact fit up to rounding) -> copysign(inf, Sxy).  Per event the span of largest |t| among the non-NaN ones,
+ * the smallest L among equals (several +-inf included): label = sign of its t (-1, 0, 1), t_value = its t, touch_idx = t0 + L - 1,
+ * ret = y[touch_idx] / y[t0] - 1.  ret, the special t-values and the count are exact; a finite t-value is a re-associated float64
+ * sum (64-tick blocks plus a carry; the measured tolerance is in DESIGN.md).  Events may come in any order, duplicates included.
+ * An event whose longest span does not fit (t0 + max_len > n) or all of whose spans are NaN gets label 0, NaN t-value and return
+ * and its own event_idx as touch index; *d_n_skipped (device int64, may be NULL; the caller zeroes it) counts them, as
+ * fmk_triple_barrier_dev counts its window-less events.  FMK_E_ARG: min_len < 3, max_len < min_len, step < 1, an event index outside
+ * [0, n).  n_events == 0 is a valid empty call.  One wave per event reads 8 B x max_len; the call waits once, for the index check.
+ * Host flavour: *n_skipped (host int64, may be NULL too) receives the count. */
+int fmk_trend_scanning_dev(fmk_ctx *ctx, const double *d_y, int64_t n, const int64_t *d_event_idx, int64_t n_events,
+                           int64_t min_len, int64_t max_len, int64_t step, int8_t *d_labels, double *d_t_value,
+                           int64_t *d_touch_idx, double *d_ret, int64_t *d_n_skipped);
+int fmk_trend_scanning(fmk_ctx *ctx, const double *y, int64_t n, const int64_t *event_idx, int64_t n_events, int64_t min_len,
+                       int64_t max_len, int64_t step, int8_t *labels, double *t_value, int64_t *touch_idx, double *ret,
+                       int64_t *n_skipped);
 /* The concurrency column of average_uniqueness (weights.py:31-38): how many events [event_idx, touch_idx] cover each tick, int16
  * with the reference's wrap-around.  n_events == 0: a zero column.  FMK_E_ARG: an event outside 0 <= event_idx <= touch_idx < n
  * (the reference slices silently into something else there). */
