@@ -302,6 +302,21 @@ static inline int fmk_rule_apen(fmk_ctx *ctx, int64_t window, int64_t m, double 
     return FMK_OK;
 }
 
+// the causal FIR filter (fmk_fir.hip): the weights are a host array in both flavours, so both can look at them; the geometry is
+// here for fmk_fir_geometry and the kernel alike
+#define FMK_FIR_MAX_WIDTH 8192
+#define FMK_FIR_TILE 512                   // outputs per workgroup
+#define FMK_FIR_TAPS 512                   // taps per staging pass
+static inline int fmk_rule_fir(fmk_ctx *ctx, const double *w, int64_t width, const double *x, const double *out)
+{
+    FMK_TRY(fmk_rule_least(ctx, width, 1, "fir: at least one weight is needed."));
+    if (width > FMK_FIR_MAX_WIDTH) return fmk_set_error(ctx, FMK_E_ARG, "fir: at most 8192 weights.");
+    for (int64_t k = 0; k < width; ++k)
+        if (!(w[k] - w[k] == 0.0)) return fmk_set_error(ctx, FMK_E_ARG, "fir: the weights must be finite.");
+    if (out == x) return fmk_set_error(ctx, FMK_E_ARG, "fir: the output must not be the input.");
+    return FMK_OK;
+}
+
 // One excursion of a call onto the context's auxiliary stream (fmk_api.hip), the only way there.  Rules:
 //  - one fork per context at a time: fork() while another FmkSide of the context is open is an error;
 //  - the context scratch belongs to the context's stream: fmk_scratch inside run() is an error;

@@ -887,4 +887,13 @@ int fmk_orb_break(fmk_ctx *ctx, const int64_t *ts, const double *high, const dou
     return down(ctx, orb_short, (const uint8_t *)d_sh, n);
 }
 
+// the causal FIR filter (fmk_fir.hip): w stays a host array, the _dev entry uploads it
+int fmk_fir(fmk_ctx *ctx, const double *x, int64_t n, const double *w, int64_t width, double *out)
+{
+    FMK_TRY(fmk_rule_fir(ctx, w, width, x, out));
+    FMK_TRY(fmk_series_check(ctx, "fir", n));
+    if (n == 0) return FMK_OK;
+    return series_host(ctx, FMK_OK, x, n, out, [=](const double *d_x, double *d_o) { return fmk_fir_dev(ctx, d_x, n, w, width, d_o); });
+}
+
 }  // extern "C"

@@ -15,7 +15,7 @@ import numpy as np
 from . import _ffi
 from ._ffi import (DIRECTIONAL_FIELDS, FOOTPRINT_BAR_FIELDS, FOOTPRINT_FLAT_FIELDS, Context, DeviceArray,
                    DirectionalOut, FootprintOut, c_f64, c_i64, c_vp)
-from .feature.core import clock
+from .feature.core import clock, fracdiff
 from .feature.series_ops import OPS, resident
 
 DENSE_GAP_MOD = 100_000_000          # mean gap 50 ms, no empty 1-min bar
@@ -490,6 +490,17 @@ class DeviceTrades:
         """approximate_entropy (feature/core/entropy.py; reference transforms.py:1400-1457) of a resident float64 series; ValueError
         for the arguments that function refuses."""
         return resident(self.ctx, OPS["approximate_entropy"], (y,), window, m, tolerance)
+
+    # the causal FIR filter and fractional differentiation (csrc/fmk_fir.hip); the weights are host numbers
+    def fir(self, y: DeviceArray, weights) -> DeviceArray:
+        """fir (feature/core/fracdiff.py) of a resident float64 series: out[t] = sum_k weights[k] * y[t-k], one fused multiply-add
+        per tap, oldest first; ValueError for the weights that function refuses."""
+        return fracdiff.resident(self.ctx, y, weights)
+
+    def frac_diff(self, y: DeviceArray, d: float, threshold: float = 1e-5) -> DeviceArray:
+        """frac_diff_ffd (feature/core/fracdiff.py) of a resident float64 series: the fixed-width window fractional
+        differentiation of order d; ValueError for a d or a threshold that frac_diff_weights refuses."""
+        return fracdiff.resident(self.ctx, y, fracdiff.frac_diff_weights(d, threshold))
 
     # the bar clock, run lengths and the opening range (csrc/fmk_clock.hip).  ts=None: the tape's own stamps; a DeviceArray of bar
     # stamps (int64 nanoseconds, e.g. from gather_ts) may be given instead

@@ -11,7 +11,8 @@ approximate entropy `ApproximateEntropy` (reference transforms.py:1400-1457; the
 `antropy.app_entropy`, here the kernel of csrc/fmk_entropy.hip, which needs no `antropy`), and the bar clock, run lengths and the
 opening range `BarDuration`, `BarDurationEWMA`, `BarRate`, `DirRunLen` and `ORBBreak` (reference transforms.py:1511-1548, :1460-1508,
 :1210-1270, :1605-1664, :1122-1207; there pandas' diff, ewm and time-window rolling, a sequential loop and a Python loop per day, here
-the kernels of csrc/fmk_clock.hip).
+the kernels of csrc/fmk_clock.hip), and the fixed-width window fractional differentiation `FracDiff` (no counterpart in the reference;
+core/fracdiff.py, the kernel of csrc/fmk_fir.hip).
 
 Counterparts of finmlkit/feature/transforms.py:89-117 (ReturnT), :308-332 (EWMST) and the
 pipeline part of finmlkit/feature/kit.py:Compose (:630-720), enough to run the QuickStart flow
@@ -29,7 +30,7 @@ import pandas as pd
 
 from .. import _ffi
 from .._ffi import DeviceArray, c_f64, c_i64
-from .core import clock
+from .core import clock, fracdiff
 from .core.structural_break.cusum import cusum_test_rolling
 from .core.correlation import rolling_price_volume_correlation
 from .core.momentum import LENGTH_MESSAGE, stoch_k
@@ -259,6 +260,23 @@ class ApproximateEntropy(_SeriesOp):
 
     def _params(self):
         return (self.window, self.m, self.tolerance)
+
+
+class FracDiff(SISOTransform):
+    """Fixed-width window fractional differentiation of order `d` (core/fracdiff.py; the reference has no counterpart).  The weights
+    are computed once, here: a `d` or a `threshold` that `frac_diff_weights` refuses raises ValueError at construction."""
+
+    def __init__(self, d: float, threshold: float = 1e-5, input_col: str = "close"):
+        super().__init__(input_col, f"ffd{d}")
+        self.d = d
+        self.threshold = threshold
+        self.weights = fracdiff.frac_diff_weights(d, threshold)
+
+    def _hip(self, x):
+        return self._prepare_output_nb(x.index, fracdiff.fir(self._prepare_input_nb(x), self.weights))
+
+    def _dev(self, ts, y):
+        return fracdiff.resident(ts.ctx, y, self.weights)
 
 
 class EWMA(_SeriesOp):

@@ -730,6 +730,24 @@ int fmk_label_weights_dev(fmk_ctx *ctx, const double *d_close, const int16_t *d_
 int fmk_label_weights(fmk_ctx *ctx, const double *close_, const int16_t *concurrency, int64_t n, const int64_t *event_idx,
                       const int64_t *touch_idx, int64_t n_events, double *avg_uniqueness, double *return_attribution);
 
+/* ---- causal FIR filter on a float64 series of n elements -> float64 array of n elements (csrc/fmk_fir.hip), and with the weights
+ * of feature/core/fracdiff.py the fixed-width window fractional differentiation "FFD" (Lopez de Prado, Advances in Financial
+ * Machine Learning, ch. 5; the reference has no such function: the definition is this project's).
+ * w[0 .. width-1] is a HOST array in both flavours (at most 64 KiB; the call checks it and copies it to the device in the stream's
+ * order); w[k] multiplies x[t-k].  With x~[i] = x[i] where x[i] is finite and NaN elsewhere:
+ *   out[t] = NaN for t < width - 1;
+ *   out[t] = acc after  acc = +0.0;  for k = width-1, width-2, .. 0: acc = fma(w[k], x~[t-k], acc)
+ * -- one correctly rounded fused multiply-add per tap, oldest tap first, one chain per output.  So a NaN or an infinity anywhere in
+ * x[t-width+1 .. t] makes out[t] NaN, n < width gives NaN everywhere, and the bits depend on nothing but x and w: not on the tile, on
+ * the taps per staging pass (fmk_fir_geometry) or on the pointers' alignment beyond 8 bytes.  n == 0 succeeds and touches nothing.
+ * FMK_E_ARG, checked in this order before a device is touched and before x or out is looked at: width < 1, width > 8192, a weight
+ * that is not finite, out == x; then n >= 2^31. */
+int fmk_fir_dev(fmk_ctx *ctx, const double *d_x, int64_t n, const double *w, int64_t width, double *d_out);
+int fmk_fir(fmk_ctx *ctx, const double *x, int64_t n, const double *w, int64_t width, double *out);
+/* The kernel's geometry, for callers that place work at its seams: out2[0] outputs per workgroup, [1] taps per staging pass.  Needs
+ * no context and no device. */
+int fmk_fir_geometry(int64_t *out2);
+
 /* ---- TradesData(preprocess=True) loops: finmlkit/bar/utils.py ("next" rank 4) ------------ */
 /* merge_split_trades (bar/utils.py:263-329): trades with the head's timestamp, maker flag and price (|dp| < 1e-8)
  * are merged, amounts summed in float32 in trade order; side = -1 if is_buyer_maker else 1 (is_buyer_maker may be
