@@ -84,6 +84,11 @@ struct fmk_mail {
         long long skipped;                 // k_trend: events whose longest span does not fit, or all of whose spans are NaN
         long long bad;                     // k_trend: event indices outside the series (the call fails)
     } trend;
+    struct Sadf {                          // fmk_sadf.hip
+        unsigned long long work;           // k_sadf: next end point of the persistent grid
+        long long skipped;                 // k_sadf: end points without a usable window
+        long long bad;                     // k_sadf: end-point indices outside the series (the call fails)
+    } sadf;
     struct Brk {                           // fmk_break.hip
         int nonpos;                        // k_brk_log: an element <= 0
         unsigned long long pairs, skipped; // k_brk_pairs: (t, n) pairs walked, pairs the den <= 1e-16 test dropped
@@ -286,6 +291,22 @@ static inline int fmk_rule_trend(fmk_ctx *ctx, int64_t min_len, int64_t max_len,
     FMK_TRY(fmk_rule_least(ctx, min_len, 3, "trend_scanning: min_len must be at least 3."));
     if (max_len < min_len) return fmk_set_error(ctx, FMK_E_ARG, "trend_scanning: max_len must not be less than min_len.");
     return fmk_rule_least(ctx, step, 1, "trend_scanning: step must be at least 1.");
+}
+// the ADF / SADF statistic (fmk_sadf.hip): k = lags + 2 (+ 1 with a time trend) regressors need k + 1 rows for one degree of freedom
+#define FMK_ADF_MAX_LAGS 4
+static inline int fmk_rule_sadf(fmk_ctx *ctx, int64_t min_len, int64_t max_len, int64_t step, int64_t lags, int trend, const void *y,
+                                const void *stat, const void *start)
+{
+    if (lags < 0 || lags > FMK_ADF_MAX_LAGS) return fmk_set_error(ctx, FMK_E_ARG, "sadf: lags must be between 0 and 4.");
+    if (trend != 0 && trend != 1) return fmk_set_error(ctx, FMK_E_ARG, "sadf: trend must be \"c\" (0) or \"ct\" (1).");
+    const int64_t k = lags + 2 + trend;
+    if (min_len < k + 1)
+        return fmk_set_error(ctx, FMK_E_ARG, "sadf: min_len must be at least %lld (one more than the %lld regressors).", (long long)(k + 1),
+                             (long long)k);
+    if (max_len < min_len) return fmk_set_error(ctx, FMK_E_ARG, "sadf: max_len must not be less than min_len.");
+    FMK_TRY(fmk_rule_least(ctx, step, 1, "sadf: step must be at least 1."));
+    if (y && (stat == y || start == y)) return fmk_set_error(ctx, FMK_E_ARG, "sadf: an output must not be the input.");
+    return FMK_OK;
 }
 // the approximate entropy (fmk_entropy.hip): the order-(m + 1) embedding needs one vector; one tile's span and the table of
 // logarithms have to fit in LDS; the kernels are instantiated per m

@@ -896,4 +896,29 @@ int fmk_fir(fmk_ctx *ctx, const double *x, int64_t n, const double *w, int64_t w
     return series_host(ctx, FMK_OK, x, n, out, [=](const double *d_x, double *d_o) { return fmk_fir_dev(ctx, d_x, n, w, width, d_o); });
 }
 
+// the ADF / SADF statistic (fmk_sadf.hip); end_idx == NULL: end point e is element e
+int fmk_sadf(fmk_ctx *ctx, const double *y, int64_t n, const int64_t *end_idx, int64_t n_end, int64_t min_len, int64_t max_len,
+             int64_t step, int64_t lags, int trend, double *stat, int64_t *start, int64_t *n_skipped)
+{
+    FMK_TRY(fmk_rule_sadf(ctx, min_len, max_len, step, lags, trend, y, stat, start));
+    if (n_end < 0 || n < 0) return fmk_set_error(ctx, FMK_E_ARG, "negative dimensions are not allowed");
+    if (n_skipped) *n_skipped = 0;
+    if (n_end == 0) return FMK_OK;
+    if (n == 0) return fmk_set_error(ctx, FMK_E_ARG, "sadf: end points outside the (empty) series");
+    DevBag bag(ctx);
+    double *d_y, *d_stat;
+    int64_t *d_ev = nullptr, *d_start, *d_skip;
+    FMK_TRY(bag.up(y, n, &d_y));
+    if (end_idx) FMK_TRY(bag.up(end_idx, n_end, &d_ev));
+    FMK_TRY(bag.out(n_end, &d_stat));
+    FMK_TRY(bag.out(n_end, &d_start));
+    FMK_TRY(bag.out(1, &d_skip));
+    FMK_TRY(fmk_memset(ctx, d_skip, 0, sizeof(int64_t)));
+    FMK_TRY(fmk_sadf_dev(ctx, d_y, n, d_ev, n_end, min_len, max_len, step, lags, trend, d_stat, d_start, d_skip));
+    FMK_TRY(down(ctx, stat, d_stat, n_end));
+    FMK_TRY(down(ctx, start, d_start, n_end));
+    FMK_TRY(down(ctx, n_skipped, d_skip, 1));
+    return FMK_OK;
+}
+
 }  // extern "C"

@@ -16,6 +16,7 @@ from . import _ffi
 from ._ffi import (DIRECTIONAL_FIELDS, FOOTPRINT_BAR_FIELDS, FOOTPRINT_FLAT_FIELDS, Context, DeviceArray,
                    DirectionalOut, FootprintOut, c_f64, c_i64, c_vp)
 from .feature.core import clock, fracdiff
+from .feature.core.structural_break import adf
 from .feature.series_ops import OPS, resident
 
 DENSE_GAP_MOD = 100_000_000          # mean gap 50 ms, no empty 1-min bar
@@ -571,6 +572,20 @@ class DeviceTrades:
             self.ctx.call("fmk_cusum_test_rolling_dev", x.p, c_i64(x.n), c_i64(max(0, int(window_size))), c_i64(int(warmup_period)),
                           *[o.p for o in out])
         return out
+
+    def sadf(self, min_len: int, max_len: Optional[int] = None, lags: int = 1, trend: str = "c", step: int = 1,
+             end_idx: Optional[DeviceArray] = None, series: Optional[DeviceArray] = None):
+        """sadf (feature/core/structural_break/adf.py) on a resident float64 series (default: the price
+        column; pass log prices for the book's test) -> (stat float64, start int64, n_skipped): the supremum ADF statistic of every
+        end point, the first row of the window that attains it (-1 without one) and a device int64 counting the end points without
+        a usable window.  end_idx: an int64 DeviceArray of end points, as `cusum_filter` returns its events; None: every element.
+        max_len None: all history.  ValueError for the arguments that function refuses."""
+        return adf.resident(self.ctx, self.price if series is None else series, end_idx, min_len, max_len, lags, trend, step)
+
+    def adf_rolling(self, window: int, lags: int = 1, trend: str = "c", series: Optional[DeviceArray] = None) -> DeviceArray:
+        """adf_rolling (feature/core/structural_break/adf.py) on a resident float64 series (default: the price column): the ADF
+        statistic of the `window` rows that end at every element."""
+        return adf.resident(self.ctx, self.price if series is None else series, None, window, window, lags, trend, 1)[0]
 
     # ------------------------------------------------------------------ labels and sample weights
     def triple_barrier(self, event_idx: DeviceArray, targets: DeviceArray, horizontal_barriers, vertical_barrier: float,

@@ -18,6 +18,7 @@ from numpy.typing import NDArray
 
 from ... import _ffi
 from ..._ffi import DeviceArray, c_i64, c_vp, ptr
+from .structural_break import adf
 
 FIR_MAX_WIDTH = 8192                 # csrc/fmk_common.h: FMK_FIR_MAX_WIDTH
 D_MESSAGE = "frac_diff: d must be finite and not negative."
@@ -107,3 +108,44 @@ def resident(ctx, y: DeviceArray, weights) -> DeviceArray:
     out = DeviceArray(ctx, y.n, np.float64)
     _ffi.check(entries()[1](ctx.handle, y.p, y.n, ptr(w), w.size, out.p), ctx.handle)
     return out
+
+
+ADF_CRIT_95 = -2.8623                # the 95 % critical value of the ADF test with a constant that the book's Table 5.1 quotes
+
+
+def ffd_adf_stats(x, ds, threshold: float = 1e-5, lags: int = 1) -> NDArray[np.float64]:
+    """The ADF statistic (constant, `lags` lagged differences) of frac_diff_ffd(x, d, threshold) for every d of `ds`, taken over the
+    series from its first full window on (the leading NaN are left out; a NaN later on makes the statistic NaN, and so does a tail
+    too short for one degree of freedom).  `x` goes up once; per d one fmk_fir_dev and one fmk_sadf_dev with a single end point run
+    on the device and eight bytes come back."""
+    ds = [float(d) for d in ds]
+    weights = [frac_diff_weights(d, threshold) for d in ds]
+    x = np.ascontiguousarray(x, dtype=np.float64)
+    lags = adf.check_arguments(len(x), None, adf.MAX_LAGS + 3, None, lags, "c", 1)[2]      # (refuses lags outside 0..4)
+    k = adf.regressors(lags, "c")
+    stats = np.full(len(ds), np.nan)
+    tails = [len(x) - (w.size - 1) for w in weights]                       # elements from the first full window on
+    if not any(tail - lags - 1 >= k + 1 for tail in tails):
+        return stats
+    ctx = _ffi.default_context()
+    d_x = DeviceArray.from_host(ctx, x)
+    d_last = DeviceArray.from_host(ctx, np.array([max(tail - 1, 0) for tail in tails], np.int64))
+    for i, (w, tail) in enumerate(zip(weights, tails)):
+        rows = tail - lags - 1
+        if rows < k + 1:
+            continue
+        y = resident(ctx, d_x, w).view(w.size - 1)
+        stats[i] = adf.resident(ctx, y, d_last.view(i, 1), rows, rows, lags, "c", 1)[0].to_host()[0]
+    return stats
+
+
+def min_ffd_d(x, ds=np.linspace(0, 1, 11), threshold: float = 1e-5, lags: int = 1, crit: float = ADF_CRIT_95):
+    """-> (d, stats): the first `d` of `ds` whose FFD series passes the ADF test, i.e. has a statistic below `crit`, or None when
+    none has, and the statistic of every d (ffd_adf_stats; NaN never passes).  This is the book's search for the smallest order
+    that makes a series stationary (ch. 5, Table 5.1).  `crit` defaults to -2.8623, the 95 % critical value that table quotes for a
+    test with a constant; it depends on the sample size and on the deterministic terms (MacKinnon's tables), so pass your own for
+    another level or a short series: this library computes no p-values."""
+    ds = np.asarray(ds, dtype=np.float64).reshape(-1)
+    stats = ffd_adf_stats(x, ds, threshold, lags)
+    below = np.flatnonzero(stats < crit)
+    return (float(ds[below[0]]) if below.size else None), stats

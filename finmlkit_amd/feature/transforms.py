@@ -12,7 +12,8 @@ approximate entropy `ApproximateEntropy` (reference transforms.py:1400-1457; the
 opening range `BarDuration`, `BarDurationEWMA`, `BarRate`, `DirRunLen` and `ORBBreak` (reference transforms.py:1511-1548, :1460-1508,
 :1210-1270, :1605-1664, :1122-1207; there pandas' diff, ewm and time-window rolling, a sequential loop and a Python loop per day, here
 the kernels of csrc/fmk_clock.hip), and the fixed-width window fractional differentiation `FracDiff` (no counterpart in the reference;
-core/fracdiff.py, the kernel of csrc/fmk_fir.hip).
+core/fracdiff.py, the kernel of csrc/fmk_fir.hip) and the supremum ADF statistic `SADF` (no counterpart either;
+core/structural_break/adf.py, the kernel of csrc/fmk_sadf.hip).
 
 Counterparts of finmlkit/feature/transforms.py:89-117 (ReturnT), :308-332 (EWMST) and the
 pipeline part of finmlkit/feature/kit.py:Compose (:630-720), enough to run the QuickStart flow
@@ -31,6 +32,7 @@ import pandas as pd
 from .. import _ffi
 from .._ffi import DeviceArray, c_f64, c_i64
 from .core import clock, fracdiff
+from .core.structural_break import adf
 from .core.structural_break.cusum import cusum_test_rolling
 from .core.correlation import rolling_price_volume_correlation
 from .core.momentum import LENGTH_MESSAGE, stoch_k
@@ -277,6 +279,24 @@ class FracDiff(SISOTransform):
 
     def _dev(self, ts, y):
         return fracdiff.resident(ts.ctx, y, self.weights)
+
+
+class SADF(SISOTransform):
+    """Supremum ADF statistic of every element (core/structural_break/adf.py; the reference has no counterpart): the largest ADF
+    statistic over the backward windows of `min_len` .. `max_len` rows (None: all history).  The output is the statistic; the
+    arguments that `sadf` refuses raise ValueError at construction."""
+
+    def __init__(self, min_len: int, max_len=None, lags: int = 1, trend: str = "c", step: int = 1, input_col: str = "close"):
+        super().__init__(input_col, f"sadf_{min_len}_{'all' if max_len is None else max_len}")
+        adf.check_arguments(0, None, min_len, max_len, lags, trend, step)
+        self.min_len, self.max_len, self.lags, self.trend, self.step = min_len, max_len, lags, trend, step
+
+    def _hip(self, x):
+        stat, _ = adf.sadf(self._prepare_input_nb(x), self.min_len, self.max_len, self.lags, self.trend, self.step)
+        return self._prepare_output_nb(x.index, stat)
+
+    def _dev(self, ts, y):
+        return adf.resident(ts.ctx, y, None, self.min_len, self.max_len, self.lags, self.trend, self.step)[0]
 
 
 class EWMA(_SeriesOp):

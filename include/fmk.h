@@ -748,6 +748,38 @@ int fmk_fir(fmk_ctx *ctx, const double *x, int64_t n, const double *w, int64_t w
  * no context and no device. */
 int fmk_fir_geometry(int64_t *out2);
 
+/* ---- augmented Dickey-Fuller statistic of backward windows and its supremum, SADF (csrc/fmk_sadf.hip; Lopez de Prado, Advances in
+ * Financial Machine Learning, ch. 17; the reference has no such function: the definition is this project's).
+ * y: any float64 series of n elements, taken as given (pass log prices); an element that is not finite counts as NaN.  L = lags in
+ * 0..4, trend FMK_ADF_C or FMK_ADF_CT.  With dy_i = y_i - y_{i-1}, row i (i >= L + 1) of END POINT t has the target dy_i and the
+ * k = L + 2 (+ 1 for CT) regressors, in the order of the factor,
+ *   1, (i - t if CT), dy_{i-1}, .., dy_{i-L}, y_{i-1} - y_t
+ * (centring the level on y_t and the trend on t changes neither the coefficient of the level nor its t-statistic: there is an
+ * intercept; it keeps float64 moments usable at price levels of 10^5 and is part of the definition).  A window is the m rows
+ * i in [s, t], s = t - m + 1 >= L + 1; it reads y[s-L-1 .. t].  A = the (k+1) x (k+1) matrix of the window's moments (sums of
+ * products of the columns above, the target as the last row and column; the moments of 1 and i - t alone are m, -m(m-1)/2 and
+ * (m-1)m(2m-1)/6).  For j = 0 .. k-1: d_j = A[j][j]; the window is DEGENERATE when !(d_j > 2^-26 * G_jj), G_jj the moment A[j][j]
+ * started as; then for i > j: l = A[i][j] * (1 / d_j), A[i][r] -= l * A[r][j] for r = j+1 .. i.  This leaves SSR = A[k][k]; with
+ * z = A[k][k-1] and d = A[k-1][k-1]:
+ *   ADF(s, t) = z / sqrt(d * SSR / (m - k));      SSR / (sum of dy_i^2) <= 2^-26 (an exact fit) -> copysign(inf, z).
+ * A degenerate window (a constant stretch, an exact ramp under CT or with lags, collinear lags) and a window that holds a NaN (its
+ * sums are NaN and fail the pivot test) are never chosen.  stat[e] = the largest ADF(s, t) over m = min_len, min_len + step, ..
+ * <= max_len with s >= L + 1, start[e] = the s of that window, the shortest window among equal statistics (several +inf included);
+ * an end point without a usable window gets NaN and -1, and *d_n_skipped (device int64, may be NULL; the caller zeroes it) counts
+ * them.  min_len == max_len is the rolling ADF; one end point n-1 with min_len = max_len = n-L-1 the ADF of the whole series.
+ * d_end_idx: n_end end points in any order, duplicates included; NULL: end point e is element e (n_end = n: every t).  The special
+ * values and the count are exact; a finite statistic is float64 arithmetic on re-associated sums (64-row blocks plus a carry; the
+ * measured tolerance is in DESIGN.md).  FMK_E_ARG, the rules before a device is touched, in this order: lags outside 0..4, an
+ * unknown trend, min_len < k + 1, max_len < min_len, step < 1, d_stat or d_start == d_y; then an end point outside [0, n).
+ * n_end == 0 is a valid empty call.  One wave per end point; the call waits once, for the index check.  Host flavour: *n_skipped
+ * (host int64, may be NULL too) receives the count, end_idx may be NULL as above. */
+#define FMK_ADF_C 0
+#define FMK_ADF_CT 1
+int fmk_sadf_dev(fmk_ctx *ctx, const double *d_y, int64_t n, const int64_t *d_end_idx, int64_t n_end, int64_t min_len,
+                 int64_t max_len, int64_t step, int64_t lags, int trend, double *d_stat, int64_t *d_start, int64_t *d_n_skipped);
+int fmk_sadf(fmk_ctx *ctx, const double *y, int64_t n, const int64_t *end_idx, int64_t n_end, int64_t min_len, int64_t max_len,
+             int64_t step, int64_t lags, int trend, double *stat, int64_t *start, int64_t *n_skipped);
+
 /* ---- TradesData(preprocess=True) loops: finmlkit/bar/utils.py ("next" rank 4) ------------ */
 /* merge_split_trades (bar/utils.py:263-329): trades with the head's timestamp, maker flag and price (|dp| < 1e-8)
  * are merged, amounts summed in float32 in trade order; side = -1 if is_buyer_maker else 1 (is_buyer_maker may be
