@@ -34,10 +34,10 @@ struct fmk_mail {
 
     // ---- per-call fields
     uint8_t staging[1024];                 // host copy: fmk_read_back's landing area
-    struct Vol {                           // fmk_volume.hip / fmk_volume_exact.h: the level tables
-        struct Levels { int status; uint32_t root; int root_tie; } lv;                          // k_vol_level0 / k_vol_level_up4
-        struct Table { uint32_t root; uint32_t maxlen; int status; unsigned long long nfrag; } tb;      // k_vg_* (vg_run)
-        struct Closes { uint32_t count; int status; } closes;                                   // host copy: vg_run's last batch
+    struct Vol {                           // fmk_volume.hip / fmk_volume_exact.h / fmk_voltree.h: the level tables
+        struct Levels { int status; uint32_t root; int root_tie; } lv;                          // k_vol_level0 / k_vx_level0 / k_vol_tree_up
+        struct Table { uint32_t root; uint32_t maxlen; int status; unsigned long long nfrag; } tb;      // k_vg_* / k_vol_tree_up (vol_global_tables)
+        struct Closes { uint32_t count; int status; } closes;                                   // host copy: vol_tree_closes' batch
         struct Chase { int64_t res; int prefix_status; } chase;                                 // host copy: vol_chase's batch
         int64_t chase_res;                 // k_vc_chase: closes (or the total, total_only)
         int mismatch;                      // k_vol_verify

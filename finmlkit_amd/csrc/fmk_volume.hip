@@ -10,14 +10,17 @@
 //            prefix sums of the block + S ticks of look-ahead in LDS; nxt(j) for EVERY tick j of the
 //            block by bisection in LDS; pointer doubling in LDS turns nxt into
 //            E0[j] = first chain node >= end of the block, C0[j] = chain nodes inside the block.
-//   level k  (k_vol_level_up): a block of S*2^k ticks is two blocks of level k-1.  The chain enters any
+//   level k  (fmk_voltree.h, k_vol_tree_up): a block of S*16^k ticks is sixteen blocks of level k-1.  The chain enters any
 //            block within its first S ticks (S >= longest bar), so a table over those S entry ticks is
-//            enough:  E^k[i] = E^{k-1}_right[ E^{k-1}_left[i] ],  C^k = C_left + C_right.   O(N/2^k) work.
-//   top-down (k_vol_descend): the root block's entry is the first close c_1; every block hands its entry
-//            to the left child and E_left[entry] (+ the close count so far) to the right child.
+//            enough:  E^k[i] = E^{k-1}_16th[ .. E^{k-1}_2nd[ E^{k-1}_1st[i] ] ],  C^k = the sum of the C^{k-1} on the way.
+//            O(N/16^k) work.
+//   top-down (fmk_voltree.h, k_vol_tree_down): the root block's entry is the first close c_1; every block hands its entry
+//            to its first child and, to each further child, the exit of the child before it (+ the close count so far).
 //   emit     (k_vol_emit): every level-0 block walks its <= S/bar-length chain nodes and writes them to
 //            their final output slots.
-// Total work O(N) + 2*log2(N/S) tiny launches; no sequential pass over the stream.
+// Total work O(N) + 2*log16(N/S) tiny launches; no sequential pass over the stream.  The tree -- its plan, its two kernels and
+// its host driver -- is the same for the three table tiers (these LDS tables, the exact-sum classes of fmk_volume_exact.h, the
+// global tables further down) and lives in fmk_voltree.h; a tier brings its level 0, its status checks and its emit.
 //
 // Arithmetic: bar sums are differences of block-local float64 prefix sums (not the reference's
 // sequential sum from the bar start).  Every decision gets a class (0 certain, 1 within (1e-11 + 2^-52 * length) * thr of
@@ -31,22 +34,16 @@
 #include <stdlib.h>
 
 #include "fmk_common.h"
+#include "fmk_voltree.h"              // VOL_END, VOL_RADIX, the status word bits, vol_flag; the table tree
 #include "../../include/fmk_diag.h"
 
-#define VOL_END 0xFFFFFFFFu
 // threads per workgroup of k_vol_level0.  The workgroup's LDS (53.3 KB: three per CU) does not depend on it, so this sets
 // the waves per CU: 256 -> 12 waves, 14.6 ms per 1e9 ticks at 865-tick bars; 512 -> 24 waves, 11.8 ms; 1024 -> 32 waves
 // (two workgroups: the wave limit) but 19.6 ms -- barriers across 16 waves, and a thread's monotone walk covers 2 ticks
 #define VOL_THREADS 512
-#define VOL_RADIX 16                    // blocks composed per table level (LDS tier)
 
 int fmk_threshold_serial(fmk_ctx *ctx, int dollar, const double *d_price, const void *d_amount, int is_f64, int64_t n,
                          double thr, int64_t *d_close_idx, int64_t capacity, int64_t *n_idx, int64_t *n_unc);
-
-// status word bits
-#define VOL_ST_OVERFLOW 1   // a bar is longer than S ticks
-#define VOL_ST_BAD 2        // negative / NaN volume
-#define VOL_ST_INEXACT 4    // an amount that is not a multiple of 2^-20 below 2^20: sums are not exact in float64
 
 // A decision whose margin is EXACTLY zero (sum == threshold in this file's evaluation order) is certain only when every sum
 // involved is exact in float64 -- then the reference's sequential sum is the same number.  That holds for streams of
@@ -101,10 +98,6 @@ __device__ __forceinline__ int64_t vol_replay(const void *__restrict__ amount, i
 // (tools/fuzz_volume.py seed 5202 case 241, round 5).  Every margin that involves a local prefix therefore adds 2^-42 of it.
 __device__ __forceinline__ double vol_prefix_slack(double local_prefix) { return 2.2737367544323206e-13 * fabs(local_prefix); }
 
-__device__ __forceinline__ void vol_flag(int *status, int bit)     // one atomic per kernel, not per wave
-{
-    if (!(__atomic_load_n(status, __ATOMIC_RELAXED) & bit)) atomicOr(status, bit);
-}
 // ... and the THRESHOLD has to be such a multiple too: the decisions compare a prefix with (earlier prefix + thr), and with
 // thr = 2840.5000000000005 (one ulp above a multiple of 1/8; found by tools/fuzz_parity.py seed 778 case 121) that sum rounds
 // to the grid -- a bar whose amounts add up to 2840.5 looked like an exact tie and closed, where the reference's
@@ -360,123 +353,6 @@ __global__ __launch_bounds__(VOL_THREADS) void k_vol_level0(const void *__restri
     }
 }
 
-// tables of level k from level k-1: one thread per (block, entry).  The table span S = 1 << ls is a run-time value: the
-// LDS tiers use 2048 / 4096, the global tier (below) whatever power of two covers the longest bar.
-__global__ __launch_bounds__(256) void k_vol_level_up(int ls, const uint32_t *__restrict__ Ep, const uint32_t *__restrict__ Cp,
-                                                      int64_t nblk_prev, int64_t span_prev /* ticks per prev block */,
-                                                      uint32_t *__restrict__ Ek, uint32_t *__restrict__ Ck,
-                                                      int64_t nblk, int *__restrict__ status)
-{
-    const int64_t S = (int64_t)1 << ls;
-    const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (t >= nblk * S) return;
-    const int64_t b = t >> ls;
-    const int64_t i = t & (S - 1);
-    const int64_t left = 2 * b, right = 2 * b + 1;
-    uint32_t x = Ep[left * S + i];
-    uint32_t c = Cp[left * S + i];
-    if (x != VOL_END && right < nblk_prev) {
-        const int64_t i2 = (int64_t)x - right * span_prev;
-        if (i2 < 0 || i2 >= S) { atomicOr(status, VOL_ST_OVERFLOW); x = VOL_END; }
-        else {
-            c += Cp[right * S + i2];
-            x = Ep[right * S + i2];
-        }
-    }
-    Ek[t] = x;
-    Ck[t] = c;
-}
-
-// entries / output offsets of level k-1 from level k
-__global__ __launch_bounds__(256) void k_vol_descend(int ls, const uint32_t *__restrict__ ent_k, const int64_t *__restrict__ off_k,
-                                                     int64_t nblk_k, int64_t span_prev,
-                                                     const uint32_t *__restrict__ Ep, const uint32_t *__restrict__ Cp,
-                                                     int64_t nblk_prev, uint32_t *__restrict__ ent_p,
-                                                     int64_t *__restrict__ off_p)
-{
-    const int64_t S = (int64_t)1 << ls;
-    const int64_t b = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (b >= nblk_k) return;
-    const uint32_t e = ent_k[b];
-    const int64_t o = off_k[b];
-    const int64_t left = 2 * b, right = 2 * b + 1;
-    ent_p[left] = e;
-    off_p[left] = o;
-    if (right < nblk_prev) {
-        uint32_t x = VOL_END;
-        int64_t oo = o;
-        if (e != VOL_END) {
-            const int64_t i = (int64_t)e - left * span_prev;       // entry lies in the left child's first S ticks
-            if (i >= 0 && i < S) {
-                x = Ep[left * S + i];
-                oo = o + Cp[left * S + i];
-            } else {
-                x = e;                                              // (cannot happen when S >= longest bar)
-            }
-        }
-        ent_p[right] = x;
-        off_p[right] = oo;
-    }
-}
-
-// Radix-4 flavours (round 2): level q+1 composes FOUR blocks of level q.  Composing two at a time writes and re-reads a
-// table of N / 2^k entries at every one of the ~20 levels (8 B read + 8 B gathered + 8 B written per entry: 24 GB per 1e9
-// ticks, 4.2 of the indexer's 12.1 ms); four at a time writes N / 4^q entries with three dependent gathers each:
-// 13 GB, half the launches, and a third fewer tables to keep.  Measured at 1e9 ticks (cfg-3 threshold): radix 2 / 4 / 8 / 16 / 32 ->
-// 11.6 / 9.5 / 8.9 / 8.7 / 8.6 ms for the whole indexer; VOL_RADIX = 16 (the kernels take the radix as an argument).
-__global__ __launch_bounds__(256) void k_vol_level_up4(int ls, const uint32_t *__restrict__ Ep, const uint32_t *__restrict__ Cp,
-                                                       int64_t nblk_prev, int64_t span_prev, uint32_t *__restrict__ Ek,
-                                                       uint32_t *__restrict__ Ck, int64_t nblk, int *__restrict__ status,
-                                                       int radix)
-{
-    const int64_t S = (int64_t)1 << ls;
-    const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (t >= nblk * S) return;
-    const int64_t b = t >> ls;
-    const int64_t i = t & (S - 1);
-    const int64_t c0 = (int64_t)radix * b;
-    uint32_t x = Ep[c0 * S + i];
-    uint32_t c = Cp[c0 * S + i];
-    for (int j = 1; j < radix; ++j) {
-        const int64_t child = c0 + j;
-        if (x == VOL_END || child >= nblk_prev) break;
-        const int64_t i2 = (int64_t)x - child * span_prev;           // the chain enters the next child in its first S ticks
-        if (i2 < 0 || i2 >= S) { atomicOr(status, VOL_ST_OVERFLOW); x = VOL_END; break; }
-        c += Cp[child * S + i2];
-        x = Ep[child * S + i2];
-    }
-    Ek[t] = x;
-    Ck[t] = c;
-}
-
-__global__ __launch_bounds__(256) void k_vol_descend4(int ls, const uint32_t *__restrict__ ent_k, const int64_t *__restrict__ off_k,
-                                                      int64_t nblk_k, int64_t span_prev, const uint32_t *__restrict__ Ep,
-                                                      const uint32_t *__restrict__ Cp, int64_t nblk_prev,
-                                                      uint32_t *__restrict__ ent_p, int64_t *__restrict__ off_p, int radix)
-{
-    const int64_t S = (int64_t)1 << ls;
-    const int64_t b = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (b >= nblk_k) return;
-    uint32_t e = ent_k[b];
-    int64_t o = off_k[b];
-    const int64_t c0 = (int64_t)radix * b;
-    ent_p[c0] = e;
-    off_p[c0] = o;
-    for (int j = 1; j < radix; ++j) {
-        const int64_t child = c0 + j;
-        if (child >= nblk_prev) break;
-        if (e != VOL_END) {
-            const int64_t i = (int64_t)e - (child - 1) * span_prev;  // the entry lies in the previous child's first S ticks
-            if (i >= 0 && i < S) {
-                o += Cp[(child - 1) * S + i];
-                e = Ep[(child - 1) * S + i];
-            }                                                        // (else: cannot happen when S >= longest bar)
-        }
-        ent_p[child] = e;
-        off_p[child] = o;
-    }
-}
-
 __global__ __launch_bounds__(256) void k_vol_emit(int ls, const uint32_t *__restrict__ ent0, const int64_t *__restrict__ off0,
                                                   int64_t nblk0, const uint32_t *__restrict__ nxt,
                                                   int64_t *__restrict__ out, int64_t cap,
@@ -535,6 +411,30 @@ void fmk_volume_trim(fmk_ctx *ctx)
     ctx->idx_cache[0] = nullptr;
 }
 
+// A workspace of the exact-sum and global tiers, grown to `bytes`.  Returns 1 -- "use the next tier" -- when the device cannot
+// provide it: the chain walk needs no tables, and a full HBM is no reason to fail the call.
+static int vol_ensure(fmk_ctx *ctx, void **buf, size_t *have, size_t bytes)
+{
+    if (*have >= bytes) return FMK_OK;
+    if (*buf) FMK_HIP(ctx, hipFree(*buf));
+    *buf = nullptr; *have = 0;
+    if (hipMalloc(buf, bytes) != hipSuccess) {
+        (void)hipGetLastError();                                    // clear the sticky out-of-memory error
+        *buf = nullptr;
+        return 1;
+    }
+    *have = bytes;
+    return FMK_OK;
+}
+// the table tiers' output: c.count = closes + 1 (slot 0 is tick 0, logic.py:104) and room for as many in c.dbuf
+static int vol_ensure_out(fmk_ctx *ctx, VolCache &c, int64_t closes)
+{
+    c.count = closes + 1;
+    if (c.dbuf && c.cap < c.count) { FMK_HIP(ctx, hipFree(c.dbuf)); c.dbuf = nullptr; }
+    if (!c.dbuf) { FMK_HIP(ctx, hipMalloc((void **)&c.dbuf, (size_t)c.count * 8)); c.cap = c.count; }
+    return FMK_OK;
+}
+
 static int vol_certify(fmk_ctx *ctx, const void *a, int is_f64, int64_t n, double thr, VolCache &c);
 
 // what the ladder of the last fmk_volume_bar_indexer[_dev] call of this process did (tests; include/fmk_diag.h:
@@ -587,42 +487,20 @@ static int vol_run(fmk_ctx *ctx, const void *a, int64_t n, double thr, VolCache 
     constexpr int LS = 11;
     static_assert(S == (1 << LS), "table span");
     const int64_t nblk0 = fmk_ceil_div(n, S);
-    // levels: nblk[k] = ceil(nblk0 / R^k) until 1 (radix-R composition, k_vol_level_up4)
-    const int RAD = VOL_RADIX;
-    int64_t nblk[64], spanq[64];
-    int K = 0;
-    nblk[0] = nblk0;
-    spanq[0] = S;
-    while (nblk[K] > 1) { nblk[K + 1] = (nblk[K] + RAD - 1) / RAD; spanq[K + 1] = spanq[K] * RAD; ++K; }
-    // workspace layout (uint32 tables + per-level entry/offset arrays)
-    size_t tbl = 0;
-    for (int k = 0; k <= K; ++k) tbl += (size_t)nblk[k] * S;
-    size_t ents = 0;
-    for (int k = 0; k <= K; ++k) ents += (size_t)nblk[k];
-    const size_t bytes = ((size_t)nblk0 * S + 2 * tbl) * 4 + ents * (4 + 8) + 256 + (size_t)nblk0 * S;
+    VolTree t = vol_tree_plan(nblk0, S, S, VOL_RADIX);
+    // workspace: the chain links of every tick, the tree, a fragile byte per tick
+    const size_t bytes = (size_t)nblk0 * S * 4 + vol_tree_bytes(t) + 256 + (size_t)nblk0 * S;
     if (!c.d_list) FMK_HIP(ctx, hipMalloc((void **)&c.d_list, ((size_t)1 + VOL_LIST_CAP) * 8));
     FMK_HIP(ctx, hipMemsetAsync(c.d_list, 0, 8, ctx->stream));
-    if (c.work_bytes < bytes) {
+    if (c.work_bytes < bytes) {                                     // (a failed allocation is an error here, not a decline)
         if (c.work) FMK_HIP(ctx, hipFree(c.work));
         c.work = nullptr; c.work_bytes = 0;
         FMK_HIP(ctx, hipMalloc(&c.work, bytes));
         c.work_bytes = bytes;
     }
     uint32_t *nxt = (uint32_t *)c.work;
-    uint32_t *Eall = nxt + (size_t)nblk0 * S;
-    uint32_t *Call = Eall + tbl;
-    int64_t *offall = (int64_t *)(Call + tbl);
-    uint32_t *entall = (uint32_t *)(offall + ents);
-    unsigned char *fragile = (unsigned char *)(entall + ents);
-    uint32_t *E[64], *C[64], *ent[64];
-    int64_t *off[64];
-    {
-        size_t to = 0, eo = 0;
-        for (int k = 0; k <= K; ++k) {
-            E[k] = Eall + to; C[k] = Call + to; to += (size_t)nblk[k] * S;
-            ent[k] = entall + eo; off[k] = offall + eo; eo += (size_t)nblk[k];
-        }
-    }
+    vol_tree_bind(t, nxt + (size_t)nblk0 * S);
+    unsigned char *fragile = (unsigned char *)nxt + (size_t)nblk0 * S * 4 + vol_tree_bytes(t);
     fmk_mail::Vol::Levels *d_lv = &ctx->d_mail->vol.lv, lv;
     int *d_status = &d_lv->status, *d_root_tie = &d_lv->root_tie;
     uint32_t *d_root = &d_lv->root;
@@ -632,17 +510,12 @@ static int vol_run(fmk_ctx *ctx, const void *a, int64_t n, double thr, VolCache 
         if (lds > 64 * 1024)
             FMK_HIP(ctx, hipFuncSetAttribute((const void *)k_vol_level0<AF64, S>, hipFuncAttributeMaxDynamicSharedMemorySize,
                                              (int)lds));
-        k_vol_level0<AF64, S><<<(unsigned)nblk0, VOL_THREADS, lds, ctx->stream>>>(a, n, thr, nxt, E[0], C[0], d_root,
+        k_vol_level0<AF64, S><<<(unsigned)nblk0, VOL_THREADS, lds, ctx->stream>>>(a, n, thr, nxt, t.E[0], t.C[0], d_root,
                                                                                   d_status, d_root_tie, fragile, c.d_list,
                                                                                   ctx->fast_threshold ? 0 : 1);
     }
     FMK_LAUNCH_CHECK(ctx);
-    for (int k = 1; k <= K; ++k) {
-        const int64_t tot = nblk[k] * S;
-        k_vol_level_up4<<<(unsigned)fmk_ceil_div(tot, 256), 256, 0, ctx->stream>>>(
-            LS, E[k - 1], C[k - 1], nblk[k - 1], spanq[k - 1], E[k], C[k], nblk[k], d_status, RAD);
-        FMK_LAUNCH_CHECK(ctx);
-    }
+    FMK_TRY(vol_tree_up(ctx, t, d_status));
     // root entry + total count
     FMK_TRY(fmk_read_back(ctx, &lv, d_lv, sizeof lv));
     const int status = lv.status;
@@ -650,25 +523,10 @@ static int vol_run(fmk_ctx *ctx, const void *a, int64_t n, double thr, VolCache 
     if (status & VOL_ST_BAD) return 2;              // negative / NaN volumes: only the serial walk reproduces those
     if (status & VOL_ST_OVERFLOW) return 1;
     int64_t closes = 0;
-    if (root != VOL_END) {
-        if ((int64_t)root >= S) return 1;
-        uint32_t cnt = 0;
-        FMK_TRY(fmk_read_back(ctx, &cnt, C[K] + root, 4));
-        closes = cnt;
-    }
-    c.count = closes + 1;
-    if (c.dbuf && c.cap < c.count) { FMK_HIP(ctx, hipFree(c.dbuf)); c.dbuf = nullptr; }
-    if (!c.dbuf) { FMK_HIP(ctx, hipMalloc((void **)&c.dbuf, (size_t)c.count * 8)); c.cap = c.count; }
-    // top-down
-    const int64_t one = 1;
-    FMK_HIP(ctx, hipMemcpyAsync(ent[K], &root, 4, hipMemcpyHostToDevice, ctx->stream));
-    FMK_HIP(ctx, hipMemcpyAsync(off[K], &one, 8, hipMemcpyHostToDevice, ctx->stream));
-    for (int k = K; k >= 1; --k) {
-        k_vol_descend4<<<(unsigned)fmk_ceil_div(nblk[k], 256), 256, 0, ctx->stream>>>(
-            LS, ent[k], off[k], nblk[k], spanq[k - 1], E[k - 1], C[k - 1], nblk[k - 1], ent[k - 1], off[k - 1], RAD);
-        FMK_LAUNCH_CHECK(ctx);
-    }
-    k_vol_emit<<<(unsigned)fmk_ceil_div(nblk0, 256), 256, 0, ctx->stream>>>(LS, ent[0], off[0], nblk0, nxt, c.dbuf, c.cap,
+    FMK_TRY(vol_tree_closes(ctx, t, root, &closes));
+    FMK_TRY(vol_ensure_out(ctx, c, closes));
+    FMK_TRY(vol_tree_down(ctx, t, root));
+    k_vol_emit<<<(unsigned)fmk_ceil_div(nblk0, 256), 256, 0, ctx->stream>>>(LS, t.ent[0], t.off[0], nblk0, nxt, c.dbuf, c.cap,
                                                                             fragile, c.d_list, d_status, d_root_tie, thr);
     FMK_LAUNCH_CHECK(ctx);
     return vol_certify(ctx, a, AF64 ? 1 : 0, n, thr, c);
@@ -1490,22 +1348,6 @@ static int vol_certify(fmk_ctx *ctx, const void *a, int is_f64, int64_t n, doubl
     return FMK_OK;
 }
 
-// workspace of the global tier (5 + 16 bytes per tick).  Returns 1 -- "use the next tier" -- when the device cannot
-// provide it: the chain walk needs no tables, and a full HBM is no reason to fail the call.
-static int vol_ensure(fmk_ctx *ctx, void **buf, size_t *have, size_t bytes)
-{
-    if (*have >= bytes) return FMK_OK;
-    if (*buf) FMK_HIP(ctx, hipFree(*buf));
-    *buf = nullptr; *have = 0;
-    if (hipMalloc(buf, bytes) != hipSuccess) {
-        (void)hipGetLastError();                                    // clear the sticky out-of-memory error
-        *buf = nullptr;
-        return 1;
-    }
-    *have = bytes;
-    return FMK_OK;
-}
-
 // needs the full-stream prefix of a total_only vol_chase call in c.work.  Returns FMK_OK, 1 (not suitable: walk the chain)
 static int vol_global_tables(fmk_ctx *ctx, const void *a, int is_f64, int64_t n, double thr, VolCache &c, double mean_len)
 {
@@ -1569,56 +1411,19 @@ static int vol_global_tables(fmk_ctx *ctx, const void *a, int is_f64, int64_t n,
     // leaves the tables far ahead; beyond that (or a span of more than 4M ticks) the chain is walked
     if ((double)S > 32.0 * mean_len || ls > 22) return 1;
     const int64_t nblk0 = fmk_ceil_div(n, S);
-    int64_t nb[64], spanq[64];
-    int K = 0;
-    nb[0] = nblk0;
-    spanq[0] = S;
-    while (nb[K] > 1) { nb[K + 1] = (nb[K] + VOL_RADIX - 1) / VOL_RADIX; spanq[K + 1] = spanq[K] * VOL_RADIX; ++K; }   // radix-16 levels
-    size_t tbl = 0, ents = 0;
-    for (int k = 0; k <= K; ++k) { tbl += (size_t)nb[k] * S; ents += (size_t)nb[k]; }
-    FMK_TRY(vol_ensure(ctx, &c.work3, &c.work3_bytes, 2 * tbl * 4 + ents * (4 + 8) + 256));
-    uint32_t *Eall = (uint32_t *)c.work3;
-    uint32_t *Call = Eall + tbl;
-    int64_t *offall = (int64_t *)(Call + tbl);
-    uint32_t *entall = (uint32_t *)(offall + ents);
-    uint32_t *E[64], *C[64], *ent[64];
-    int64_t *off[64];
-    {
-        size_t to = 0, eo = 0;
-        for (int k = 0; k <= K; ++k) {
-            E[k] = Eall + to; C[k] = Call + to; to += (size_t)nb[k] * S;
-            ent[k] = entall + eo; off[k] = offall + eo; eo += (size_t)nb[k];
-        }
-    }
-    k_vg_level0<<<(unsigned)fmk_ceil_div(nblk0 * S, 256), 256, 0, ctx->stream>>>(nxt, n, ls, nblk0 * S, E[0], C[0]);
+    VolTree t = vol_tree_plan(nblk0, S, S, VOL_RADIX);
+    FMK_TRY(vol_ensure(ctx, &c.work3, &c.work3_bytes, vol_tree_bytes(t) + 256));
+    vol_tree_bind(t, c.work3);
+    k_vg_level0<<<(unsigned)fmk_ceil_div(nblk0 * S, 256), 256, 0, ctx->stream>>>(nxt, n, ls, nblk0 * S, t.E[0], t.C[0]);
     FMK_LAUNCH_CHECK(ctx);
-    for (int k = 1; k <= K; ++k) {
-        k_vol_level_up4<<<(unsigned)fmk_ceil_div(nb[k] * S, 256), 256, 0, ctx->stream>>>(
-            ls, E[k - 1], C[k - 1], nb[k - 1], spanq[k - 1], E[k], C[k], nb[k], d_status, VOL_RADIX);
-        FMK_LAUNCH_CHECK(ctx);
-    }
+    FMK_TRY(vol_tree_up(ctx, t, d_status));
     int64_t closes = 0;
-    if (root != VOL_END) {
-        if ((int64_t)root >= S) return 1;
-        auto &h = ctx->h_mail->vol.closes;
-        hipError_t e = hipMemcpyAsync(&h.count, C[K] + root, 4, hipMemcpyDeviceToHost, ctx->stream);
-        if (e == hipSuccess) e = hipMemcpyAsync(&h.status, d_status, 4, hipMemcpyDeviceToHost, ctx->stream);
-        FMK_TRY(fmk_wait(ctx, e));
-        if (h.status & VOL_ST_OVERFLOW) return 1;
-        closes = h.count;
-    }
-    c.count = closes + 1;
-    if (c.dbuf && c.cap < c.count) { FMK_HIP(ctx, hipFree(c.dbuf)); c.dbuf = nullptr; }
-    if (!c.dbuf) { FMK_HIP(ctx, hipMalloc((void **)&c.dbuf, (size_t)c.count * 8)); c.cap = c.count; }
-    const int64_t one = 1;
-    FMK_HIP(ctx, hipMemcpyAsync(ent[K], &root, 4, hipMemcpyHostToDevice, ctx->stream));
-    FMK_HIP(ctx, hipMemcpyAsync(off[K], &one, 8, hipMemcpyHostToDevice, ctx->stream));
-    for (int k = K; k >= 1; --k) {
-        k_vol_descend4<<<(unsigned)fmk_ceil_div(nb[k], 256), 256, 0, ctx->stream>>>(
-            ls, ent[k], off[k], nb[k], spanq[k - 1], E[k - 1], C[k - 1], nb[k - 1], ent[k - 1], off[k - 1], VOL_RADIX);
-        FMK_LAUNCH_CHECK(ctx);
-    }
-    k_vol_emit<<<(unsigned)fmk_ceil_div(nblk0, 256), 256, 0, ctx->stream>>>(ls, ent[0], off[0], nblk0, nxt, c.dbuf, c.cap,
+    int status = 0;
+    FMK_TRY(vol_tree_closes(ctx, t, root, &closes, d_status, &status));
+    if (status & VOL_ST_OVERFLOW) return 1;
+    FMK_TRY(vol_ensure_out(ctx, c, closes));
+    FMK_TRY(vol_tree_down(ctx, t, root));
+    k_vol_emit<<<(unsigned)fmk_ceil_div(nblk0, 256), 256, 0, ctx->stream>>>(ls, t.ent[0], t.off[0], nblk0, nxt, c.dbuf, c.cap,
                                                                             fragile, c.d_list, d_pstat, nullptr, thr);
     FMK_LAUNCH_CHECK(ctx);
     return vol_certify(ctx, a, is_f64, n, thr, c);

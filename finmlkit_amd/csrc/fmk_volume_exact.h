@@ -1,5 +1,5 @@
 // fmk_volume_exact.h -- _volume_bar_indexer (finmlkit/bar/logic.py:87-115), the EXACT-SUM tier of the jump tables (round 4).
-// Included by fmk_volume.hip after its table kernels (k_vol_level_up4, k_vol_descend4) and VolCache.
+// Included by fmk_volume.hip after the table tree (fmk_voltree.h), VolCache and vol_ensure.
 //
 // Why a second level 0.  k_vol_level0 builds, for EVERY tick of a 2048-tick block, the chain link nxt(j), a fragile byte and the pair
 // (E, C) -- 13 B/tick written, the block's 2 x 2048 ticks read, i.e. 21 B/tick of HBM traffic for a 4 B/tick column -- and it has
@@ -315,115 +315,18 @@ __global__ __launch_bounds__(256) void k_vx_emit(int64_t S, const uint32_t *__re
     }
 }
 
-// k_vol_level_up4 / k_vol_descend4 for tables of W rows per block, W any number (theirs is a power of two): level q + 1 composes
-// `radix` blocks of level q over the W entry ticks of the first of them
-// a row of the packed level-0 table: count, and the chain's exit as an absolute tick (VOL_END: none)
-__device__ __forceinline__ void vx_unpack0(uint32_t w, int64_t block, int64_t S, uint32_t *e, uint32_t *c)
-{
-    *c = w >> 16;
-    *e = (w & 0xFFFFu) == 0xFFFFu ? VOL_END : (uint32_t)((block + 1) * S + (w & 0xFFFFu));
-}
-
-template <bool PACKED>
-__global__ __launch_bounds__(256) void k_vx_level_up(int W, const uint32_t *__restrict__ Ep, const uint32_t *__restrict__ Cp,
-                                                     int64_t nblk_prev, int64_t span_prev, uint32_t *__restrict__ Ek,
-                                                     uint32_t *__restrict__ Ck, int64_t nblk, int *__restrict__ status, int radix)
-{
-    const int64_t b = blockIdx.x;
-    const int i = (int)(blockIdx.y * blockDim.x + threadIdx.x);
-    if (i >= W || b >= nblk) return;
-    const int64_t c0 = (int64_t)radix * b;
-    uint32_t x, c;
-    if constexpr (PACKED) vx_unpack0(Ep[c0 * W + i], c0, span_prev, &x, &c);
-    else { x = Ep[c0 * W + i]; c = Cp[c0 * W + i]; }
-    for (int j = 1; j < radix; ++j) {
-        const int64_t child = c0 + j;
-        if (x == VOL_END || child >= nblk_prev) break;
-        const int64_t i2 = (int64_t)x - child * span_prev;           // the chain enters the next child in its first W ticks
-        if (i2 < 0 || i2 >= W) { vol_flag(status, VOL_ST_OVERFLOW); x = VOL_END; break; }
-        if constexpr (PACKED) {
-            uint32_t c2;
-            vx_unpack0(Ep[child * W + i2], child, span_prev, &x, &c2);
-            c += c2;
-        } else {
-            c += Cp[child * W + i2];
-            x = Ep[child * W + i2];
-        }
-    }
-    Ek[b * W + i] = x;
-    Ck[b * W + i] = c;
-}
-
-template <bool PACKED>
-__global__ __launch_bounds__(256) void k_vx_descend(int W, const uint32_t *__restrict__ ent_k, const int64_t *__restrict__ off_k,
-                                                    int64_t nblk_k, int64_t span_prev, const uint32_t *__restrict__ Ep,
-                                                    const uint32_t *__restrict__ Cp, int64_t nblk_prev,
-                                                    uint32_t *__restrict__ ent_p, int64_t *__restrict__ off_p, int radix)
-{
-    const int64_t b = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (b >= nblk_k) return;
-    uint32_t e = ent_k[b];
-    int64_t o = off_k[b];
-    const int64_t c0 = (int64_t)radix * b;
-    ent_p[c0] = e;
-    off_p[c0] = o;
-    for (int j = 1; j < radix; ++j) {
-        const int64_t child = c0 + j;
-        if (child >= nblk_prev) break;
-        if (e != VOL_END) {
-            const int64_t i = (int64_t)e - (child - 1) * span_prev;  // the entry lies in the previous child's first W ticks
-            if (i >= 0 && i < W) {
-                if constexpr (PACKED) {
-                    uint32_t c2;
-                    vx_unpack0(Ep[(child - 1) * W + i], child - 1, span_prev, &e, &c2);
-                    o += c2;
-                } else {
-                    o += Cp[(child - 1) * W + i];
-                    e = Ep[(child - 1) * W + i];
-                }
-            }
-        }
-        ent_p[child] = e;
-        off_p[child] = o;
-    }
-}
-
 // returns FMK_OK, 1 (a bar beyond W ticks: the next class), 4 (a window that does not certify: the older tier), 2 (negative / NaN
 // amounts) or an error
 template <bool AF64, int S, int W, int THREADS, bool PAD>
 static int vx_run(fmk_ctx *ctx, const void *a, int64_t n, double thr, VolCache &c)
 {
     const int64_t nblk0 = fmk_ceil_div(n, S);
-    const int RAD = VOL_RADIX;
-    int64_t nblk[64], spanq[64];
-    int K = 0;
-    nblk[0] = nblk0;
-    spanq[0] = S;
-    while (nblk[K] > 1) { nblk[K + 1] = (nblk[K] + RAD - 1) / RAD; spanq[K + 1] = spanq[K] * RAD; ++K; }
-    size_t tbl = 0, ents = 0;
-    for (int k = 0; k <= K; ++k) { tbl += (size_t)nblk[k] * W; ents += (size_t)nblk[k]; }
+    VolTree t = vol_tree_plan(nblk0, S, W, VOL_RADIX, true);
+    // workspace: a 16-bit link per tick, the tree
     const size_t nxt_bytes = (((size_t)nblk0 * S * 2) + 255) & ~(size_t)255;
-    const size_t bytes = nxt_bytes + 2 * tbl * 4 + ents * (4 + 8) + 256;
-    if (c.work_bytes < bytes) {
-        if (c.work) FMK_HIP(ctx, hipFree(c.work));
-        c.work = nullptr; c.work_bytes = 0;
-        if (hipMalloc(&c.work, bytes) != hipSuccess) { (void)hipGetLastError(); c.work = nullptr; return 1; }
-        c.work_bytes = bytes;
-    }
+    FMK_TRY(vol_ensure(ctx, &c.work, &c.work_bytes, nxt_bytes + vol_tree_bytes(t) + 256));
     uint16_t *nxt16 = (uint16_t *)c.work;
-    uint32_t *Eall = (uint32_t *)((char *)c.work + nxt_bytes);
-    uint32_t *Call = Eall + tbl;
-    int64_t *offall = (int64_t *)(Call + tbl);
-    uint32_t *entall = (uint32_t *)(offall + ents);
-    uint32_t *E[64], *C[64], *ent[64];
-    int64_t *off[64];
-    {
-        size_t to = 0, eo = 0;
-        for (int k = 0; k <= K; ++k) {
-            E[k] = Eall + to; C[k] = Call + to; to += (size_t)nblk[k] * W;
-            ent[k] = entall + eo; off[k] = offall + eo; eo += (size_t)nblk[k];
-        }
-    }
+    vol_tree_bind(t, (char *)c.work + nxt_bytes);
     fmk_mail::Vol::Levels *d_lv = &ctx->d_mail->vol.lv, lv;
     int *d_status = &d_lv->status;
     uint32_t *d_root = &d_lv->root;
@@ -434,19 +337,11 @@ static int vx_run(fmk_ctx *ctx, const void *a, int64_t n, double thr, VolCache &
         if (lds > 64 * 1024)
             FMK_HIP(ctx, hipFuncSetAttribute((const void *)k_vx_level0<AF64, S, W, THREADS, PAD>,
                                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        k_vx_level0<AF64, S, W, THREADS, PAD><<<(unsigned)nblk0, THREADS, lds, ctx->stream>>>(a, n, thr, nxt16, E[0], d_root, d_status);
+        k_vx_level0<AF64, S, W, THREADS, PAD><<<(unsigned)nblk0, THREADS, lds, ctx->stream>>>(a, n, thr, nxt16, t.E[0], d_root, d_status);
     }
     FMK_LAUNCH_CHECK(ctx);
-    // the status is known after level 0; the level-ups are cheap (N W / (S RAD) entries and less) and run regardless
-    for (int k = 1; k <= K; ++k) {
-        if (k == 1)
-            k_vx_level_up<true><<<dim3((unsigned)nblk[k], (unsigned)fmk_ceil_div(W, 256)), 256, 0, ctx->stream>>>(
-                W, E[0], nullptr, nblk[0], spanq[0], E[k], C[k], nblk[k], d_status, RAD);
-        else
-            k_vx_level_up<false><<<dim3((unsigned)nblk[k], (unsigned)fmk_ceil_div(W, 256)), 256, 0, ctx->stream>>>(
-                W, E[k - 1], C[k - 1], nblk[k - 1], spanq[k - 1], E[k], C[k], nblk[k], d_status, RAD);
-        FMK_LAUNCH_CHECK(ctx);
-    }
+    // the status is known after level 0; the level-ups are cheap (N W / (S VOL_RADIX) entries and less) and run regardless
+    FMK_TRY(vol_tree_up(ctx, t, d_status));
     FMK_TRY(fmk_read_back(ctx, &lv, d_lv, sizeof lv));
     const int status = lv.status;
     const uint32_t root = lv.root;
@@ -454,28 +349,10 @@ static int vx_run(fmk_ctx *ctx, const void *a, int64_t n, double thr, VolCache &
     if (status & VOL_ST_INEXACT) return 4;                          // no class of this tier will serve the stream
     if (status & VOL_ST_OVERFLOW) return 1;
     int64_t closes = 0;
-    if (root != VOL_END) {
-        if ((int64_t)root >= W) return 1;
-        uint32_t cnt = 0;
-        FMK_TRY(fmk_read_back(ctx, &cnt, (K == 0 ? E[0] : C[K]) + root, 4));
-        closes = K == 0 ? cnt >> 16 : cnt;                           // (a single block: the packed level-0 row itself)
-    }
-    c.count = closes + 1;
-    if (c.dbuf && c.cap < c.count) { FMK_HIP(ctx, hipFree(c.dbuf)); c.dbuf = nullptr; }
-    if (!c.dbuf) { FMK_HIP(ctx, hipMalloc((void **)&c.dbuf, (size_t)c.count * 8)); c.cap = c.count; }
-    const int64_t one = 1;
-    FMK_HIP(ctx, hipMemcpyAsync(ent[K], &root, 4, hipMemcpyHostToDevice, ctx->stream));
-    FMK_HIP(ctx, hipMemcpyAsync(off[K], &one, 8, hipMemcpyHostToDevice, ctx->stream));
-    for (int k = K; k >= 1; --k) {
-        if (k == 1)
-            k_vx_descend<true><<<(unsigned)fmk_ceil_div(nblk[k], 256), 256, 0, ctx->stream>>>(
-                W, ent[k], off[k], nblk[k], spanq[0], E[0], nullptr, nblk[0], ent[0], off[0], RAD);
-        else
-            k_vx_descend<false><<<(unsigned)fmk_ceil_div(nblk[k], 256), 256, 0, ctx->stream>>>(
-                W, ent[k], off[k], nblk[k], spanq[k - 1], E[k - 1], C[k - 1], nblk[k - 1], ent[k - 1], off[k - 1], RAD);
-        FMK_LAUNCH_CHECK(ctx);
-    }
-    k_vx_emit<<<(unsigned)fmk_ceil_div(nblk0, 256), 256, 0, ctx->stream>>>(S, ent[0], off[0], nblk0, nxt16, c.dbuf, c.cap);
+    FMK_TRY(vol_tree_closes(ctx, t, root, &closes));
+    FMK_TRY(vol_ensure_out(ctx, c, closes));
+    FMK_TRY(vol_tree_down(ctx, t, root));
+    k_vx_emit<<<(unsigned)fmk_ceil_div(nblk0, 256), 256, 0, ctx->stream>>>(S, t.ent[0], t.off[0], nblk0, nxt16, c.dbuf, c.cap);
     FMK_LAUNCH_CHECK(ctx);
     c.unc = 0;                                                      // exact sums: every decision is the reference's
     return FMK_OK;

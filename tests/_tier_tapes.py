@@ -337,10 +337,26 @@ def refused_cases():
     return out
 
 
+LDS_S = 2048                   # ticks per level-0 block of the LDS tables (vol_run)
+
+
+def lds_tree_cases():
+    """The tape of refused_lognormal_f64 at the edges of the LDS tier's table tree (csrc/fmk_voltree.h, radix 16): one block with and
+    without a tail (no level above level 0), two and three blocks (one level), 17 blocks (two levels), 257 blocks (three)."""
+    out = []
+    for n in (LDS_S - 1, LDS_S, LDS_S + 1, 2 * LDS_S + 1, 16 * LDS_S + 1, 256 * LDS_S + 1):
+        def make(n=n):
+            a = np.random.default_rng(41).lognormal(0.0, 0.5, n)
+            return a, float(np.mean(a)) * 300.0
+        out.append(VolCase(f"lds_lognormal_n{n}", make, LDS, {E1024: NOCERT}, certifies=False, est_band=(200.0, 450.0)))
+    return out
+
+
 def global_cases():
     out = []
-    for L in (3000, 20_000, 60_000):
-        for n in (70_001, 1_200_000):
+    # 3000-tick bars give tables of 4096 rows: n = 4097 is two blocks (one level above level 0), 16 * 4096 + 1 is 17 (two levels)
+    for L, ns in ((3000, (4097, 16 * 4096 + 1, 70_001, 1_200_000)), (20_000, (70_001, 1_200_000)), (60_000, (70_001, 1_200_000))):
+        for n in ns:
             def make(L=L, n=n):
                 a = np.random.default_rng(50 + L // 1000).lognormal(0.0, 0.5, n)
                 return a, L * (math.fsum(a) / n)
@@ -480,7 +496,7 @@ def serial_cases():
 
 
 def volume_cases():
-    return (class_alone_cases() + handoff_cases() + limit_cases() + refused_cases() + global_cases() + golden_case() + knife_cases() + chain_cases() + misled_cases()
+    return (class_alone_cases() + handoff_cases() + limit_cases() + refused_cases() + lds_tree_cases() + global_cases() + golden_case() + knife_cases() + chain_cases() + misled_cases()
             + serial_cases())
 
 
