@@ -238,6 +238,13 @@ class DeviceArray:
         return DeviceArray(self.ctx, count, self.dtype, self.ptr + start * self.dtype.itemsize, owner=self)
 
     @classmethod
+    def adopt(cls, ctx: Context, n: int, dtype, dptr: int) -> "DeviceArray":
+        """Takes over a block that a library call handed back from fmk_alloc (fmk_flow_bar_indexer_dev): freed like an own one."""
+        d = cls(ctx, n, dtype, dptr)
+        d._owned = True
+        return d
+
+    @classmethod
     def from_host(cls, ctx: Context, a) -> "DeviceArray":
         a = np.ascontiguousarray(a)
         d = cls(ctx, a.size, a.dtype)
@@ -265,6 +272,34 @@ class DeviceArray:
                 self.ctx.free(self.ptr)
         except Exception:
             pass
+
+
+FLOW_RULES = {"imbalance": 0, "run": 1}
+FLOW_KINDS = {"tick": 0, "volume": 1, "dollar": 2}
+
+
+def flow_kind(kind) -> int:
+    """The size a tick contributes to an imbalance / run bar: "tick" 1, "volume" the amount, "dollar" price * amount."""
+    if kind not in FLOW_KINDS:
+        raise ValueError(f"kind must be one of {sorted(FLOW_KINDS)}, got {kind!r}")
+    return FLOW_KINDS[kind]
+
+
+def flow_bar_index(ctx: Context, rule: str, kind: str, price, amount, amount_is_f64: int, side, n: int, threshold: float) -> DeviceArray:
+    """fmk_flow_bar_indexer_dev on device columns (DeviceArrays; price may be None unless kind is "dollar") -> the int64 close
+    indices in a buffer of exactly their number, which the returned array owns.  One call, nothing cached."""
+    k = flow_kind(kind)
+    out, m = c_vp(), c_i64()
+    ctx.call("fmk_flow_bar_indexer_dev", C.c_int(FLOW_RULES[rule]), C.c_int(k), price.p if (k == 2 and price is not None) else None,
+             amount.p if k >= 1 else None, C.c_int(int(amount_is_f64)), side.p, c_i64(n), c_f64(threshold), C.byref(out), C.byref(m))
+    return DeviceArray.adopt(ctx, m.value, np.int64, out.value)
+
+
+def flow_bars_last() -> dict:
+    """fmk_diag_flowbars_last: which rung answered the last imbalance / run bar call of this process, and why the tables declined."""
+    v = [c_i64() for _ in range(4)]
+    check(lib().fmk_diag_flowbars_last(*[C.byref(x) for x in v]))
+    return dict(zip(("rung", "code", "longest", "ls"), (int(x.value) for x in v)))
 
 
 def upload_columns(ctx: Context, arrays):

@@ -90,6 +90,32 @@ class DollarBarKit(_ThresholdKit):
         return self._close_from(self._device().dollar_bar_index(self.dollar_thrs))
 
 
+class ImbalanceBarKit(_ThresholdKit):
+    """The signed flow of the bar, |sum side * size| >= `threshold`, closes it (AFML 2.3.2, fixed threshold; the reference has no
+    such kit).  `kind`: the size of a tick -- "tick" 1, "volume" the amount, "dollar" price * amount."""
+
+    def __init__(self, trades: TradesData, threshold: float, kind: str = "volume"):
+        super().__init__(trades)
+        self.threshold, self.kind = threshold, kind
+        logger.info(f"Imbalance bar builder initialized with {kind} threshold: {threshold}.")
+
+    def _comp_bar_close(self):
+        return self._close_from(self._device().imbalance_bar_index(self.threshold, self.kind))
+
+
+class RunBarKit(_ThresholdKit):
+    """The larger of the bar's buy total and sell total >= `threshold` closes it (AFML 2.3.2, fixed threshold; the reference has
+    no such kit).  `kind` as for ImbalanceBarKit."""
+
+    def __init__(self, trades: TradesData, threshold: float, kind: str = "volume"):
+        super().__init__(trades)
+        self.threshold, self.kind = threshold, kind
+        logger.info(f"Run bar builder initialized with {kind} threshold: {threshold}.")
+
+    def _comp_bar_close(self):
+        return self._close_from(self._device().run_bar_index(self.threshold, self.kind))
+
+
 class CUSUMBarKit(BarBuilderBase):
     """Symmetric CUSUM bars with an adaptive threshold sigma_mult * sigma (reference kit.py:140-181)."""
 

@@ -81,14 +81,40 @@ def _dollar_bar_indexer(prices: NDArray[np.float64], volumes: NDArray, threshold
     return _threshold_indexer("fmk_dollar_bar_indexer_dev", (dp.p, dv.p, C.c_int(f64)), len(v), threshold)
 
 
-def _imbalance_bar_indexer(timestamps, prices, volumes, threshold):
-    """Reference stub: finmlkit/bar/logic.py:224-241."""
-    raise NotImplementedError("Imbalance bar indexer is not implemented yet.")
+def _flow_bar_indexer(rule, timestamps, prices, volumes, threshold, kind, sides) -> NDArray[np.int64]:
+    k = _ffi.flow_kind(kind)
+    n = len(prices)
+    if len(timestamps) != n or len(volumes) != n or (sides is not None and len(sides) != n):
+        raise ValueError("timestamps, prices, volumes and sides must have the same length.")
+    if n == 0:                                     # like the other indexers: the list starts as [0] and the loop does not run
+        return np.zeros(1, np.int64)
+    ctx = _ffi.default_context()
+    v, f64 = _ffi.amount_array(volumes)
+    dv = DeviceArray.from_host(ctx, v) if k >= 1 else None
+    dp = None
+    if k == 2 or sides is None:
+        dp = DeviceArray.from_host(ctx, np.ascontiguousarray(prices, dtype=np.float64))
+    if sides is None:                              # the tick rule on the device: the side column never visits the host
+        ds = DeviceArray(ctx, n, np.int8)
+        ctx.call("fmk_comp_trade_side_vector_dev", dp.p, c_i64(n), ds.p)
+    else:
+        ds = DeviceArray.from_host(ctx, np.ascontiguousarray(sides, dtype=np.int8))
+    return _ffi.flow_bar_index(ctx, rule, kind, dp, dv, f64, ds, n, float(threshold)).to_host()
 
 
-def _run_bar_indexer(timestamps, prices, volumes, threshold):
-    """Reference stub: finmlkit/bar/logic.py:244-261."""
-    raise NotImplementedError("Run bar indexer is not implemented yet.")
+def _imbalance_bar_indexer(timestamps, prices, volumes, threshold, kind="volume", sides=None) -> NDArray[np.int64]:
+    """Imbalance bars with a fixed threshold (AFML 2.3.2; the reference has a stub, finmlkit/bar/logic.py:224-241): the signed sum
+    theta += side * size closes a bar at the first |theta| >= threshold behind tick 0 and starts again from zero.  size by `kind`:
+    "tick" 1, "volume" the amount, "dollar" price * amount; `sides` -1 / 0 / +1 per tick, None: the tick rule
+    (comp_trade_side_vector).  Returns the int64 close indices, the first of which is 0 (like _volume_bar_indexer)."""
+    return _flow_bar_indexer("imbalance", timestamps, prices, volumes, threshold, kind, sides)
+
+
+def _run_bar_indexer(timestamps, prices, volumes, threshold, kind="volume", sides=None) -> NDArray[np.int64]:
+    """Run bars with a fixed threshold (AFML 2.3.2; reference stub: finmlkit/bar/logic.py:244-261): the buy total and the sell
+    total of the bar are kept apart, and the bar closes at the first tick behind tick 0 where either reaches the threshold.
+    Arguments and result as _imbalance_bar_indexer."""
+    return _flow_bar_indexer("run", timestamps, prices, volumes, threshold, kind, sides)
 
 
 def _cusum_bar_indexer(timestamps: NDArray[np.int64], prices: NDArray[np.float64], sigma: NDArray[np.float64],

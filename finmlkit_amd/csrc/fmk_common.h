@@ -42,6 +42,12 @@ struct fmk_mail {
         int64_t chase_res;                 // k_vc_chase: closes (or the total, total_only)
         int mismatch;                      // k_vol_verify
     } vol;
+    struct Fb {                            // fmk_flowbars.hip
+        // k_fb_prefix: status bits, the tape's quantum as a binary exponent (atomicMin); k_fb_scan: the sum of |increment|;
+        // k_fb_links / k_fb_root: the longest link, the first close; k_vol_tree_up: tree_status
+        struct Tape { int status; int qexp; uint32_t maxlen; uint32_t root; double sum_abs; int tree_status; } tape;
+        int64_t serial_count;              // k_fb_serial
+    } fb;
     struct Dl {                            // fmk_dollar.hip
         struct Pass1 { int bad; unsigned long long dmax; double whale; double total[2] /* hi, lo; not cleared */; } p1;
         struct Emit { unsigned long long frag; int64_t res; unsigned long long area; } emit;       // res also: k_dl_scan_min

@@ -260,6 +260,25 @@ class DeviceTrades:
         return self._threshold_index("fmk_dollar_bar_indexer_dev",
                                      (self.price.p, self.amount.p, C.c_int(self.amount_is_f64)), threshold)
 
+    def _flow_bar_index(self, rule: str, threshold: float, kind: str) -> DeviceArray:
+        _ffi.flow_kind(kind)
+        if self.side is None:
+            raise ValueError(f"{rule} bars need the side column of the trades")
+        if self.n == 0:
+            d = DeviceArray(self.ctx, 1, np.int64)
+            d.zero()
+            return d
+        return _ffi.flow_bar_index(self.ctx, rule, kind, self.price, self.amount, self.amount_is_f64, self.side, self.n,
+                                   float(threshold))
+
+    def imbalance_bar_index(self, threshold: float, kind: str = "volume") -> DeviceArray:
+        """Imbalance bars with a fixed threshold on the resident columns (bar.logic._imbalance_bar_indexer)."""
+        return self._flow_bar_index("imbalance", threshold, kind)
+
+    def run_bar_index(self, threshold: float, kind: str = "volume") -> DeviceArray:
+        """Run bars with a fixed threshold on the resident columns (bar.logic._run_bar_indexer)."""
+        return self._flow_bar_index("run", threshold, kind)
+
     def gather_ts(self, close_idx: DeviceArray) -> DeviceArray:
         out = DeviceArray(self.ctx, close_idx.n, np.int64)
         self.ctx.call("fmk_gather_i64_dev", self.ts.p, c_i64(self.n), close_idx.p, c_i64(close_idx.n), out.p)

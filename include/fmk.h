@@ -148,6 +148,14 @@ int fmk_dollar_bar_indexer_dev(fmk_ctx *ctx, const double *d_price, const void *
                                int amount_is_f64, int64_t n, double threshold,
                                int64_t *d_close_idx, int64_t capacity, int64_t *n_idx,
                                int64_t *n_uncertified);
+/* Imbalance (rule 0) and run (rule 1) bars with a FIXED threshold (AFML 2.3.2; the reference has only stubs, logic.py:224-261; the
+ * loops that define them: DESIGN.md "Imbalance and run bars").  Tick size by kind: 0 one per tick, 1 the amount, 2 price * amount
+ * (d_price is read for kind 2 only).  d_side: -1 / 0 / +1 per tick.  ONE call does the work once: *d_close_idx receives a buffer of
+ * exactly *n_idx close indices (the first is 0) from fmk_alloc, which the caller gives back with fmk_free.  Nothing is cached
+ * between calls, so a column overwritten in place is read again.  Bit-equal to the loops on every input. */
+int fmk_flow_bar_indexer_dev(fmk_ctx *ctx, int rule, int kind, const double *d_price, const void *d_amount,
+                             int amount_is_f64, const int8_t *d_side, int64_t n, double threshold,
+                             int64_t **d_close_idx, int64_t *n_idx);
 /* d_out[i] = d_in[idx[i]] for int64 (close_ts = timestamps[close_indices], kit.py:66). */
 int fmk_gather_i64_dev(fmk_ctx *ctx, const int64_t *d_in, int64_t n_in, const int64_t *d_idx,
                        int64_t n_idx, int64_t *d_out);

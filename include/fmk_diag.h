@@ -88,6 +88,12 @@ enum fmk_vol_tier {
  * pass; NaN where the ladder did not compute one.  *listed: the fragile decisions the last tier that certified by replay listed on
  * the chain BEFORE the replay (0: none, or no such tier ran). */
 int fmk_diag_volume_last(int64_t *tier, int64_t *tried, int64_t *codes, double *est_len, double *mean_len, int64_t *listed);
+/* The last fmk_flow_bar_indexer_dev call of this process (csrc/fmk_flowbars.hip).  *rung: 0 the tables, 1 the serial walk (-1: no
+ * call yet).  *code: why the tables declined -- 0 not tried (FMK_FLOWBARS_SERIAL, n beyond 2^31 - 4096) or not declined, 2 a bad amount
+ * or price (negative, NaN, infinite) or a threshold outside (0, inf), 4 the tape does not certify (its sums are not exact in
+ * float64), 1 a bar beyond 2^22 ticks.  *longest: the longest link the tables measured (0: not measured), *ls: log2 of the table
+ * span they were built with (0: not built). */
+int fmk_diag_flowbars_last(int64_t *rung, int64_t *code, int64_t *longest, int64_t *ls);
 /* order-flow redo since the last call: {(bar, column) pairs redone in tick order, 512-term tiles walked, tiles added term by term,
  * pairs of column 0 .. 6 (buy / sell volume, buy / sell dollars, spread, signed volume, signed dollars)} */
 int fmk_diag_dir_redo(fmk_ctx *ctx, int64_t *out10);
