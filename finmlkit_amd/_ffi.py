@@ -36,7 +36,13 @@ class FootprintOut(C.Structure):
         "cot_price_levels", "imb_max_run_signed", "vp_skew", "vp_gini")]
 
 
+class MicrostructureOut(C.Structure):
+    _fields_ = [(k, c_vp) for k in (
+        "kyle_lambda", "kyle_t", "amihud_lambda", "amihud_t", "hasbrouck_lambda", "hasbrouck_t", "serial_cov", "roll_spread")]
+
+
 DIRECTIONAL_FIELDS = [(k, np.int64 if "ticks" in k else np.float32) for k, _ in DirectionalOut._fields_]
+MICROSTRUCTURE_FIELDS = [(k, np.float64) for k, _ in MicrostructureOut._fields_]
 FOOTPRINT_FLAT_FIELDS = [("price_levels", np.int32), ("buy_volumes", np.float32), ("sell_volumes", np.float32),
                          ("buy_ticks", np.int32), ("sell_ticks", np.int32), ("buy_imbalances", np.uint8),
                          ("sell_imbalances", np.uint8)]
@@ -67,6 +73,9 @@ def lib() -> C.CDLL:
                 l.fmk_last_error.argtypes = [c_vp]
                 l.fmk_ctx_stream.restype = c_vp
                 l.fmk_ctx_stream.argtypes = [c_vp]
+                for f in (l.fmk_comp_bar_microstructure, l.fmk_comp_bar_microstructure_dev):
+                    f.restype = C.c_int          # (ctx, price, amount, amount_is_f64, n, close_idx, n_idx, side, out)
+                    f.argtypes = [c_vp, c_vp, c_vp, C.c_int, c_i64, c_vp, c_i64, c_vp, C.POINTER(MicrostructureOut)]
                 if l.fmk_abi_version() != 1:
                     raise FmkError("libfmk_hip.so ABI version mismatch")
                 _lib = l

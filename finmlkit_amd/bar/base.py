@@ -140,6 +140,21 @@ class BarBuilderBase(ABC):
         df.set_index("timestamp", inplace=True)
         return df
 
+    def build_microstructure_features(self) -> pd.DataFrame:
+        """Kyle / Amihud / Hasbrouck lambdas with t-values and the Roll serial covariance and spread per bar (AFML ch. 19;
+        comp_bar_microstructure_features), indexed by close timestamp."""
+        from ..engine import to_host
+        self._set_bar_close()
+        if "side" not in self.trades_df.columns:
+            raise KeyError("side")
+        d = to_host(self._device().bar_microstructure(self._d_close_idx))
+        df = pd.DataFrame({"timestamp": self.bar_close_timestamps})
+        for k, _ in _ffi.MICROSTRUCTURE_FIELDS:
+            df[k] = d[k]
+        df["timestamp"] = pd.to_datetime(df["timestamp"], unit="ns")
+        df.set_index("timestamp", inplace=True)
+        return df
+
     def build_trade_size_features(self, theta, theta_mult: float = 5.0) -> pd.DataFrame:
         """Relative mean / 95th-percentile trade size, block share and size Gini per bar
         (reference base.py:214-245)."""
@@ -233,6 +248,31 @@ def comp_bar_directional_features(prices: NDArray[np.float64], volumes: NDArray,
     ctx.call("fmk_comp_bar_directional", ptr(p), ptr(v), C.c_int(f64), c_i64(len(p)), ptr(ci), c_i64(len(ci)),
              ptr(sd), C.byref(st))
     return tuple(outs[k] for k, _ in _ffi.DIRECTIONAL_FIELDS)
+
+
+def comp_bar_microstructure_features(prices: NDArray[np.float64], volumes: NDArray, bar_close_indices: NDArray[np.int64],
+                                     trade_sides: NDArray[np.int8]):
+    """Kyle's, Amihud's and Hasbrouck's lambda with their t-values and the Roll serial covariance / spread of every bar (AFML
+    ch. 19; the reference has none -- DESIGN.md "Per-bar microstructure features" is the definition).
+
+    Returns eight float64 arrays: (kyle_lambda, kyle_t, amihud_lambda, amihud_t, hasbrouck_lambda, hasbrouck_t, serial_cov,
+    roll_spread).  A degenerate bar (fewer than three ticks, a non-positive or non-finite price, ...) is NaN, never an error."""
+    p = np.ascontiguousarray(prices, dtype=np.float64)
+    v, f64 = _ffi.amount_array(volumes)
+    ci = np.ascontiguousarray(bar_close_indices, dtype=np.int64)
+    sd = np.ascontiguousarray(trade_sides, dtype=np.int8)
+    if not (len(p) == len(v) == len(sd)):
+        raise ValueError("Prices, volumes and trade sides must have the same length.")
+    if len(ci) < 1:
+        raise ValueError("negative dimensions are not allowed")
+    _check_close_indices(ci, len(p))
+    ctx = _ffi.default_context()
+    nb = len(ci) - 1
+    outs = {k: np.empty(nb, dt) for k, dt in _ffi.MICROSTRUCTURE_FIELDS}
+    st = _ffi.MicrostructureOut(**{k: a.ctypes.data for k, a in outs.items()})
+    ctx.call("fmk_comp_bar_microstructure", ptr(p), ptr(v), C.c_int(f64), c_i64(len(p)), ptr(ci), c_i64(len(ci)), ptr(sd),
+             C.byref(st))
+    return tuple(outs[k] for k, _ in _ffi.MICROSTRUCTURE_FIELDS)
 
 
 def comp_bar_trade_size_features(amounts: NDArray, theta: NDArray[np.float64], bar_close_indices: NDArray[np.int64],

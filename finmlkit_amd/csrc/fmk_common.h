@@ -100,6 +100,7 @@ struct fmk_mail {
         unsigned long long pairs, skipped; // k_brk_pairs: (t, n) pairs walked, pairs the den <= 1e-16 test dropped
         int64_t last[4];                   // host copy only: outputs, slabs per tile span, slab elements, tiles of the last call
     } brk;
+    struct Micro { int bad; } micro;       // fmk_micro.hip (k_micro_lanes): a bar's close indices outside the tape (the call fails)
 };
 static_assert(sizeof(fmk_mail::fp_median) == 2 * sizeof(int), "k_bar_footprints adds to saw_long + 1");
 static_assert(alignof(fmk_mail) == 8, "the 64-bit atomics of the kernels need 8-byte fields");
@@ -341,6 +342,34 @@ static inline int fmk_rule_fir(fmk_ctx *ctx, const double *w, int64_t width, con
     for (int64_t k = 0; k < width; ++k)
         if (!(w[k] - w[k] == 0.0)) return fmk_set_error(ctx, FMK_E_ARG, "fir: the weights must be finite.");
     if (out == x) return fmk_set_error(ctx, FMK_E_ARG, "fir: the output must not be the input.");
+    return FMK_OK;
+}
+
+// the per-bar microstructure features (fmk_micro.hip): what both flavours refuse from their arguments alone -- the host flavour with
+// its host pointers, before anything is uploaded (it also looks at the close indices themselves, which it can read)
+static inline bool fmk_ranges_overlap(const void *a, size_t na, const void *b, size_t nb)
+{
+    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
+    return a && b && na && nb && x < y + nb && y < x + na;
+}
+static inline int fmk_rule_micro(fmk_ctx *ctx, const double *price, const void *amount, int amount_is_f64, int64_t n,
+                                 const int64_t *close_idx, int64_t n_idx, const int8_t *side, const fmk_microstructure_out *out)
+{
+    if (n_idx < 1 || n < 0) return fmk_set_error(ctx, FMK_E_ARG, "negative dimensions are not allowed");
+    if (n_idx == 1) return FMK_OK;
+    if (!out || !price || !amount || !close_idx || !side)
+        return fmk_set_error(ctx, FMK_E_ARG, "comp_bar_microstructure: a null column");
+    double *const cols[8] = {out->kyle_lambda, out->kyle_t, out->amihud_lambda, out->amihud_t,
+                             out->hasbrouck_lambda, out->hasbrouck_t, out->serial_cov, out->roll_spread};
+    const size_t ob = sizeof(double) * (size_t)(n_idx - 1);
+    for (int k = 0; k < 8; ++k) {
+        if (!cols[k]) return fmk_set_error(ctx, FMK_E_ARG, "comp_bar_microstructure: a null output column");
+        if (fmk_ranges_overlap(cols[k], ob, price, sizeof(double) * (size_t)n) ||
+            fmk_ranges_overlap(cols[k], ob, amount, (amount_is_f64 ? 8 : 4) * (size_t)n) ||
+            fmk_ranges_overlap(cols[k], ob, side, (size_t)n) ||
+            fmk_ranges_overlap(cols[k], ob, close_idx, sizeof(int64_t) * (size_t)n_idx))
+            return fmk_set_error(ctx, FMK_E_ARG, "comp_bar_microstructure: an output must not alias an input.");
+    }
     return FMK_OK;
 }
 

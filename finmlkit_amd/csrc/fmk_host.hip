@@ -311,6 +311,36 @@ int fmk_comp_bar_trade_size(fmk_ctx *ctx, const void *amount, int amount_is_f64,
     return down(ctx, size_gini, d_o[3], nb);
 }
 
+int fmk_comp_bar_microstructure(fmk_ctx *ctx, const double *price, const void *amount, int amount_is_f64, int64_t n,
+                                const int64_t *close_idx, int64_t n_idx, const int8_t *side, const fmk_microstructure_out *out)
+{
+    FMK_TRY(fmk_rule_micro(ctx, price, amount, amount_is_f64, n, close_idx, n_idx, side, out));
+    if (n_idx == 1) return FMK_OK;
+    for (int64_t i = 0; i < n_idx; ++i)
+        if (close_idx[i] < -1 || close_idx[i] >= n)
+            return fmk_set_error(ctx, FMK_E_ARG, "comp_bar_microstructure: close index %lld is outside [-1, %lld)",
+                                 (long long)close_idx[i], (long long)n);
+    const int64_t nb = n_idx - 1;
+    DevBag bag(ctx);
+    double *d_p;
+    void *d_a;
+    int64_t *d_ci;
+    int8_t *d_s;
+    FMK_TRY(bag.up(price, n, &d_p));
+    FMK_TRY(bag.up_amount(amount, amount_is_f64, n, &d_a));
+    FMK_TRY(bag.up(close_idx, n_idx, &d_ci));
+    FMK_TRY(bag.up(side, n, &d_s));
+    fmk_microstructure_out d;
+    double **dc[] = {&d.kyle_lambda, &d.kyle_t, &d.amihud_lambda, &d.amihud_t, &d.hasbrouck_lambda, &d.hasbrouck_t, &d.serial_cov,
+                     &d.roll_spread};
+    double *const hc[] = {out->kyle_lambda, out->kyle_t, out->amihud_lambda, out->amihud_t, out->hasbrouck_lambda, out->hasbrouck_t,
+                          out->serial_cov, out->roll_spread};
+    for (auto p : dc) FMK_TRY(bag.out(nb, p));
+    FMK_TRY(fmk_comp_bar_microstructure_dev(ctx, d_p, d_a, amount_is_f64, n, d_ci, n_idx, d_s, &d));
+    for (int k = 0; k < 8; ++k) FMK_TRY(down(ctx, hc[k], (const double *)*dc[k], nb));
+    return FMK_OK;
+}
+
 int fmk_comp_lagged_returns(fmk_ctx *ctx, const int64_t *ts, const double *close_, int64_t n,
                             double return_window_sec, int is_log, double *out)
 {

@@ -13,8 +13,8 @@ from typing import Dict, Optional, Tuple
 import numpy as np
 
 from . import _ffi
-from ._ffi import (DIRECTIONAL_FIELDS, FOOTPRINT_BAR_FIELDS, FOOTPRINT_FLAT_FIELDS, Context, DeviceArray,
-                   DirectionalOut, FootprintOut, c_f64, c_i64, c_vp)
+from ._ffi import (DIRECTIONAL_FIELDS, FOOTPRINT_BAR_FIELDS, FOOTPRINT_FLAT_FIELDS, MICROSTRUCTURE_FIELDS, Context, DeviceArray,
+                   DirectionalOut, FootprintOut, MicrostructureOut, c_f64, c_i64, c_vp)
 from .feature.core import clock, fracdiff
 from .feature.core.structural_break import adf
 from .feature.series_ops import OPS, resident
@@ -327,6 +327,17 @@ class DeviceTrades:
         self.ctx.call("fmk_comp_bar_directional_dev", self.price.p, self.amount.p, C.c_int(self.amount_is_f64),
                       c_i64(self.n), close_idx.p, c_i64(close_idx.n), self.side.p, C.byref(st), nz.p)
         return out, nz
+
+    def bar_microstructure(self, close_idx: DeviceArray) -> Dict[str, DeviceArray]:
+        """comp_bar_microstructure_features on device-resident columns: the eight float64 columns stay in HBM."""
+        if self.side is None:
+            raise ValueError("the microstructure features need the side column of the trades")
+        nb = max(close_idx.n - 1, 0)
+        out = {k: DeviceArray(self.ctx, nb, dt) for k, dt in MICROSTRUCTURE_FIELDS}
+        st = MicrostructureOut(**{k: out[k].ptr for k in out})
+        self.ctx.call("fmk_comp_bar_microstructure_dev", self.price.p, self.amount.p, C.c_int(self.amount_is_f64),
+                      c_i64(self.n), close_idx.p, c_i64(close_idx.n), self.side.p, C.byref(st))
+        return out
 
     def bar_footprints(self, close_idx: DeviceArray, lows: DeviceArray, highs: DeviceArray,
                        price_tick_size: float, imbalance_factor: float = 3.0):

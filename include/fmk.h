@@ -249,6 +249,32 @@ int fmk_comp_bar_trade_size(fmk_ctx *ctx, const void *amount, int amount_is_f64,
                             double theta_mult, float *mean_size_rel, float *size_95_rel,
                             float *pct_block, float *size_gini);
 
+/* comp_bar_microstructure_features: the tick-level estimators of AFML ch. 19 per bar (the reference has none; DESIGN.md "Per-bar
+ * microstructure features" is the definition).  Bar b holds the ticks s = ci[b] + 1 .. e = ci[b + 1], L of them.  For t = s + 1 .. e,
+ * in float64 without contraction (m = L - 1 of each; a bar reads no tick outside itself):
+ *   d_t = p_t - p_{t-1};  r_t = log(p_t / p_{t-1}), the quotient rounded, then the host's log bits (as comp_lagged_returns);
+ *   xk_t = side_t * v_t;  xa_t = p_t * v_t;  xh_t = side_t * sqrt(p_t * v_t), product rounded, root correctly rounded;
+ *   q_t = d_t * d_{t-1} for t = s + 2 .. e.
+ * Three regressions through the origin over the m differences -- Kyle (d on xk), Amihud (|r| on xa), Hasbrouck (r on xh) -- from the
+ * float64 moments Sxx, Sxy, Syy, whose summation ORDER IS FREE but a function of the bar alone.  The first rule that holds:
+ *   1. m < 2, a moment not finite, or Sxx == 0 -> lambda = t = NaN;          2. Syy == 0 -> lambda = t = 0.0;
+ *   3. lambda = Sxy / Sxx, u = 1 - Sxy Sxy / (Sxx Syy); u <= 2^-26 -> t = copysign(inf, Sxy);
+ *   4. t = Sxy / sqrt(Sxx Syy) * sqrt((m - 1) / u).
+ * Roll: serial_cov = sum(q) / (m - 1) for m >= 2, else NaN; roll_spread = 2 sqrt(-serial_cov) where it is negative, 0.0 where it is
+ * >= 0, NaN where it is NaN.  Nothing fails for a degenerate bar: bars of 0, 1 and 2 ticks are NaN rows, and rule 1 makes a
+ * non-positive or non-finite price or an infinite amount a NaN row.
+ * Refused (FMK_E_ARG): n_idx < 1, an output that overlaps an input, a close index outside [-1, n) -- the host flavour before
+ * anything is uploaded; the device flavour finds a bad close index on the device: such a bar is not read, the call waits once for
+ * that flag.  n_idx == 1 is zero bars and succeeds. */
+typedef struct fmk_microstructure_out {
+    double *kyle_lambda, *kyle_t, *amihud_lambda, *amihud_t, *hasbrouck_lambda, *hasbrouck_t, *serial_cov, *roll_spread;
+} fmk_microstructure_out;
+int fmk_comp_bar_microstructure_dev(fmk_ctx *ctx, const double *d_price, const void *d_amount, int amount_is_f64, int64_t n,
+                                    const int64_t *d_close_idx, int64_t n_idx, const int8_t *d_side,
+                                    const fmk_microstructure_out *d_out);
+int fmk_comp_bar_microstructure(fmk_ctx *ctx, const double *price, const void *amount, int amount_is_f64, int64_t n,
+                                const int64_t *close_idx, int64_t n_idx, const int8_t *side, const fmk_microstructure_out *out);
+
 /* ---- cfg 4: time bars + order-flow + footprints ----------------------------------------
  * Replaces BarBuilderBase.build_ohlcv + build_directional_features + build_footprints (base.py:126-300) called back to back (38 B/tick
  * as three reducers).  Two phases like comp_bar_footprints (the CSR row count must reach the caller's allocator).  (Round 1's
