@@ -680,6 +680,27 @@ class DeviceTrades:
                       avg.p, None if att is None else att.p)
         return avg, att
 
+    def sequential_bootstrap(self, event_idx: DeviceArray, touch_idx: DeviceArray, n_draws: Optional[int] = None, n_runs: int = 1,
+                             seed: int = 0, return_uniqueness: bool = False):
+        """sequential_bootstrap (label/bootstrap.py) on resident spans, as `triple_barrier` and
+        `trend_scanning` return them, on this tape's axis -> draws, a flat run-major int64 DeviceArray of n_runs * n_draws positions
+        in the event arrays; with return_uniqueness also the int64 DeviceArray of each drawn event's average uniqueness when it was
+        drawn, in units of 2^-30.  The library reads the two index arrays back for the host-side compression of the axis (16 bytes
+        per event, nothing of the tape), so the call waits for the stream."""
+        from .label.bootstrap import check_arguments
+        if touch_idx.n != event_idx.n:
+            raise ValueError("sequential_bootstrap: event_idxs and touch_idxs must have the same length.")
+        if event_idx.dtype != np.int64 or touch_idx.dtype != np.int64:
+            raise TypeError("sequential_bootstrap: the event and touch indices must be int64")
+        if event_idx.n < 1:
+            raise ValueError("sequential_bootstrap: n_events must be between 1 and 2^31 - 1.")
+        n_draws, n_runs, seed, dpl = check_arguments(event_idx.n, n_draws, n_runs, seed, None)
+        draws = DeviceArray(self.ctx, n_runs * n_draws, np.int64)
+        q = DeviceArray(self.ctx, n_runs * n_draws, np.int64) if return_uniqueness else None
+        self.ctx.call("fmk_sequential_bootstrap_dev", event_idx.p, touch_idx.p, c_i64(event_idx.n), c_i64(self.n), c_i64(n_draws),
+                      c_i64(n_runs), C.c_uint64(seed), None, c_i64(dpl), draws.p, None if q is None else q.p)
+        return (draws, q) if return_uniqueness else draws
+
 
 def to_host(d: Dict[str, DeviceArray]) -> Dict[str, np.ndarray]:
     return {k: v.to_host() for k, v in d.items()}

@@ -11,6 +11,7 @@ import pandas as pd
 
 from .. import _ffi
 from ..bar.data_model import TradesData
+from .bootstrap import sequential_bootstrap
 from .tbm import check_arguments
 from .weights import (average_uniqueness, class_balance_weights, normalize_attribution, return_attribution, time_decay)
 
@@ -199,6 +200,17 @@ class SampleWeights:
         out = pd.DataFrame({"avg_uniqueness": avg_u}, index=labels.index)
         out["return_attribution"] = info_w
         return out
+
+    @staticmethod
+    def sequential_bootstrap(labels: pd.DataFrame, n_draws: Optional[int] = None, n_runs: int = 1, seed: int = 0) -> np.ndarray:
+        """Sequential-bootstrap samples (label/bootstrap.py) of the rows of a frame with `event_idx` / `touch_idx` columns, the one
+        `compute_labels` returns -> int64 row positions of shape (n_runs, n_draws), for `labels.iloc[...]`; n_draws defaults to the
+        number of rows."""
+        if not isinstance(labels, pd.DataFrame):
+            raise ValueError("Events must be a pandas DataFrame.")
+        if "event_idx" not in labels.columns or "touch_idx" not in labels.columns:
+            raise ValueError("Events DataFrame must contain 'event_idx' and 'touch_idxs' columns.")
+        return sequential_bootstrap(labels.event_idx.values, labels.touch_idx.values, n_draws, n_runs, seed)
 
     @staticmethod
     def compute_final_weights(avg_uniqueness: pd.Series, time_decay_intercept: float = 1., return_attribution: pd.Series = None,

@@ -763,6 +763,35 @@ int fmk_label_weights_dev(fmk_ctx *ctx, const double *d_close, const int16_t *d_
                           const int64_t *d_touch_idx, int64_t n_events, double *d_avg_uniqueness, double *d_return_attribution);
 int fmk_label_weights(fmk_ctx *ctx, const double *close_, const int16_t *concurrency, int64_t n, const int64_t *event_idx,
                       const int64_t *touch_idx, int64_t n_events, double *avg_uniqueness, double *return_attribution);
+/* The sequential bootstrap (Lopez de Prado, Advances in Financial Machine Learning, section 4.5; the reference has no such function:
+ * the definition is this project's; csrc/fmk_seqboot.hip, csrc/fmk_seqboot_rule.h).  Events i = 0 .. m-1 with
+ * spans [event_idx[i], touch_idx[i]] on an axis of n positions, in any order, duplicates included; n_draws = K draws per run, n_runs
+ * = R independent runs.  The definition is in unsigned integers, so every sum is exact and the output does not depend on any tiling.
+ * Per run r, with c_t the number of earlier draws of the run whose span covers position t:
+ *   w(c) = floor(2^30 / (c + 1));  S_i = sum of w(c_t) over the span of i;  L_i = its length;  Q_i = floor(S_i / L_i), the average
+ *   uniqueness of candidate i, itself counted, in units of 2^-30;  T = sum of all Q_i;
+ *   the word of draw k: words[r*K + k] when words is given, else z = seed + (r*K + k + 1) * 0x9E3779B97F4A7C15 (mod 2^64) through
+ *   the splitmix64 finaliser (z = (z ^ z>>30) * 0xBF58476D1CE4E5B9, z = (z ^ z>>27) * 0x94D049BB133111EB, word = z ^ z>>31);
+ *   target = the high 64 bits of word * T;  draw k = the smallest i with Q_0 + .. + Q_i > target;  then c_t += 1 over its span.
+ * draws[r*K + k] = the drawn event's position in the event arrays; q[r*K + k] (may be NULL) = its Q when it was drawn.
+ * FMK_E_ARG outside 1 <= m <= 2^31 - 1, 1 <= K <= 2^24, 1 <= R with R*K <= 2^40, n <= 2^32 (they keep every sum inside 64 bits and
+ * every Q positive), for draws_per_launch < 0, and for an event outside 0 <= event_idx <= touch_idx < n.  FMK_E_NOMEM when the
+ * scratch does not fit: 4 bytes per interval and per event and run, 8 more per interval and run beyond the intervals that fit in
+ * LDS (fmk_seqboot_geometry), with at most 2^32 - 1024 intervals between the span boundaries (the kernel's positions are 32-bit).
+ * The axis is compressed to the intervals between span boundaries on the HOST, inside both entry points: the _dev flavour reads the
+ * two index arrays back for it (16 bytes per event, nothing of a tape) and so waits for the stream; d_words, d_draws and d_q are
+ * device arrays.  One workgroup per run; the draws go out in launches of draws_per_launch draws each (0: the library's choice), the
+ * concurrency persists in device memory in between, and the split changes nothing in the output. */
+int fmk_sequential_bootstrap_dev(fmk_ctx *ctx, const int64_t *d_event_idx, const int64_t *d_touch_idx, int64_t n_events, int64_t n,
+                                 int64_t n_draws, int64_t n_runs, uint64_t seed, const uint64_t *d_words, int64_t draws_per_launch,
+                                 int64_t *d_draws, int64_t *d_q);
+int fmk_sequential_bootstrap(fmk_ctx *ctx, const int64_t *event_idx, const int64_t *touch_idx, int64_t n_events, int64_t n,
+                             int64_t n_draws, int64_t n_runs, uint64_t seed, const uint64_t *words, int64_t draws_per_launch,
+                             int64_t *draws, int64_t *q);
+/* The kernel's geometry, for callers that place work at its seams: out3[0] threads of a workgroup (an event or interval count past a
+ * multiple of it gives the last thread a shorter run), [1] the intervals that fit in LDS (more: the scratch flavour), [2] the draws
+ * per launch when draws_per_launch is 0.  Needs no context and no device. */
+int fmk_seqboot_geometry(int64_t *out3);
 
 /* ---- causal FIR filter on a float64 series of n elements -> float64 array of n elements (csrc/fmk_fir.hip), and with the weights
  * of feature/core/fracdiff.py the fixed-width window fractional differentiation "FFD" (Lopez de Prado, Advances in Financial
