@@ -195,6 +195,17 @@ class Context:
         """The flag as last set through this object (False after creation)."""
         return getattr(self, "_enqueue_only", False)
 
+    def set_price_grid(self, on: bool):
+        """True (default): bar_ohlcv / time_bars_ohlcv of a trade set that carries a certified price grid read its int32 column;
+        False: they read the float64 price column -- the same results bit for bit (A/B timing, tests)."""
+        self.call("fmk_ctx_set_price_grid", C.c_int(1 if on else 0))
+
+    def ohlcv_grid_launches(self) -> int:
+        """fmk_diag_ohlcv_grid_last: the kernel launches of this context's last OHLCV call that read the price grid."""
+        v = c_i64()
+        self.call("fmk_diag_ohlcv_grid_last", C.byref(v))
+        return int(v.value)
+
     def sync(self):
         self.call("fmk_ctx_sync")
 
@@ -281,6 +292,26 @@ class DeviceArray:
                 self.ctx.free(self.ptr)
         except Exception:
             pass
+
+
+class PriceGrid(C.Structure):
+    """struct fmk_price_grid (csrc/fmk_common.h): how the int32 column k of a tape becomes its price, bit for bit.  form 0: no grid,
+    1: float64(k) * r, 2: the correctly rounded quotient k / 10**d; r = the double nearest 10**-d, s = 10**d."""
+    _fields_ = [("form", C.c_int32), ("d", C.c_int32), ("r", C.c_double), ("s", C.c_double)]
+
+
+def price_grid_build(ctx: Context, price: "DeviceArray"):
+    """fmk_price_grid_build_dev on a FINAL price column: one pass, once per tape -> (k column, PriceGrid), or (None, None) when the
+    tape does not certify (the column is given back)."""
+    if price.n == 0:
+        return None, None
+    k = DeviceArray(ctx, price.n, np.int32)
+    g = PriceGrid()
+    ctx.call("fmk_price_grid_build_dev", price.p, c_i64(price.n), k.p, C.byref(g))
+    if g.form == 0:
+        k.free()
+        return None, None
+    return k, g
 
 
 FLOW_RULES = {"imbalance": 0, "run": 1}

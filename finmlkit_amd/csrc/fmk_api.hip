@@ -63,6 +63,7 @@ int fmk_ctx_create(int device, fmk_ctx **out)
     if (!c) return fmk_set_error(nullptr, FMK_E_NOMEM, "calloc");
     c->device = device;
     c->n_cu = prop.multiProcessorCount;
+    c->price_grid = 1;
 #define CK(x)                                                                              \
     do {                                                                                   \
         hipError_t e2 = (x);                                                               \
@@ -400,6 +401,12 @@ int fmk_ctx_set_fast_threshold(fmk_ctx *ctx, int on)
 int fmk_ctx_set_enqueue_only(fmk_ctx *ctx, int on)
 {
     ctx->enqueue_only = on ? 1 : 0;
+    return FMK_OK;
+}
+
+int fmk_ctx_set_price_grid(fmk_ctx *ctx, int on)
+{
+    ctx->price_grid = on ? 1 : 0;
     return FMK_OK;
 }
 

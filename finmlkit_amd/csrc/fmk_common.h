@@ -3,6 +3,7 @@
 #pragma once
 
 #include <hip/hip_runtime.h>
+#include <math.h>
 #include <stdint.h>
 #include <stdio.h>
 #include <string.h>
@@ -70,6 +71,7 @@ struct fmk_mail {
     struct Ohlcv {                         // fmk_ohlcv.hip
         int saw_long;                      // a bar longer than the small kernels take (also the pipelined step's host copy)
         int64_t span[3];                   // k_list_span: listed bars, first tick, last tick
+        unsigned long long grid_mis[2];    // k_price_grid_build: ticks whose price form A / form B does not reproduce
     } ohlcv;
     struct Bf {                            // fmk_barflow.hip
         int fu_census[3];                  // k_fu_census: min low bit, max exponent, bad
@@ -124,6 +126,9 @@ struct fmk_ctx {
     int fast_threshold;
     // 1 = calls never wait for the device where they have the choice (fmk_ctx_set_enqueue_only)
     int enqueue_only;
+    // 1 (default) = the OHLCV entry points that are handed a certified price grid read it; 0 = they take the float64 column
+    // (fmk_ctx_set_price_grid); grid_launches: the launches of the last OHLCV call that read the grid (fmk_diag_ohlcv_grid_last)
+    int price_grid, grid_launches;
     hipEvent_t kev[FMK_PROFILE_SLOTS][2];
     // stream-ordered caching allocator behind fmk_alloc / fmk_free (fmk_api.hip): freed blocks are kept and handed
     // out again to later requests of (almost) the same size -- no hipMalloc / hipFree / synchronisation per call
@@ -225,6 +230,90 @@ int fmk_long_bar_list(fmk_ctx *ctx, const int64_t *d_close_idx, int64_t nb, int6
 #define FMK_LAUNCH_CHECK(ctx) FMK_HIP(ctx, hipGetLastError())
 
 static inline int64_t fmk_ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
+
+// ---------------------------------------------------------------------------------------
+// The price grid: a tape whose every price is reproduced BIT FOR BIT from an int32 k carries k as a fifth column, and the small-bar
+// OHLCV kernel reads 4 B per tick of it instead of the 8 B of the float64 price (fmk_ohlcv.hip).  Exchange prices lie on a tick grid:
+//   form A  p = (double)k * r              the synthetic tape (fmk_synth.hip: (double)k * 0.01)
+//   form B  p = RN(k / s), s = 10^d        the nearest double to a decimal string; computed without a division as
+//           y = (double)k * r; e = fma(-y, s, (double)k); p = fma(e, r, y)   with r = RN(1 / s): one Newton step on the quotient, exact
+//           for every int32 k and d = 0 .. 8 (tools/pricegrid_check.cpp sweeps it against (double)k / s)
+// The certificate is the decode itself: fmk_price_grid_build_dev runs it on every tick and compares the bits with the price column,
+// so -0.0, NaN, infinities, an off-grid tick or a k beyond int32 refuse the tape with no special case, and a certified tape gives the
+// float64 path's results whatever the form.  Plain C++ (host and device) so that the tool can check it without a device.
+// ---------------------------------------------------------------------------------------
+#define FMK_GRID_NONE 0
+#define FMK_GRID_A 1
+#define FMK_GRID_B 2
+#define FMK_GRID_MAX_D 8
+#define FMK_GRID_SAMPLE 128                // prices the scale d is chosen from (one read-back through the mailbox)
+struct fmk_price_grid {
+    int32_t form;                          // FMK_GRID_NONE: no grid, the reducers read the float64 column
+    int32_t d;                             // s = 10^d
+    double r;                              // RN(10^-d), the double the decimal literal gives (0.01 for d = 2)
+    double s;                              // 10^d
+};
+#define FMK_GRID_HD __host__ __device__ inline
+static inline double fmk_grid_scale(int d)
+{
+    const double s[FMK_GRID_MAX_D + 1] = {1.0, 10.0, 100.0, 1000.0, 10000.0, 100000.0, 1000000.0, 10000000.0, 100000000.0};
+    return s[d];
+}
+static inline double fmk_grid_recip(int d)
+{
+    const double r[FMK_GRID_MAX_D + 1] = {1.0, 0.1, 0.01, 0.001, 0.0001, 0.00001, 0.000001, 0.0000001, 0.00000001};
+    return r[d];
+}
+template <int FORM>
+FMK_GRID_HD double fmk_grid_decode(int32_t k, double r, double s)
+{
+    const double x = (double)k;
+    const double y = x * r;
+    if (FORM == FMK_GRID_A) return y;
+    const double e = fma(-y, s, x);        // explicit: the library is built with -ffp-contract=off
+    return fma(e, r, y);
+}
+FMK_GRID_HD uint64_t fmk_grid_bits(double x) { return __builtin_bit_cast(uint64_t, x); }
+// k = the grid point next to p, false when it does not fit an int32 (NaN and the infinities fail the comparisons)
+FMK_GRID_HD bool fmk_grid_encode(double p, double s, int32_t *k)
+{
+    const double t = rint(p * s);
+    if (!(t >= -2147483648.0 && t <= 2147483647.0)) { *k = 0; return false; }
+    *k = (int32_t)t;
+    return true;
+}
+// one tick of the certificate: k (0 when out of range) and whether form A / form B give the price's bits
+FMK_GRID_HD int32_t fmk_grid_tick(double p, double r, double s, bool *ok_a, bool *ok_b)
+{
+    int32_t k;
+    const bool in = fmk_grid_encode(p, s, &k);
+    const uint64_t want = fmk_grid_bits(p);
+    *ok_a = in && fmk_grid_bits(fmk_grid_decode<FMK_GRID_A>(k, r, s)) == want;
+    *ok_b = in && fmk_grid_bits(fmk_grid_decode<FMK_GRID_B>(k, r, s)) == want;
+    return k;
+}
+// the scale: the smallest d in 0 .. 8 at which every price of the sample certifies under one of the forms; -1: none (or no sample)
+static inline int fmk_grid_choose_d(const double *sample, int64_t m)
+{
+    if (m <= 0) return -1;
+    for (int d = 0; d <= FMK_GRID_MAX_D; ++d) {
+        const double r = fmk_grid_recip(d), s = fmk_grid_scale(d);
+        int64_t mis_a = 0, mis_b = 0;
+        for (int64_t i = 0; i < m; ++i) {
+            bool a, b;
+            (void)fmk_grid_tick(sample[i], r, s, &a, &b);
+            mis_a += !a;
+            mis_b += !b;
+        }
+        if (mis_a == 0 || mis_b == 0) return d;
+    }
+    return -1;
+}
+// the form from the whole tape's mismatch counts: A where it certifies (two instructions per tick fewer), else B, else no grid
+static inline int fmk_grid_choose_form(uint64_t mis_a, uint64_t mis_b)
+{
+    return mis_a == 0 ? FMK_GRID_A : mis_b == 0 ? FMK_GRID_B : FMK_GRID_NONE;
+}
 
 // the workgroups of a 256-lane grid-stride kernel over n elements: at most 16 per CU, at least one
 static inline unsigned fmk_grid_blocks(const fmk_ctx *ctx, int64_t n)

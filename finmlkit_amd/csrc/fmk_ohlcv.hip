@@ -14,6 +14,8 @@
 //                      trip per bar instead of one per unrolled batch), and -- when the median trade size is requested
 //                      (base.py:403) -- the amounts that are already in registers feed the exact order-statistic search
 //                      of fmk_median.h directly: the amount column is read ONCE for OHLCV + median.
+//                      Where the caller hands over the tape's certified price grid (fmk_*_grid_dev; fmk_common.h) and the amounts are
+//                      float32, the 21-chunk instantiation reads the int32 grid column instead of the float64 price: 8 B/tick.
 //   the pipelined step   k_bar_ohlcv_small<.., 21> in two launches with the time-bar indexer in two stages beside them
 //                      (fmk_time_bars_ohlcv_dev on 1-minute-sized bars, float32 amounts: ohlcv_pipelined)
 //   k_bar_ohlcv_lanes<.., TILE>  one LANE per bar, streams of <= 56 (with the median: <= 32) ticks per bar, float32 amounts
@@ -509,18 +511,102 @@ __device__ __forceinline__ void small_bar(const double *__restrict__ price, cons
     }
 }
 
+// small_bar with the chunk prices from the tape's certified int32 grid column (float32 amounts; PG = FMK_GRID_A / _B, fmk_common.h):
+// one global_load_dword per chunk in place of the global_load_dwordx2 of the price, decoded in the accumulation loop to the float64
+// column's bits -- same order of operations, same results.  open and close are read from the float64 column (ohlcv_finish: two
+// elements per bar).  A function of its own so that small_bar keeps the code it had (profiles/pricegrid_isa.txt).
+template <int NCH, bool EXACT, bool MEDIAN, int PG>
+__device__ __forceinline__ void small_bar_grid(const double *__restrict__ price, const void *__restrict__ amount,
+                                               int64_t b, int64_t start, int64_t e, int64_t cnt, int lane,
+                                               uint32_t *buf, const OhlcvOut &o, const int32_t *__restrict__ kcol, double gr, double gs)
+{
+    constexpr bool AF64 = false;
+    typedef MedKey<AF64> MK;
+    typedef typename MK::K K;     // raw bit pattern type of one amount
+    // ---- issue every load of the bar: branch-free; offsets of possibly-partial chunks are clamped to the
+    //      bar's last tick (re-reads one element of a line that is fetched anyway: no extra HBM traffic)
+    const int32_t *kb = kcol + start;                    // wave-uniform bases + 32-bit lane offsets
+    const K *ab = (const K *)amount + start;
+    const unsigned last = (unsigned)(cnt - 1);
+    int32_t kq[NCH];
+    K araw[NCH];
+#pragma unroll
+    for (int c = 0; c < NCH; ++c) {
+        unsigned idx = (unsigned)(c * 64 + lane);
+        if (!EXACT || c == NCH - 1) idx = idx < last ? idx : last;
+        kq[c] = kb[idx];
+        araw[c] = ab[idx];
+    }
+    // ---- OHLCV accumulation, same per-lane order as k_bar_ohlcv
+    double hi = -INFINITY, lo = INFINITY, tv = 0.0, td = 0.0;
+    MedBar<AF64, NCH, EXACT> bar;
+#pragma unroll
+    for (int c = 0; c < NCH; ++c) {
+        const double a = (double)__uint_as_float(araw[c]);
+        // the raw word is pinned here, behind the last load: the compiler would otherwise sink the decode into each load's block
+        // (load, wait, convert: DESIGN section 3, tools/isa_loadwaits.py)
+        asm volatile("" : "+v"(kq[c]));
+        const double pc = fmk_grid_decode<PG>(kq[c], gr, gs);
+        hi = fmax(hi, pc);                               // clamped duplicates cannot change max/min
+        lo = fmin(lo, pc);
+        const double pa = pc * a;
+        if (!EXACT || c == NCH - 1) {
+            const bool valid = (unsigned)(c * 64 + lane) <= last;
+            tv += valid ? a : 0.0;
+            td += valid ? pa : 0.0;
+            if constexpr (MEDIAN) bar.key[c] = valid ? MK::tokey(araw[c]) : MK::MAXK;
+        } else {
+            tv += a;
+            td += pa;
+            if constexpr (MEDIAN) bar.key[c] = MK::tokey(araw[c]);
+        }
+    }
+    // A bar of <= 64 ticks gets the SAME sums whichever schedule serves it (a result that depended on the stream's mean bar
+    // length would make a sharded run differ from the un-sharded one in the last bit): both this kernel and k_bar_ohlcv_lanes add
+    // the 64 tick slots (0.0 beyond the bar) as the balanced binary tree of fmk_dpp_reduce -- ((x0+x1)+(x2+x3))+... in tick
+    // order.  (A first version made both add in the reference's sequential order; here that was a 64-step readlane loop per bar,
+    // 27 ms per 1e9 ticks of 60-tick bars.)
+    ohlcv_finish<AF64>(o, b, price, start, e, hi, lo, tv, td, lane);
+    if constexpr (MEDIAN) {
+        bar.amount = amount; bar.start = start; bar.cnt = cnt; bar.lane = lane;
+        const double m = med_search<AF64, NCH, EXACT>(bar, buf);
+        if (lane == 0) o.median[b] = m;
+    }
+}
+
 // MAXNCH: the longest bar the instantiation serves, in 64-tick chunks.  FMK_SMALL_NCH (21): the 1-minute-bar kernel, held to
 // four waves per SIMD by the 21-chunk class' registers.  4: streams of 65..256-tick bars -- one wave per bar pays a full memory
 // round trip per bar, so what matters there is how many bars a CU has in flight: without the long classes the kernel fits eight
 // waves per SIMD (1e9 ticks, ohlcv + median: 80-tick bars 12.0 -> 9.0 ms, 100-tick 9.9 -> 7.3, 200-tick 5.3 -> 4.1; equal at 240).
-template <bool AF64, bool MEDIAN, int MAXNCH = FMK_SMALL_NCH>
-__global__ __launch_bounds__(256, (MAXNCH <= 4 ? 8 : MAXNCH <= 10 ? 6 : 4)) void k_bar_ohlcv_small(const double *__restrict__ price,
+// PG: the price source of small_bar.  FMK_GRID_A / _B (the 21-chunk kernel on float32 amounts, the 1-minute schedule): the chunk
+// prices come from the tape's certified int32 grid column, 8 B per tick instead of 12; the grid travels as ONE trailing argument
+// (G = OhlcvGridArg).  The float64 instantiations have no such argument (an empty pack), so they keep the kernel arguments and the
+// code they had before the grid (profiles/pricegrid_isa.txt).  The grid instantiations hold one register per chunk less in flight:
+// 96 VGPRs, which fits five waves per SIMD -- measured at 1e9 ticks 1.79 ms per step against 1.97 with four
+// (profiles/pricegrid_bench.json).
+#ifndef FMK_GRID_WAVES
+#define FMK_GRID_WAVES 5
+#endif
+struct OhlcvGridArg { const int32_t *k; double r, s; };
+__device__ __forceinline__ OhlcvGridArg ohlcv_grid_arg() { return OhlcvGridArg{nullptr, 0.0, 0.0}; }
+__device__ __forceinline__ OhlcvGridArg ohlcv_grid_arg(const OhlcvGridArg &g) { return g; }
+template <bool AF64, bool MEDIAN, int MAXNCH = FMK_SMALL_NCH, int PG = FMK_GRID_NONE, typename... G>
+__global__ __launch_bounds__(256, (MAXNCH <= 4 ? 8 : MAXNCH <= 10 ? 6 : PG ? FMK_GRID_WAVES : 4)) void k_bar_ohlcv_small(const double *__restrict__ price,
                                                             const void *__restrict__ amount,
                                                             const int64_t *__restrict__ ci, int64_t nb, int64_t n,
-                                                            int *__restrict__ saw_long, OhlcvOut o)
+                                                            int *__restrict__ saw_long, OhlcvOut o, G... grid)
 {
+    static_assert(sizeof...(G) == (PG ? 1 : 0) && (!PG || (!AF64 && MAXNCH == FMK_SMALL_NCH)), "one OhlcvGridArg with a grid, none without");
     typedef typename MedKey<AF64>::K K;
     __shared__ K sbuf[4][64];
+    // (if constexpr: the float64 instantiations compile the call they always made)
+#define FMK_SMALL_BAR(N_, EXACT_)                                                                                                   \
+    do {                                                                                                                            \
+        if constexpr (PG != FMK_GRID_NONE) {                                                                                        \
+            const OhlcvGridArg ga = ohlcv_grid_arg(grid...);                                                                        \
+            small_bar_grid<N_, EXACT_, MEDIAN, PG>(price, amount, b, start, e, cnt, lane, buf, o, ga.k, ga.r, ga.s);                \
+        } else small_bar<AF64, N_, EXACT_, MEDIAN>(price, amount, b, start, e, cnt, lane, buf, o);                                  \
+    } while (0)
     const int lane = fmk_lane();
     const int wib = fmk_uniform((int)(threadIdx.x >> 6));
     const int wpb = blockDim.x >> 6;
@@ -547,47 +633,48 @@ __global__ __launch_bounds__(256, (MAXNCH <= 4 ? 8 : MAXNCH <= 10 ? 6 : 4)) void
         // exact-size code for the chunk counts a ~1200-tick (1-minute) bar takes, size classes below
         if constexpr (MAXNCH <= 4) {
             switch (nch) {
-            case 1: small_bar<AF64, 1, true, MEDIAN>(price, amount, b, start, e, cnt, lane, buf, o); break;
-            case 2: small_bar<AF64, 2, true, MEDIAN>(price, amount, b, start, e, cnt, lane, buf, o); break;
-            case 3: small_bar<AF64, 3, true, MEDIAN>(price, amount, b, start, e, cnt, lane, buf, o); break;
-            default: small_bar<AF64, 4, true, MEDIAN>(price, amount, b, start, e, cnt, lane, buf, o); break;
+            case 1: FMK_SMALL_BAR(1, true); break;
+            case 2: FMK_SMALL_BAR(2, true); break;
+            case 3: FMK_SMALL_BAR(3, true); break;
+            default: FMK_SMALL_BAR(4, true); break;
             }
         } else if constexpr (MAXNCH <= 10) {
             // exact-size code for every chunk count (full chunks need neither clamping nor predication)
             switch (nch) {
-            case 1: small_bar<AF64, 1, true, MEDIAN>(price, amount, b, start, e, cnt, lane, buf, o); break;
-            case 2: small_bar<AF64, 2, true, MEDIAN>(price, amount, b, start, e, cnt, lane, buf, o); break;
-            case 3: small_bar<AF64, 3, true, MEDIAN>(price, amount, b, start, e, cnt, lane, buf, o); break;
-            case 4: small_bar<AF64, 4, true, MEDIAN>(price, amount, b, start, e, cnt, lane, buf, o); break;
-            case 5: small_bar<AF64, 5, true, MEDIAN>(price, amount, b, start, e, cnt, lane, buf, o); break;
-            case 6: small_bar<AF64, 6, true, MEDIAN>(price, amount, b, start, e, cnt, lane, buf, o); break;
-            case 7: small_bar<AF64, 7, true, MEDIAN>(price, amount, b, start, e, cnt, lane, buf, o); break;
-            case 8: small_bar<AF64, 8, true, MEDIAN>(price, amount, b, start, e, cnt, lane, buf, o); break;
-            case 9: small_bar<AF64, 9, true, MEDIAN>(price, amount, b, start, e, cnt, lane, buf, o); break;
-            default: small_bar<AF64, 10, true, MEDIAN>(price, amount, b, start, e, cnt, lane, buf, o); break;
+            case 1: FMK_SMALL_BAR(1, true); break;
+            case 2: FMK_SMALL_BAR(2, true); break;
+            case 3: FMK_SMALL_BAR(3, true); break;
+            case 4: FMK_SMALL_BAR(4, true); break;
+            case 5: FMK_SMALL_BAR(5, true); break;
+            case 6: FMK_SMALL_BAR(6, true); break;
+            case 7: FMK_SMALL_BAR(7, true); break;
+            case 8: FMK_SMALL_BAR(8, true); break;
+            case 9: FMK_SMALL_BAR(9, true); break;
+            default: FMK_SMALL_BAR(10, true); break;
             }
         } else {
             switch (nch) {
-            case 11: small_bar<AF64, 11, true, MEDIAN>(price, amount, b, start, e, cnt, lane, buf, o); break;
-            case 12: small_bar<AF64, 12, true, MEDIAN>(price, amount, b, start, e, cnt, lane, buf, o); break;
-            case 13: small_bar<AF64, 13, true, MEDIAN>(price, amount, b, start, e, cnt, lane, buf, o); break;
-            case 14: small_bar<AF64, 14, true, MEDIAN>(price, amount, b, start, e, cnt, lane, buf, o); break;
-            case 15: small_bar<AF64, 15, true, MEDIAN>(price, amount, b, start, e, cnt, lane, buf, o); break;
-            case 16: small_bar<AF64, 16, true, MEDIAN>(price, amount, b, start, e, cnt, lane, buf, o); break;
-            case 17: small_bar<AF64, 17, true, MEDIAN>(price, amount, b, start, e, cnt, lane, buf, o); break;
-            case 18: small_bar<AF64, 18, true, MEDIAN>(price, amount, b, start, e, cnt, lane, buf, o); break;
-            case 19: small_bar<AF64, 19, true, MEDIAN>(price, amount, b, start, e, cnt, lane, buf, o); break;
-            case 20: small_bar<AF64, 20, true, MEDIAN>(price, amount, b, start, e, cnt, lane, buf, o); break;
-            case 21: small_bar<AF64, 21, true, MEDIAN>(price, amount, b, start, e, cnt, lane, buf, o); break;
+            case 11: FMK_SMALL_BAR(11, true); break;
+            case 12: FMK_SMALL_BAR(12, true); break;
+            case 13: FMK_SMALL_BAR(13, true); break;
+            case 14: FMK_SMALL_BAR(14, true); break;
+            case 15: FMK_SMALL_BAR(15, true); break;
+            case 16: FMK_SMALL_BAR(16, true); break;
+            case 17: FMK_SMALL_BAR(17, true); break;
+            case 18: FMK_SMALL_BAR(18, true); break;
+            case 19: FMK_SMALL_BAR(19, true); break;
+            case 20: FMK_SMALL_BAR(20, true); break;
+            case 21: FMK_SMALL_BAR(21, true); break;
             default:
-                if (nch <= 1) small_bar<AF64, 1, true, MEDIAN>(price, amount, b, start, e, cnt, lane, buf, o);
-                else if (nch <= 4) small_bar<AF64, 4, false, MEDIAN>(price, amount, b, start, e, cnt, lane, buf, o);
-                else if (nch <= 10) small_bar<AF64, 10, false, MEDIAN>(price, amount, b, start, e, cnt, lane, buf, o);
-                else small_bar<AF64, 16, false, MEDIAN>(price, amount, b, start, e, cnt, lane, buf, o);
+                if (nch <= 1) FMK_SMALL_BAR(1, true);
+                else if (nch <= 4) FMK_SMALL_BAR(4, false);
+                else if (nch <= 10) FMK_SMALL_BAR(10, false);
+                else FMK_SMALL_BAR(16, false);
             }
         }
     }
 }
+#undef FMK_SMALL_BAR
 
 // ---------------------------------------------------------------------------------------------------------------------
 // The time-bar step in one call (fmk_time_bars_ohlcv_dev): what the indexer stages need to know.  (Round 4 also had the clock-edge
@@ -1525,27 +1612,41 @@ extern "C" int fmk_diag_ohlcv_plan(int64_t n, int64_t n_bars, int amount_is_f64,
     return FMK_OK;
 }
 
+// a tape's certified price grid as the launches take it (fmk_common.h); none: a null pointer
+struct OhlcvGrid { const int32_t *k; fmk_price_grid g; };
+
 // The one place where a plan becomes a kernel instantiation (`grid`: the plan's, or the second stage's of the pipelined step).
+// pg: the price grid, read by the 21-chunk kernel on float32 amounts; every other schedule reads the float64 column.
+// -> 1 if the launch reads the grid, else 0.
 template <bool AF64, bool MEDIAN>
-static void ohlcv_first_pass(const OhlcvPlan &pl, unsigned grid, hipStream_t st, const double *p, const void *a, const int64_t *ci,
-                             int64_t nb, int64_t n, int *saw_long, const OhlcvOut &o)
+static int ohlcv_first_pass(const OhlcvPlan &pl, unsigned grid, hipStream_t st, const double *p, const void *a, const int64_t *ci,
+                            int64_t nb, int64_t n, int *saw_long, const OhlcvOut &o, const OhlcvGrid *pg = nullptr)
 {
     if constexpr (!AF64) {
         const float *af = (const float *)a;
         if (pl.kind == OHLCV_ROWS && pl.lanes == 8) {                // (planned with the median only)
             if constexpr (MEDIAN) k_bar_ohlcv_rows<true, 8><<<grid, pl.block, 0, st>>>(p, af, ci, nb, n, saw_long, o);
-            return;
+            return 0;
         }
-        if (pl.kind == OHLCV_ROWS) { k_bar_ohlcv_rows<MEDIAN><<<grid, pl.block, 0, st>>>(p, af, ci, nb, n, saw_long, o); return; }
+        if (pl.kind == OHLCV_ROWS) { k_bar_ohlcv_rows<MEDIAN><<<grid, pl.block, 0, st>>>(p, af, ci, nb, n, saw_long, o); return 0; }
         if (pl.kind == OHLCV_LANES) {
             if (pl.tile == 2048) k_bar_ohlcv_lanes<MEDIAN, 2048><<<grid, pl.block, 0, st>>>(p, af, ci, nb, n, saw_long, o);
             else k_bar_ohlcv_lanes<MEDIAN, 1024><<<grid, pl.block, 0, st>>>(p, af, ci, nb, n, saw_long, o);
-            return;
+            return 0;
+        }
+        if (pg && pl.nch == FMK_SMALL_NCH) {
+            const OhlcvGridArg ga{pg->k, pg->g.r, pg->g.s};
+            if (pg->g.form == FMK_GRID_A)
+                k_bar_ohlcv_small<false, MEDIAN, FMK_SMALL_NCH, FMK_GRID_A, OhlcvGridArg><<<grid, pl.block, 0, st>>>(p, a, ci, nb, n, saw_long, o, ga);
+            else
+                k_bar_ohlcv_small<false, MEDIAN, FMK_SMALL_NCH, FMK_GRID_B, OhlcvGridArg><<<grid, pl.block, 0, st>>>(p, a, ci, nb, n, saw_long, o, ga);
+            return 1;
         }
     }
     if (pl.nch == 4) k_bar_ohlcv_small<AF64, MEDIAN, 4><<<grid, pl.block, 0, st>>>(p, a, ci, nb, n, saw_long, o);
     else if (pl.nch == 10) k_bar_ohlcv_small<AF64, MEDIAN, 10><<<grid, pl.block, 0, st>>>(p, a, ci, nb, n, saw_long, o);
     else k_bar_ohlcv_small<AF64, MEDIAN><<<grid, pl.block, 0, st>>>(p, a, ci, nb, n, saw_long, o);
+    return 0;
 }
 
 // float32 bars of 1 345 .. 2 048, .. 3 072, .. 4 096, .. 6 144 ticks: a wave per bar with 32 / 48 / 64 / 96 key registers; 6 145 .. 8 192
@@ -1613,7 +1714,7 @@ static int ohlcv_leftovers(fmk_ctx *ctx, const double *p, const void *a, const i
 // longer than 1 344 ticks?), so the flag reaches the host while the first OHLCV launch is still running: the call decides about the
 // leftover passes and returns without ever waiting for a kernel it launched.
 static int ohlcv_pipelined(fmk_ctx *ctx, const OhlcvPlan &pl, const double *p, const void *a, int64_t nb, int64_t n, const OhlcvOut &o,
-                           const TbFuse *tb)
+                           const TbFuse *tb, const OhlcvGrid *pg)
 {
     const int idx_bpc = 2;                 // workgroups per CU of the second index stage (0: no cap)
     int *saw_long = &ctx->d_mail->ohlcv.saw_long, *h_saw = &ctx->h_mail->ohlcv.saw_long;
@@ -1641,8 +1742,8 @@ static int ohlcv_pipelined(fmk_ctx *ctx, const OhlcvPlan &pl, const double *p, c
             const int sl = (ctx->profile_on) ? (ctx->profile_n++ & (FMK_PROFILE_SLOTS - 1)) : -1;      // each launch of the dominant kernel on its own
             if (sl >= 0) FMK_HIP(ctx, hipEventRecord(ctx->kev[sl][0], ctx->stream));
             const unsigned g = stage ? ohlcv_grid(ctx, cnt) : pl.grid;
-            if (o.median) ohlcv_first_pass<false, true>(pl, g, ctx->stream, p, a, ci + b0, cnt, n, saw_long, q);
-            else ohlcv_first_pass<false, false>(pl, g, ctx->stream, p, a, ci + b0, cnt, n, saw_long, q);
+            if (o.median) ctx->grid_launches += ohlcv_first_pass<false, true>(pl, g, ctx->stream, p, a, ci + b0, cnt, n, saw_long, q, pg);
+            else ctx->grid_launches += ohlcv_first_pass<false, false>(pl, g, ctx->stream, p, a, ci + b0, cnt, n, saw_long, q, pg);
             FMK_LAUNCH_CHECK(ctx);
             if (sl >= 0) FMK_HIP(ctx, hipEventRecord(ctx->kev[sl][1], ctx->stream));
         }
@@ -1656,9 +1757,10 @@ static int ohlcv_pipelined(fmk_ctx *ctx, const OhlcvPlan &pl, const double *p, c
 // kernel in two stages (ohlcv_pipelined), every other schedule runs the separate indexer first
 template <bool AF64>
 static int ohlcv_launch(fmk_ctx *ctx, const double *p, const void *a, const int64_t *ci, int64_t nb, int64_t n,
-                        const OhlcvOut &o_in, const TbFuse *tb = nullptr)
+                        const OhlcvOut &o_in, const TbFuse *tb = nullptr, const OhlcvGrid *pg = nullptr)
 {
     OhlcvOut o = o_in;
+    ctx->grid_launches = 0;
     const char *msv = tb ? getenv("FMK_TB_PIPE_MIN_STAGE") : nullptr;   // developer knob (tests), read on every time-bar call
     const OhlcvPlan pl = ohlcv_plan(n, nb, AF64, o.median != nullptr, tb != nullptr, ctx->n_cu, msv ? atoll(msv) : OHLCV_PIPE_MIN_STAGE);
     if (tb) {
@@ -1670,14 +1772,14 @@ static int ohlcv_launch(fmk_ctx *ctx, const double *p, const void *a, const int6
         FMK_HIP(ctx, hipMemsetAsync(o.vol_redo, 0, FMK_BAR_LIST_CLEAR, ctx->stream));
     }
     if constexpr (!AF64)
-        if (pl.kind == OHLCV_PIPELINED) return ohlcv_pipelined(ctx, pl, p, a, nb, n, o, tb);
+        if (pl.kind == OHLCV_PIPELINED) return ohlcv_pipelined(ctx, pl, p, a, nb, n, o, tb, pg);
     // time the dominant launch only (the one-bar boundary launch of a sharded step is not it)
     const int slot = (ctx->profile_on && nb >= 64) ? (ctx->profile_n++ & (FMK_PROFILE_SLOTS - 1)) : -1;
     if (slot >= 0) FMK_HIP(ctx, hipEventRecord(ctx->kev[slot][0], ctx->stream));
     int *saw_long = &ctx->d_mail->ohlcv.saw_long;            // set by the first kernel iff it left a bar behind
     FMK_HIP(ctx, hipMemsetAsync(saw_long, 0, sizeof(int), ctx->stream));
-    if (o.median) ohlcv_first_pass<AF64, true>(pl, pl.grid, ctx->stream, p, a, ci, nb, n, saw_long, o);
-    else ohlcv_first_pass<AF64, false>(pl, pl.grid, ctx->stream, p, a, ci, nb, n, saw_long, o);
+    if (o.median) ctx->grid_launches += ohlcv_first_pass<AF64, true>(pl, pl.grid, ctx->stream, p, a, ci, nb, n, saw_long, o, pg);
+    else ctx->grid_launches += ohlcv_first_pass<AF64, false>(pl, pl.grid, ctx->stream, p, a, ci, nb, n, saw_long, o, pg);
     FMK_LAUNCH_CHECK(ctx);
     if (slot >= 0) FMK_HIP(ctx, hipEventRecord(ctx->kev[slot][1], ctx->stream));
     // Everything below serves the bars the first kernel left behind -- six list kernels, six size classes, the generic kernel, the
@@ -1735,19 +1837,42 @@ int fmk_median_small_ohlcv_long_launch(fmk_ctx *ctx, const double *p, const floa
     return ohlcv_leftovers<false>(ctx, p, a, ci, nb, n, o, saw_long, 64 * FMK_SMALL_NCH, ohlcv_grid(ctx, nb));
 }
 
+// the grid a call may read: the caller handed one over, it certifies, the amounts are float32 and the context has not switched it off
+static const OhlcvGrid *ohlcv_grid_of(const fmk_ctx *ctx, OhlcvGrid *hold, const int32_t *d_k, const fmk_price_grid *grid, int amount_is_f64)
+{
+    if (!ctx->price_grid || !d_k || !grid || amount_is_f64) return nullptr;
+    if (grid->form != FMK_GRID_A && grid->form != FMK_GRID_B) return nullptr;
+    hold->k = d_k;
+    hold->g = *grid;
+    return hold;
+}
+
 extern "C" int fmk_comp_bar_ohlcv_dev(fmk_ctx *ctx, const double *d_price, const void *d_amount,
                                       int amount_is_f64, int64_t n, const int64_t *d_close_idx, int64_t n_idx,
                                       double *d_open, double *d_high, double *d_low, double *d_close,
                                       float *d_volume, double *d_vwap, int64_t *d_trades, double *d_median)
 {
+    return fmk_comp_bar_ohlcv_grid_dev(ctx, d_price, d_amount, amount_is_f64, n, d_close_idx, n_idx, d_open, d_high, d_low, d_close,
+                                       d_volume, d_vwap, d_trades, d_median, nullptr, nullptr);
+}
+
+extern "C" int fmk_comp_bar_ohlcv_grid_dev(fmk_ctx *ctx, const double *d_price, const void *d_amount,
+                                           int amount_is_f64, int64_t n, const int64_t *d_close_idx, int64_t n_idx,
+                                           double *d_open, double *d_high, double *d_low, double *d_close,
+                                           float *d_volume, double *d_vwap, int64_t *d_trades, double *d_median,
+                                           const int32_t *d_k, const fmk_price_grid *grid)
+{
+    ctx->grid_launches = 0;
     if (n_idx < 2)   // base.py:334-335
         return fmk_set_error(ctx, FMK_E_ARG, "Bar close indices must contain at least two elements.");
     if (n <= 0) return fmk_set_error(ctx, FMK_E_ARG, "comp_bar_ohlcv: empty price array");
     FMK_HIP(ctx, hipSetDevice(ctx->device));
     const int64_t nb = n_idx - 1;
     OhlcvOut o{d_open, d_high, d_low, d_close, d_volume, d_vwap, d_trades, d_median, nullptr};
+    OhlcvGrid hold;
     return amount_is_f64 ? ohlcv_launch<true>(ctx, d_price, d_amount, d_close_idx, nb, n, o)
-                         : ohlcv_launch<false>(ctx, d_price, d_amount, d_close_idx, nb, n, o);
+                         : ohlcv_launch<false>(ctx, d_price, d_amount, d_close_idx, nb, n, o, nullptr,
+                                               ohlcv_grid_of(ctx, &hold, d_k, grid, amount_is_f64));
 }
 
 // _time_bar_indexer + comp_bar_ohlcv in one call (TimeBarKit.build_ohlcv on resident columns; bench.py's step): the results of
@@ -1759,6 +1884,18 @@ extern "C" int fmk_time_bars_ohlcv_dev(fmk_ctx *ctx, const int64_t *d_ts, const 
                                        double *d_high, double *d_low, double *d_close, float *d_volume, double *d_vwap,
                                        int64_t *d_trades, double *d_median)
 {
+    return fmk_time_bars_ohlcv_grid_dev(ctx, d_ts, d_price, d_amount, amount_is_f64, n, ts_first, ts_last, first_edge, delta, n_edges,
+                                        d_clock, d_close_idx, d_open, d_high, d_low, d_close, d_volume, d_vwap, d_trades, d_median,
+                                        nullptr, nullptr);
+}
+
+extern "C" int fmk_time_bars_ohlcv_grid_dev(fmk_ctx *ctx, const int64_t *d_ts, const double *d_price, const void *d_amount,
+                                            int amount_is_f64, int64_t n, int64_t ts_first, int64_t ts_last, int64_t first_edge,
+                                            int64_t delta, int64_t n_edges, int64_t *d_clock, int64_t *d_close_idx, double *d_open,
+                                            double *d_high, double *d_low, double *d_close, float *d_volume, double *d_vwap,
+                                            int64_t *d_trades, double *d_median, const int32_t *d_k, const fmk_price_grid *grid)
+{
+    ctx->grid_launches = 0;
     if (n <= 0) return fmk_set_error(ctx, FMK_E_ARG, "time_bars_ohlcv: empty input");
     if (n_edges < 2)   // base.py:334-335
         return fmk_set_error(ctx, FMK_E_ARG, "Bar close indices must contain at least two elements.");
@@ -1767,6 +1904,71 @@ extern "C" int fmk_time_bars_ohlcv_dev(fmk_ctx *ctx, const int64_t *d_ts, const 
     const int64_t nb = n_edges - 1;
     OhlcvOut o{d_open, d_high, d_low, d_close, d_volume, d_vwap, d_trades, d_median, nullptr};
     const TbFuse tb{d_ts, first_edge, delta, ts_first, ts_last, d_clock, d_close_idx};
+    OhlcvGrid hold;
     return amount_is_f64 ? ohlcv_launch<true>(ctx, d_price, d_amount, d_close_idx, nb, n, o, &tb)
-                         : ohlcv_launch<false>(ctx, d_price, d_amount, d_close_idx, nb, n, o, &tb);
+                         : ohlcv_launch<false>(ctx, d_price, d_amount, d_close_idx, nb, n, o, &tb,
+                                               ohlcv_grid_of(ctx, &hold, d_k, grid, amount_is_f64));
+}
+
+// the launches of the context's last OHLCV call that read the price grid (0: the call took the float64 column throughout)
+extern "C" int fmk_diag_ohlcv_grid_last(fmk_ctx *ctx, int64_t *launches)
+{
+    *launches = ctx->grid_launches;
+    return FMK_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// The price grid of a tape (fmk_common.h), made once where the tape is made: the scale from a sample, then ONE pass that writes
+// k = rint(p * 10^d) for every tick and counts the ticks each form fails to reproduce.  8 B read + 4 B written per tick.
+// ---------------------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void k_price_grid_sample(const double *__restrict__ price, int64_t n, int64_t m, double *__restrict__ out)
+{
+    const int64_t i = threadIdx.x;
+    if (i < m) out[i] = price[i == m - 1 ? n - 1 : i * (n / m)];       // evenly spread, the tape's first and last tick among them
+}
+
+__global__ __launch_bounds__(256) void k_price_grid_build(const double *__restrict__ price, int64_t n, double r, double s,
+                                                          int32_t *__restrict__ kcol, unsigned long long *__restrict__ mis)
+{
+    unsigned long long bad_a = 0, bad_b = 0;
+    const int64_t stride = (int64_t)gridDim.x * 256;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += stride) {
+        bool ok_a, ok_b;
+        kcol[i] = fmk_grid_tick(price[i], r, s, &ok_a, &ok_b);
+        bad_a += !ok_a;
+        bad_b += !ok_b;
+    }
+    bad_a = fmk_wave_sum(bad_a);
+    bad_b = fmk_wave_sum(bad_b);
+    if (fmk_lane() == 0) {
+        if (bad_a) atomicAdd(&mis[0], bad_a);
+        if (bad_b) atomicAdd(&mis[1], bad_b);
+    }
+}
+
+extern "C" int fmk_price_grid_build_dev(fmk_ctx *ctx, const double *d_price, int64_t n, int32_t *d_k, fmk_price_grid *grid)
+{
+    if (!grid) return fmk_set_error(ctx, FMK_E_ARG, "price_grid_build: grid is required");
+    *grid = fmk_price_grid{FMK_GRID_NONE, 0, 0.0, 0.0};
+    if (n < 0) return fmk_set_error(ctx, FMK_E_ARG, "price_grid_build: negative length");
+    if (n == 0) return FMK_OK;                                          // an empty tape has nothing to certify and no column to read
+    if (!d_price || !d_k) return fmk_set_error(ctx, FMK_E_ARG, "price_grid_build: a null column");
+    FMK_HIP(ctx, hipSetDevice(ctx->device));
+    const int64_t m = n < FMK_GRID_SAMPLE ? n : FMK_GRID_SAMPLE;
+    double sample[FMK_GRID_SAMPLE], *d_sample = nullptr;
+    FMK_TRY(fmk_scratch(ctx, sizeof sample, (void **)&d_sample));
+    k_price_grid_sample<<<1, 256, 0, ctx->stream>>>(d_price, n, m, d_sample);
+    FMK_LAUNCH_CHECK(ctx);
+    FMK_TRY(fmk_read_back(ctx, sample, d_sample, (size_t)m * sizeof(double)));
+    const int d = fmk_grid_choose_d(sample, m);
+    if (d < 0) return FMK_OK;
+    const double r = fmk_grid_recip(d), s = fmk_grid_scale(d);
+    unsigned long long *d_mis = ctx->d_mail->ohlcv.grid_mis, mis[2];
+    FMK_HIP(ctx, hipMemsetAsync(d_mis, 0, sizeof mis, ctx->stream));
+    k_price_grid_build<<<fmk_grid_blocks(ctx, n), 256, 0, ctx->stream>>>(d_price, n, r, s, d_k, d_mis);
+    FMK_LAUNCH_CHECK(ctx);
+    FMK_TRY(fmk_read_back(ctx, mis, d_mis, sizeof mis));
+    const int form = fmk_grid_choose_form(mis[0], mis[1]);
+    if (form != FMK_GRID_NONE) *grid = fmk_price_grid{form, d, r, s};
+    return FMK_OK;
 }

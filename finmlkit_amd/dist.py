@@ -204,7 +204,9 @@ class ShardedTimeBars:
                  with_side: bool = False, self_loop: bool = False):
         import numpy as np
         from ._ffi import DeviceArray
-        self.t, self.rank, self.world = trades, rank, world
+        # the sharded step reads the float64 price column: the boundary bar's columns are assembled per step (halo + shard head), so
+        # they have no certified grid, and the interior keeps the same path as the boundary (a follow-up)
+        self.t, self.rank, self.world = trades.without_grid(), rank, world
         self.interval, self.want_median = float(interval_seconds), want_median
         self.with_side = with_side and trades.side is not None
         self.self_loop = self_loop and world == 1

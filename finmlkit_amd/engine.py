@@ -37,6 +37,9 @@ class DeviceTrades:
         self._side_host = None
         self.n = price.n
         self.amount_is_f64 = int(amount.dtype == np.float64)
+        # the tape's certified int32 price grid (csrc/fmk_common.h): set by the constructors that know the price column is final
+        # (from_numpy, synth without head-room) and carried by place(); a hand-built trade set and a with_halo view have none
+        self.price_k, self.price_grid = None, None
 
     @property
     def side(self) -> Optional[DeviceArray]:
@@ -65,7 +68,12 @@ class DeviceTrades:
         t = cls(ctx, dev[0], dev[1], dev[2], dev[3] if len(dev) > 3 else None)
         if sd is not None and lazy_side:
             t._side_host = sd                     # a reference to the caller's column (or its int8 copy); uploaded on first use
+        t._build_price_grid()
         return t
+
+    def _build_price_grid(self):
+        """One pass over the FINAL price column, once per tape: the int32 grid column, where every price certifies."""
+        self.price_k, self.price_grid = _ffi.price_grid_build(self.ctx, self.price)
 
     @classmethod
     def synth(cls, n: int, seed: int = 42, first: int = 0, gap_mod: int = DENSE_GAP_MOD,
@@ -92,6 +100,8 @@ class DeviceTrades:
         t = cls(ctx, *v)
         t._backing = cols if into is None else []
         t._headroom = headroom
+        if headroom == 0:                         # (a shard's halo elements are written later: its price column is not final)
+            t._build_price_grid()
         return t
 
     # ------------------------------------------------------------------ placement (opt-in)
@@ -114,6 +124,8 @@ class DeviceTrades:
             raise ValueError("place(): this trade set has head-room for a halo in front of its columns (a shard); the placed copy "
                              "would lose it -- place the columns before sharding")
         cols = [c for c in (self.ts, self.price, self.amount, self.side) if c is not None]
+        if self.price_k is not None:              # the grid column travels with the others: every position is probed alike
+            cols.append(self.price_k)
         span = sum((c.nbytes + (2 << 20) - 1) // (2 << 20) * (2 << 20) for c in cols)
         span = (span + (1 << 30) - 1) // (1 << 30) * (1 << 30)
         # positions 1 .. P-1 lie every `step` bytes of ONE slab (they may overlap: one copy lives at a time, the best is copied again
@@ -148,10 +160,12 @@ class DeviceTrades:
                 o += (c.nbytes + (2 << 20) - 1) // (2 << 20) * (2 << 20)
             for src, dst in zip(cols, out):
                 ctx.call("fmk_d2d", dst.p, src.p, C.c_size_t(src.nbytes))
+            k = out.pop() if self.price_k is not None else None
             if self.side is None:
                 out.append(None)
             t = DeviceTrades(ctx, *out)
             t._first_last = getattr(self, "_first_last", None)
+            t.price_k, t.price_grid = k, (self.price_grid if k is not None else None)
             return t
 
         ms, offs = [timed(self)], [None]
@@ -164,6 +178,15 @@ class DeviceTrades:
         if chosen is not self:
             chosen._placement_keep = (slab, self)
         return chosen, {"probe_ms": ms, "offset_gib": [None if o is None else o / float(1 << 30) for o in offs], "chosen": best}
+
+    def without_grid(self) -> "DeviceTrades":
+        """The same columns (no copy) as a trade set that carries no price grid: its reducers read the float64 price column."""
+        if self.price_k is None:
+            return self
+        import copy
+        t = copy.copy(self)
+        t.price_k, t.price_grid = None, None
+        return t
 
     def with_halo(self, k: int) -> "DeviceTrades":
         """View that also covers the k elements in front of the shard (already filled by the caller)."""
@@ -230,11 +253,17 @@ class DeviceTrades:
             clock, idx = DeviceArray(self.ctx, ne, np.int64), DeviceArray(self.ctx, ne, np.int64)
         out = out or self.alloc_ohlcv(max(ne - 1, 0), want_median)
         med = out["median_trade_size"].p if (want_median and "median_trade_size" in out) else None
-        self.ctx.call("fmk_time_bars_ohlcv_dev", self.ts.p, self.price.p, self.amount.p, C.c_int(self.amount_is_f64),
+        grid = self._grid_args()
+        self.ctx.call("fmk_time_bars_ohlcv" + ("_grid_dev" if grid else "_dev"), self.ts.p, self.price.p, self.amount.p,
+                      C.c_int(self.amount_is_f64),
                       c_i64(self.n), c_i64(t0), c_i64(t1), c_i64(e0), c_i64(d), c_i64(ne), clock.p, idx.p,
                       out["open"].p, out["high"].p, out["low"].p, out["close"].p, out["volume"].p, out["vwap"].p,
-                      out["trades"].p, med)
+                      out["trades"].p, med, *grid)
         return clock, idx, out
+
+    def _grid_args(self):
+        """The two extra arguments of the *_grid_dev entry points; empty without a certified grid."""
+        return () if self.price_k is None else (self.price_k.p, C.byref(self.price_grid))
 
     def tick_bar_index(self, threshold: int) -> DeviceArray:
         m = c_i64()
@@ -295,9 +324,11 @@ class DeviceTrades:
         nb = close_idx.n - 1
         out = out or self.alloc_ohlcv(max(nb, 0), want_median)
         med = out["median_trade_size"].p if (want_median and "median_trade_size" in out) else None
-        self.ctx.call("fmk_comp_bar_ohlcv_dev", self.price.p, self.amount.p, C.c_int(self.amount_is_f64),
+        grid = self._grid_args()
+        self.ctx.call("fmk_comp_bar_ohlcv" + ("_grid_dev" if grid else "_dev"), self.price.p, self.amount.p,
+                      C.c_int(self.amount_is_f64),
                       c_i64(self.n), close_idx.p, c_i64(close_idx.n), out["open"].p, out["high"].p,
-                      out["low"].p, out["close"].p, out["volume"].p, out["vwap"].p, out["trades"].p, med)
+                      out["low"].p, out["close"].p, out["volume"].p, out["vwap"].p, out["trades"].p, med, *grid)
         return out
 
     def bar_median(self, close_idx: DeviceArray, out: DeviceArray) -> DeviceArray:

@@ -111,6 +111,10 @@ int fmk_ctx_set_fast_threshold(fmk_ctx *ctx, int on);
  * the device never idles for it) instead of enqueuing the ~36 launches blindly -- 0.25 ms per sharded step (FMK_TB_PIPE_EO_CENSUS=0
  * restores the blind enqueue).  A call whose tick array is no longer than the first kernel's reach enqueues nothing more either way. */
 int fmk_ctx_set_enqueue_only(fmk_ctx *ctx, int on);
+/* Price grid.  on = 1 (default): fmk_comp_bar_ohlcv_grid_dev / fmk_time_bars_ohlcv_grid_dev read the int32 grid column they are
+ * handed where a kernel can; on = 0: they read the float64 price column like the entry points without a grid -- the same results bit
+ * for bit, for A/B timing and for tests on one object. */
+int fmk_ctx_set_price_grid(fmk_ctx *ctx, int on);
 int fmk_profile_enable(fmk_ctx *ctx, int on);
 int fmk_profile_read(fmk_ctx *ctx, double *ms, int capacity, int *count);
 int fmk_profile_count(fmk_ctx *ctx, int64_t *total);   /* launches timed since enable (> 256: the ring holds the last 256, oldest at slot total mod 256) */
@@ -178,6 +182,30 @@ int fmk_time_bars_ohlcv_dev(fmk_ctx *ctx, const int64_t *d_ts, const double *d_p
                             int64_t delta, int64_t n_edges, int64_t *d_clock, int64_t *d_close_idx,
                             double *d_open, double *d_high, double *d_low, double *d_close, float *d_volume,
                             double *d_vwap, int64_t *d_trades, double *d_median);
+/* ---- the price grid of a tape ---------------------------------------------------------- */
+/* Exchange prices lie on a tick grid.  Where EVERY price of a tape is reproduced bit for bit from an int32 k -- form 1: (double)k * r,
+ * form 2: the correctly rounded quotient k / 10^d -- the tape can carry k as a fifth column and the 1-minute OHLCV kernel reads 4 B
+ * per tick of it instead of the 8 B of the price.  struct fmk_price_grid { int32_t form; int32_t d; double r; double s; } (form 0: no
+ * grid; r = the double nearest 10^-d, s = 10^d; csrc/fmk_common.h, next to the decode).
+ * fmk_price_grid_build_dev: one pass over the price column, once per tape (8 B read + 4 B written per tick): picks d in 0 .. 8 from
+ * a sample, writes d_k[n] and certifies it by running the decode on every tick.  *grid comes back with form 0 when the tape does not
+ * certify (a NaN, an infinity, -0.0, one off-grid tick, |k| >= 2^31): d_k is then of no use and the caller frees it.  Waits. */
+typedef struct fmk_price_grid fmk_price_grid;
+int fmk_price_grid_build_dev(fmk_ctx *ctx, const double *d_price, int64_t n, int32_t *d_k, fmk_price_grid *grid);
+/* fmk_comp_bar_ohlcv_dev / fmk_time_bars_ohlcv_dev with the tape's grid (d_k and grid from fmk_price_grid_build_dev on this very
+ * d_price[n]; both NULL, or form 0: no grid): the same results bit for bit.  The grid is read by the 1-minute schedule on float32
+ * amounts; bars beyond 1 344 ticks, open / close and every other schedule read d_price. */
+int fmk_comp_bar_ohlcv_grid_dev(fmk_ctx *ctx, const double *d_price, const void *d_amount,
+                                int amount_is_f64, int64_t n, const int64_t *d_close_idx,
+                                int64_t n_idx, double *d_open, double *d_high, double *d_low,
+                                double *d_close, float *d_volume, double *d_vwap, int64_t *d_trades,
+                                double *d_median, const int32_t *d_k, const fmk_price_grid *grid);
+int fmk_time_bars_ohlcv_grid_dev(fmk_ctx *ctx, const int64_t *d_ts, const double *d_price, const void *d_amount,
+                                 int amount_is_f64, int64_t n, int64_t ts_first, int64_t ts_last, int64_t first_edge,
+                                 int64_t delta, int64_t n_edges, int64_t *d_clock, int64_t *d_close_idx,
+                                 double *d_open, double *d_high, double *d_low, double *d_close, float *d_volume,
+                                 double *d_vwap, int64_t *d_trades, double *d_median, const int32_t *d_k,
+                                 const fmk_price_grid *grid);
 /* The order statistic alone (np.median of the bar's trade sizes, base.py:373-403). */
 int fmk_comp_bar_median_dev(fmk_ctx *ctx, const void *d_amount, int amount_is_f64, int64_t n,
                             const int64_t *d_close_idx, int64_t n_idx, double *d_median);

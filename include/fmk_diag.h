@@ -120,6 +120,9 @@ int fmk_diag_cusum_onepass(int64_t *used, int64_t *fix_launches, int64_t *pendin
 /* the last fmk_triple_barrier[_dev] call on this context: {schedule (0 every tick walked, 1 the block tables), events, events skipped (no tick in
  * their window), blocks opened by the table schedule, ticks walked}; waits for the context's stream */
 int fmk_diag_label_last(fmk_ctx *ctx, int64_t *out5);
+/* the context's last fmk_comp_bar_ohlcv[_grid]_dev / fmk_time_bars_ohlcv[_grid]_dev call: the kernel launches that read the tape's
+ * int32 price grid (0: every launch read the float64 price column; the pipelined time-bar step makes two) */
+int fmk_diag_ohlcv_grid_last(fmk_ctx *ctx, int64_t *launches);
 /* last fmk_cusum_filter[_dev] call of this process: the form that answered (0 pass A + the wave-per-chunk fix-up, 1 the
  * lane-per-chunk re-walk took over), launches after pass A (fix-ups and re-walks), the chunks that had not merged within the first
  * fix-up launch's limit, the number of chunks */
