@@ -1,6 +1,8 @@
 """CPU-only checks of the imbalance / run bar indexers: the defining loops (tests/_flowbars_ref.py) on hand-written tapes whose closes
 are written out, the identity the GPU tests lean on (a stretch of side-0 ticks changes no state), the host restatement of the
-certificate, the C ABI's declarations and exports, and the argument errors that are raised before any device call."""
+certificate, the tapes and closed forms that tests/test_gpu_flowbars_edges.py leans on, the C ABI's declarations and exports, and the
+argument errors that are raised before any device call."""
+import math
 import os
 import re
 import subprocess
@@ -16,45 +18,53 @@ NAN, INF = float("nan"), float("inf")
 
 
 # ---------------------------------------------------------------------------------------------- the loops, by hand
+def hand_check(group):
+    """Every tape of R.HAND_TAPES[group] gives, under the loops, the closes that are written beside it."""
+    for sides, sizes, thr, want in R.HAND_TAPES[group]:
+        assert want
+        for rule, idx in want.items():
+            assert R.RULES[rule](sides, sizes, thr) == idx, (group, rule, sides, sizes)
+    return len(R.HAND_TAPES[group])
+
+
 def test_an_exact_tie_closes():
-    # theta: 1, 2, 3 (== thr: close), 1, 0, -1, -2, -3 (== -thr: close), 1
-    assert R.imbalance([1, 1, 1, 1, -1, -1, -1, -1, 1], [1.0] * 9, 3.0) == [0, 2, 7]
-    # up: 1, 2, 3 (close); then dn: 1, 2, 3 (close)
-    assert R.run([1, 1, 1, -1, -1, -1, 1], [1.0] * 7, 3.0) == [0, 2, 5]
-    assert R.imbalance([1, 1, 1], [1.0, 1.0, 0.999], 3.0) == [0]
+    assert hand_check("tie") == 3
 
 
 def test_a_side_of_zero_contributes_nothing():
-    assert R.imbalance([1, 0, 0, 1, 0, 1], [1.0, 50.0, 50.0, 1.0, 50.0, 1.0], 3.0) == [0, 5]
-    assert R.run([1, 0, 0, 1, 0, 1], [1.0, 50.0, 50.0, 1.0, 50.0, 1.0], 3.0) == [0, 5]
+    assert hand_check("side_zero") == 1
 
 
 def test_tick_zero_is_counted_but_cannot_close():
-    # |x[0]| >= thr: no close at 0; tick 1 sees theta = 5 + 1 and closes
-    assert R.imbalance([1, 1, 1, 1], [5.0, 1.0, 1.0, 1.0], 3.0) == [0, 1]
-    assert R.imbalance([1, -1, 1, 1], [5.0, 1.0, 1.0, 1.0], 3.0) == [0, 1]        # theta = 4 at tick 1
-    assert R.imbalance([1, -1, -1, -1], [3.0, 1.0, 1.0, 1.0], 3.0) == [0]         # 2, 1, 0: tick 0 was counted
-    assert R.run([-1, 1, 1], [5.0, 1.0, 1.0], 3.0) == [0, 1]                      # dn = 5 from tick 0 closes at tick 1
-    assert R.imbalance([1], [5.0], 3.0) == [0] and R.run([1], [5.0], 3.0) == [0]
-    assert R.imbalance([], [], 3.0) == [0] and R.run([], [], 3.0) == [0]
+    assert hand_check("tick_zero") == 6
 
 
 def test_run_bars_close_on_the_sell_side_and_are_not_consecutive_runs():
-    # buys and sells alternate: neither total is a "run" of consecutive ticks, the sell total reaches 3 first
-    assert R.run([1, -1, -1, 1, -1, 1], [0.5, 1.0, 1.0, 0.5, 1.0, 0.5], 3.0) == [0, 4]
-    # the imbalance of the same tape never gets there
-    assert R.imbalance([1, -1, -1, 1, -1, 1], [0.5, 1.0, 1.0, 0.5, 1.0, 0.5], 3.0) == [0]
+    assert hand_check("sell_side") == 1
 
 
 def test_nan_amount():
-    b, q = [1, 1, 1, 1, -1, -1, -1, 1, 1, 1], [1.0, 1.0, 1.0, NAN, 1.0, 1.0, 1.0, 1.0, 1.0, 1.0]
-    # imbalance: closes at 2, then theta is NaN for good
-    assert R.imbalance(b, q, 3.0) == [0, 2]
-    # run: up is NaN from tick 3 on and never closes; dn reaches 3 at tick 6 and the close clears both; then up: 1, 2, 3
-    assert R.run(b, q, 3.0) == [0, 2, 6, 9]
-    # a side of 0 with a NaN size: 0 * NaN is NaN for the imbalance sum, and nothing for the run totals
-    assert R.imbalance([1, 0, 1, 1, 1], [1.0, NAN, 1.0, 1.0, 1.0], 3.0) == [0]
-    assert R.run([1, 0, 1, 1, 1], [1.0, NAN, 1.0, 1.0, 1.0], 3.0) == [0, 3]
+    assert hand_check("nan_amount") == 2
+
+
+def test_hand_tapes_as_columns():
+    """What the GPU tests run: float32 amounts keep the written closes, 600 ticks of side 0 behind the tape add no close (but
+    for the one-tick tape, whose tick 0 could not close), and the tapes without a NaN certify (the tables must answer them)."""
+    for group, tapes in R.HAND_TAPES.items():
+        for sides, sizes, thr, want in tapes:
+            for pad in (0, 600):
+                cols = R.hand_tape_columns(sides, sizes, pad)
+                assert len(cols[0]) == len(sides) + pad and cols[1].dtype == np.float32 and cols[2].dtype == np.int8
+                for rule in R.RULES:
+                    got = R.closes(rule, "volume", *cols, thr).tolist()
+                    loop = R.RULES[rule](sides, sizes, thr)
+                    assert loop == want.get(rule, loop)
+                    if len(sides) == 1 and pad:
+                        assert got == [0, 1], (group, rule)         # tick 0 alone reached thr: the first tick behind it closes
+                    else:
+                        assert got == loop, (group, rule, pad)
+                    if group != "nan_amount":
+                        assert R.certifies(rule, "volume", *cols, thr), (group, rule, pad)
 
 
 def test_thresholds_outside_the_tables_domain_do_what_the_comparisons_do():
@@ -84,6 +94,71 @@ def test_a_quiet_stretch_shifts_the_closes(rule, at):
     assert len(sd) == 4397 and not sd[at:at + 300].any() and sd[at + 300] == cols[2][at]
     got = R.closes(rule, "volume", px, am, sd, 8.0)
     assert np.array_equal(got, R.shifted(want, at, 300))
+
+
+# ---------------------------------------------------------------------------------------------- the tapes of the edge tests
+@pytest.mark.parametrize("sign", [1, -1])
+@pytest.mark.parametrize("K", [1, 2, 7, 8, 9, 513])
+def test_one_sided_closed_form(K, sign):
+    for n in (3 * K + 5, 3 * K, 3 * K - 1):                        # an open last bar, a close on the last tick, one tick fewer
+        px, am, sd = R.one_sided(n, sign)
+        assert len(px) == n and am.dtype == np.float32 and sd.dtype == np.int8 and (sd == sign).all() and (am == 1.0).all()
+        want = R.closes_one_sided(n, K)
+        assert want.dtype == np.int64 and (want[-1] == n - 1) == (n == 3 * K or K == 1)
+        for rule in R.RULES:
+            for kind in ("tick", "volume"):
+                assert np.array_equal(R.closes(rule, kind, px, am, sd, float(K)), want), (rule, kind, K, n)
+    px, am, sd = R.one_sided(3 * K + 5, sign, lot=0.25)
+    for rule in R.RULES:
+        assert np.array_equal(R.closes(rule, "volume", px, am, sd, K * 0.25), R.closes_one_sided(3 * K + 5, K))
+
+
+def test_biased_tapes():
+    n = 16 * 4096 + 1
+    for p_up in (0.5, 0.7, 1.0):
+        px, am, sd = R.biased(n, 1, p_up, 0.1, 0.05)
+        assert len(px) == n and am.dtype == np.float32 and sd.dtype == np.int8
+        assert 0.08 < (sd == 0).mean() < 0.12 and 0.03 < (am == 0).mean() < 0.07
+        up = (sd == 1).sum() / (sd != 0).sum()
+        assert abs(up - p_up) < 0.01 and ((sd == -1).sum() == 0) == (p_up == 1.0)
+        assert (am * 64 == np.round(am * 64)).all() and (px * 4 == np.round(px * 4)).all() and (px > 0).all()
+        for rule in R.RULES:
+            for kind, thr in (("volume", 8.0), ("tick", 16.0), ("dollar", 800.0)):
+                assert R.certifies(rule, kind, px, am, sd, thr)
+                assert len(R.closes(rule, kind, px, am, sd, thr)) > 100
+    assert not np.array_equal(R.biased(n, 1, 0.7, 0.1, 0.05)[2], R.biased(n, 2, 0.7, 0.1, 0.05)[2])
+
+
+@pytest.mark.parametrize("rule", ["imbalance", "run"])
+def test_certificate_edge_tapes(rule):
+    inside, outside = (R.certificate_edge(X) for X in R.CERT_EDGE_X)
+    for px, am, sd in (inside, outside):
+        assert len(px) == 1500 and am.dtype == np.float64 and np.flatnonzero(sd).tolist() == list(R.CERT_EDGE_AT)
+        assert R.low_bit_exp(am) == -30
+        assert R.closes(rule, "volume", px, am, sd, R.CERT_EDGE_THR).tolist() == list(R.CERT_EDGE_CLOSES)
+    assert math.fsum(inside[1].tolist()) + R.CERT_EDGE_THR == 2.0 ** 23 - 2.0 ** -30
+    assert math.fsum(outside[1].tolist()) + R.CERT_EDGE_THR == 2.0 ** 23
+    assert R.certifies(rule, "volume", *inside, R.CERT_EDGE_THR) and not R.certifies(rule, "volume", *outside, R.CERT_EDGE_THR)
+
+
+@pytest.mark.parametrize("rule", ["imbalance", "run"])
+def test_a_threshold_between_two_quanta_rounds_up(rule):
+    """Lots of k / 64: a sum reaches thr exactly when it reaches the next multiple of 1 / 64 (what fb_certificate's ceil relies on)."""
+    n = 65537
+    cols = R.recipe(n)
+    at = {thr: R.closes(rule, "volume", *cols, thr) for thr in R.ROUNDING_THR}
+    lo, eight, hi, above, lot, sub = (at[thr] for thr in R.ROUNDING_THR)
+    assert np.array_equal(lo, eight) and np.array_equal(hi, above) and not np.array_equal(hi, eight)
+    assert np.array_equal(lot, np.arange(n)) and np.array_equal(sub, np.arange(n))
+
+
+def test_long_bars_with_live_flow():
+    n = (1 << 20) + 1
+    for i, (rule, thr, longest) in enumerate(R.LONG_BARS):
+        w = R.closes(rule, "volume", *R.recipe(n), thr)
+        assert np.diff(w).max() == longest
+        if i == 0:
+            assert longest > 65 * 512                               # more than one round of 64 block summaries
 
 
 # ---------------------------------------------------------------------------------------------- the certificate on the host
