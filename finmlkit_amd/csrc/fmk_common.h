@@ -434,6 +434,43 @@ static inline int fmk_rule_fir(fmk_ctx *ctx, const double *w, int64_t width, con
     return FMK_OK;
 }
 
+// the encoded-series entropies (fmk_lz.hip; the limits are fmk_lz_rule.h's): the edges are a host array in both flavours of encode
+static inline int fmk_rule_encode(fmk_ctx *ctx, const double *edges, int64_t n_edges)
+{
+    if (!edges) n_edges = 0;
+    FMK_TRY(fmk_rule_least(ctx, n_edges, 1, "encode: at least one edge is needed."));
+    if (n_edges > 254) return fmk_set_error(ctx, FMK_E_ARG, "encode: at most 254 edges.");
+    for (int64_t k = 0; k < n_edges; ++k)
+        if (!(edges[k] - edges[k] == 0.0)) return fmk_set_error(ctx, FMK_E_ARG, "encode: the edges must be finite.");
+    for (int64_t k = 1; k < n_edges; ++k)
+        if (!(edges[k - 1] < edges[k])) return fmk_set_error(ctx, FMK_E_ARG, "encode: the edges must be strictly increasing.");
+    return FMK_OK;
+}
+static inline int fmk_rule_plugin_entropy(fmk_ctx *ctx, int64_t window, int64_t word, int64_t alphabet)
+{
+    if (alphabet < 2 || alphabet > 255) return fmk_set_error(ctx, FMK_E_ARG, "plugin_entropy: alphabet must be between 2 and 255.");
+    FMK_TRY(fmk_rule_least(ctx, word, 1, "plugin_entropy: word must be at least 1."));
+    int64_t bins = 1;
+    for (int64_t j = 0; j < word && bins <= 4096; ++j) bins *= alphabet;
+    if (bins > 4096) return fmk_set_error(ctx, FMK_E_ARG, "plugin_entropy: alphabet^word must be at most 4096.");
+    if (window < word) return fmk_set_error(ctx, FMK_E_ARG, "plugin_entropy: window must be at least word.");
+    if (window > 4096) return fmk_set_error(ctx, FMK_E_ARG, "plugin_entropy: window must be at most 4096.");
+    return FMK_OK;
+}
+static inline int fmk_rule_match_lengths(fmk_ctx *ctx, int64_t lookback)
+{
+    if (lookback < 1 || lookback > 1024) return fmk_set_error(ctx, FMK_E_ARG, "match_lengths: lookback must be between 1 and 1024.");
+    return FMK_OK;
+}
+static inline int fmk_rule_kontoyiannis(fmk_ctx *ctx, int64_t window, int64_t lookback)
+{
+    if (lookback < 1 || lookback > 1024)
+        return fmk_set_error(ctx, FMK_E_ARG, "kontoyiannis_entropy: lookback must be between 1 and 1024.");
+    if (window < 2 * lookback) return fmk_set_error(ctx, FMK_E_ARG, "kontoyiannis_entropy: window must be at least 2 * lookback.");
+    if (window > 4096) return fmk_set_error(ctx, FMK_E_ARG, "kontoyiannis_entropy: window must be at most 4096.");
+    return FMK_OK;
+}
+
 // the per-bar microstructure features (fmk_micro.hip): what both flavours refuse from their arguments alone -- the host flavour with
 // its host pointers, before anything is uploaded (it also looks at the close indices themselves, which it can read)
 static inline bool fmk_ranges_overlap(const void *a, size_t na, const void *b, size_t nb)

@@ -100,6 +100,21 @@ int pair_host(fmk_ctx *ctx, int rule, const double *a, const double *b, int64_t 
     return down(ctx, out, (const T *)d_o, n);
 }
 
+// the encoded-series entropies (fmk_lz.hip): one series of In up, dev(d_in, d_out), one series of Out down; the caller has asked the
+// rules, and an empty series is answered before the context is looked at
+template <typename In, typename Out, typename Dev>
+int lz_host(fmk_ctx *ctx, const In *in, int64_t n, Out *out, Dev dev)
+{
+    if (n == 0) return FMK_OK;
+    DevBag bag(ctx);
+    In *d_in;
+    Out *d_o;
+    FMK_TRY(bag.up(in, n, &d_in));
+    FMK_TRY(bag.out(n, &d_o));
+    FMK_TRY(dev((const In *)d_in, d_o));
+    return down(ctx, out, (const Out *)d_o, n);
+}
+
 }  // namespace
 
 extern "C" {
@@ -949,6 +964,37 @@ int fmk_sadf(fmk_ctx *ctx, const double *y, int64_t n, const int64_t *end_idx, i
     FMK_TRY(down(ctx, start, d_start, n_end));
     FMK_TRY(down(ctx, n_skipped, d_skip, 1));
     return FMK_OK;
+}
+
+// the encoded-series entropies (fmk_lz.hip): edges stays a host array, the _dev entry uploads it
+int fmk_encode(fmk_ctx *ctx, const double *x, int64_t n, const double *edges, int64_t n_edges, uint8_t *codes)
+{
+    FMK_TRY(fmk_rule_encode(ctx, edges, n_edges));
+    FMK_TRY(fmk_series_check(ctx, "encode", n));
+    return lz_host(ctx, x, n, codes, [=](const double *d_x, uint8_t *d_c) { return fmk_encode_dev(ctx, d_x, n, edges, n_edges, d_c); });
+}
+
+int fmk_plugin_entropy(fmk_ctx *ctx, const uint8_t *codes, int64_t n, int64_t window, int64_t word, int64_t alphabet, double *out)
+{
+    FMK_TRY(fmk_rule_plugin_entropy(ctx, window, word, alphabet));
+    FMK_TRY(fmk_series_check(ctx, "plugin_entropy", n));
+    return lz_host(ctx, codes, n, out,
+                   [=](const uint8_t *d_c, double *d_o) { return fmk_plugin_entropy_dev(ctx, d_c, n, window, word, alphabet, d_o); });
+}
+
+int fmk_match_lengths(fmk_ctx *ctx, const uint8_t *codes, int64_t n, int64_t lookback, uint16_t *len)
+{
+    FMK_TRY(fmk_rule_match_lengths(ctx, lookback));
+    FMK_TRY(fmk_series_check(ctx, "match_lengths", n));
+    return lz_host(ctx, codes, n, len, [=](const uint8_t *d_c, uint16_t *d_l) { return fmk_match_lengths_dev(ctx, d_c, n, lookback, d_l); });
+}
+
+int fmk_kontoyiannis_entropy(fmk_ctx *ctx, const uint8_t *codes, int64_t n, int64_t window, int64_t lookback, double *out)
+{
+    FMK_TRY(fmk_rule_kontoyiannis(ctx, window, lookback));
+    FMK_TRY(fmk_series_check(ctx, "kontoyiannis_entropy", n));
+    return lz_host(ctx, codes, n, out,
+                   [=](const uint8_t *d_c, double *d_o) { return fmk_kontoyiannis_entropy_dev(ctx, d_c, n, window, lookback, d_o); });
 }
 
 }  // extern "C"

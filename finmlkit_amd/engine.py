@@ -15,7 +15,7 @@ import numpy as np
 from . import _ffi
 from ._ffi import (DIRECTIONAL_FIELDS, FOOTPRINT_BAR_FIELDS, FOOTPRINT_FLAT_FIELDS, MICROSTRUCTURE_FIELDS, Context, DeviceArray,
                    DirectionalOut, FootprintOut, MicrostructureOut, c_f64, c_i64, c_vp)
-from .feature.core import clock, fracdiff
+from .feature.core import clock, fracdiff, lz
 from .feature.core.structural_break import adf
 from .feature.series_ops import OPS, resident
 
@@ -563,6 +563,26 @@ class DeviceTrades:
         """frac_diff_ffd (feature/core/fracdiff.py) of a resident float64 series: the fixed-width window fractional
         differentiation of order d; ValueError for a d or a threshold that frac_diff_weights refuses."""
         return fracdiff.resident(self.ctx, y, fracdiff.frac_diff_weights(d, threshold))
+
+    # the encoding and the entropies of an encoded series (csrc/fmk_lz.hip); the edges are host numbers, a message is a uint8 array
+    def encode(self, y: DeviceArray, edges) -> DeviceArray:
+        """encode (feature/core/lz.py) of a resident float64 series -> a uint8 array of codes: the edges at or below each element,
+        255 for a NaN; ValueError for the edges that function refuses."""
+        return lz.resident(self.ctx, "encode", y, edges)
+
+    def plugin_entropy(self, codes: DeviceArray, window: int, word: int = 1, alphabet: int = 2) -> DeviceArray:
+        """plugin_entropy (feature/core/lz.py) of a resident uint8 message, in bits per symbol; ValueError for the arguments that
+        function refuses."""
+        return lz.resident(self.ctx, "plugin_entropy", codes, window, word, alphabet)
+
+    def match_lengths(self, codes: DeviceArray, lookback: int) -> DeviceArray:
+        """match_lengths (feature/core/lz.py) of a resident uint8 message -> a uint16 array."""
+        return lz.resident(self.ctx, "match_lengths", codes, lookback)
+
+    def kontoyiannis_entropy(self, codes: DeviceArray, window: int, lookback: int) -> DeviceArray:
+        """kontoyiannis_entropy (feature/core/lz.py) of a resident uint8 message, in bits per symbol; ValueError for the arguments
+        that function refuses."""
+        return lz.resident(self.ctx, "kontoyiannis_entropy", codes, window, lookback)
 
     # the bar clock, run lengths and the opening range (csrc/fmk_clock.hip).  ts=None: the tape's own stamps; a DeviceArray of bar
     # stamps (int64 nanoseconds, e.g. from gather_ts) may be given instead

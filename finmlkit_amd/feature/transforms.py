@@ -13,7 +13,8 @@ opening range `BarDuration`, `BarDurationEWMA`, `BarRate`, `DirRunLen` and `ORBB
 :1210-1270, :1605-1664, :1122-1207; there pandas' diff, ewm and time-window rolling, a sequential loop and a Python loop per day, here
 the kernels of csrc/fmk_clock.hip), and the fixed-width window fractional differentiation `FracDiff` (no counterpart in the reference;
 core/fracdiff.py, the kernel of csrc/fmk_fir.hip) and the supremum ADF statistic `SADF` (no counterpart either;
-core/structural_break/adf.py, the kernel of csrc/fmk_sadf.hip).
+core/structural_break/adf.py, the kernel of csrc/fmk_sadf.hip), and the entropies of the encoded column `PluginEntropy` and
+`KontoyiannisEntropy` (no counterpart either; core/lz.py, the kernels of csrc/fmk_lz.hip).
 
 Counterparts of finmlkit/feature/transforms.py:89-117 (ReturnT), :308-332 (EWMST) and the
 pipeline part of finmlkit/feature/kit.py:Compose (:630-720), enough to run the QuickStart flow
@@ -31,7 +32,7 @@ import pandas as pd
 
 from .. import _ffi
 from .._ffi import DeviceArray, c_f64, c_i64
-from .core import clock, fracdiff
+from .core import clock, fracdiff, lz
 from .core.structural_break import adf
 from .core.structural_break.cusum import cusum_test_rolling
 from .core.correlation import rolling_price_volume_correlation
@@ -297,6 +298,65 @@ class SADF(SISOTransform):
 
     def _dev(self, ts, y):
         return adf.resident(ts.ctx, y, None, self.min_len, self.max_len, self.lags, self.trend, self.step)[0]
+
+
+class _EncodedEntropy(SISOTransform):
+    """An entropy of the input column's message (core/lz.py; the reference has no counterpart): the column is encoded with `edges`
+    -- 1 to 254 increasing values, or an int q for `quantile_edges(column, q)`, computed on the host from the column itself -- and
+    the estimator runs on the codes; every backend is the kernel.  The arguments the functions refuse raise ValueError at
+    construction.  In a `Compose` chain the codes never visit the host; there an int q raises ValueError, as the column is not on
+    the host to take quantiles of."""
+    _function = ""
+
+    def __init__(self, input_col: str, output_col: str, edges):
+        super().__init__(input_col, output_col)
+        if isinstance(edges, (int, np.integer)) and not isinstance(edges, bool):
+            lz.quantile_edges([0.0], edges)                          # (refuses a q outside 2..255)
+            self.edges = int(edges)
+        else:
+            self.edges = lz.rule_edges(edges)
+
+    def _scalars(self, edges):
+        """the estimator's arguments behind the codes, for the edges in use"""
+        raise NotImplementedError
+
+    def _hip(self, x):
+        col = np.ascontiguousarray(self._prepare_input_nb(x), dtype=np.float64)
+        edges = lz.quantile_edges(col, self.edges) if isinstance(self.edges, int) else self.edges
+        return self._prepare_output_nb(x.index, getattr(lz, self._function)(lz.encode(col, edges), *self._scalars(edges)))
+
+    def _dev(self, ts, y):
+        if isinstance(self.edges, int):
+            raise ValueError(lz.Q_DEV_MESSAGE.format(type(self).__name__))
+        return lz.resident(ts.ctx, self._function, lz.resident(ts.ctx, "encode", y, self.edges), *self._scalars(self.edges))
+
+
+class PluginEntropy(_EncodedEntropy):
+    """Rolling plug-in entropy rate of the encoded column in bits per symbol (AFML snippet 18.1 on a rolling window): the words are
+    `word` codes long, the alphabet is the edges' count plus one."""
+    _function = "plugin_entropy"
+
+    def __init__(self, window: int = 64, word: int = 2, edges=(0.0,), input_col: str = "ret1"):
+        super().__init__(input_col, f"plugin{window}_w{word}", edges)
+        # an int q: at most q codes; ties may leave fewer, and the alphabet of a call is that of the edges it encodes with
+        self.alphabet = self.edges if isinstance(self.edges, int) else len(self.edges) + 1
+        self.window, self.word, _ = lz.check_arguments("plugin_entropy", window=window, word=word, alphabet=self.alphabet)
+
+    def _scalars(self, edges):
+        return (self.window, self.word, len(edges) + 1)
+
+
+class KontoyiannisEntropy(_EncodedEntropy):
+    """Rolling Kontoyiannis Lempel-Ziv entropy rate of the encoded column in bits per symbol (AFML snippet 18.4, the sliding-window
+    form with a look-back of `lookback` codes)."""
+    _function = "kontoyiannis_entropy"
+
+    def __init__(self, window: int = 64, lookback: int = 16, edges=(0.0,), input_col: str = "ret1"):
+        super().__init__(input_col, f"konto{window}_{lookback}", edges)
+        self.window, self.lookback = lz.check_arguments("kontoyiannis_entropy", window=window, lookback=lookback)
+
+    def _scalars(self, edges):
+        return (self.window, self.lookback)
 
 
 class EWMA(_SeriesOp):

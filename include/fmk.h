@@ -871,6 +871,42 @@ int fmk_sadf_dev(fmk_ctx *ctx, const double *d_y, int64_t n, const int64_t *d_en
 int fmk_sadf(fmk_ctx *ctx, const double *y, int64_t n, const int64_t *end_idx, int64_t n_end, int64_t min_len, int64_t max_len,
              int64_t step, int64_t lags, int trend, double *stat, int64_t *start, int64_t *n_skipped);
 
+/* ---- entropy of an encoded series (csrc/fmk_lz.hip; Lopez de Prado, Advances in Financial Machine Learning, ch. 18; the reference
+ * has no such functions: the definitions are this project's).  A message is a uint8 array of codes; a code
+ * >= alphabet is INVALID and 255 always is (the match lengths and the Kontoyiannis estimator take no alphabet: 255 alone).  A window
+ * that reads an invalid code gives NaN.  n == 0 succeeds and touches nothing, not even the context.
+ *
+ * encode: codes[i] = the number of edges <= x[i] (np.searchsorted(edges, x, side="right"); -inf 0, +inf n_edges), 255 for a NaN.
+ * edges[0 .. n_edges) is a HOST array in both flavours (the call checks it and copies it to the device in the stream's order); the
+ * alphabet is n_edges + 1.  FMK_E_ARG, in this order: n_edges < 1, n_edges > 254, an edge that is not finite, edges that are not
+ * strictly increasing; then n >= 2^31.
+ *
+ * plugin_entropy, bits per symbol: the window codes[t-window+1 .. t] holds M = window - word + 1 overlapping words of `word` codes;
+ * c(v) = the count of word v;  out[t] = (sum over the words v, ascending in their id, of c(v) * (log2 M - log2 c(v))) / M / word
+ * -- which is (log2 M - (1/M) sum_c N_c log2 c) / word with N_c the occurrences whose word has count c, and -sum p log2 p / word.
+ * log2 M - log2 c is one table entry, 0.0 at c = M: a window whose words are all the same gives exactly 0.0.  NaN for t < window - 1.
+ * The bits depend on codes, window, word and alphabet alone.  FMK_E_ARG, in this order: alphabet outside 2..255, word < 1,
+ * alphabet^word > 4096, window < word, window > 4096; then n >= 2^31.
+ *
+ * match_lengths (n = lookback, N = the series' length): for n <= p <= N - n whose codes[p-n .. p+n) are all valid
+ *   len[p] = 1 + max over d = 1 .. n of min(n, the number of k >= p in a row with codes[k] == codes[k-d])
+ * (a match may run over p itself; len[p] lies in 1 .. n + 1); len[p] = 0 everywhere else.  The work is the same whatever the data.
+ * FMK_E_ARG: lookback outside 1..1024; then N >= 2^31.
+ *
+ * kontoyiannis_entropy, bits per symbol (the sliding-window form of the book's snippet 18.4): with count = window - 2n + 1
+ *   out[t] = (log2(n + 1) / count) * (1/len[t-window+1+n] + .. + 1/len[t-n+1]),   the sum oldest first, each quotient rounded
+ * NaN for t < window - 1 and where one of those len is 0: exactly the windows that read an invalid code.  len is scratch from the
+ * context's pool.  FMK_E_ARG, in this order: lookback outside 1..1024, window < 2 * lookback, window > 4096; then N >= 2^31. */
+int fmk_encode_dev(fmk_ctx *ctx, const double *d_x, int64_t n, const double *edges, int64_t n_edges, uint8_t *d_codes);
+int fmk_encode(fmk_ctx *ctx, const double *x, int64_t n, const double *edges, int64_t n_edges, uint8_t *codes);
+int fmk_plugin_entropy_dev(fmk_ctx *ctx, const uint8_t *d_codes, int64_t n, int64_t window, int64_t word, int64_t alphabet,
+                           double *d_out);
+int fmk_plugin_entropy(fmk_ctx *ctx, const uint8_t *codes, int64_t n, int64_t window, int64_t word, int64_t alphabet, double *out);
+int fmk_match_lengths_dev(fmk_ctx *ctx, const uint8_t *d_codes, int64_t n, int64_t lookback, uint16_t *d_len);
+int fmk_match_lengths(fmk_ctx *ctx, const uint8_t *codes, int64_t n, int64_t lookback, uint16_t *len);
+int fmk_kontoyiannis_entropy_dev(fmk_ctx *ctx, const uint8_t *d_codes, int64_t n, int64_t window, int64_t lookback, double *d_out);
+int fmk_kontoyiannis_entropy(fmk_ctx *ctx, const uint8_t *codes, int64_t n, int64_t window, int64_t lookback, double *out);
+
 /* ---- TradesData(preprocess=True) loops: finmlkit/bar/utils.py ("next" rank 4) ------------ */
 /* merge_split_trades (bar/utils.py:263-329): trades with the head's timestamp, maker flag and price (|dp| < 1e-8)
  * are merged, amounts summed in float32 in trade order; side = -1 if is_buyer_maker else 1 (is_buyer_maker may be
