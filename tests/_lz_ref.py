@@ -138,3 +138,109 @@ def plugin_entropy(codes, window, word=1, alphabet=2):
         p = c / M
         out[t] = -(p * np.log2(p)).sum() / word + 0.0                # (+ 0.0: no -0.0 for a constant window)
     return out
+
+
+# ------------------------------------------------------------------------------------------ the messages of the tests
+TILE = 256                           # positions per workgroup of the match lengths (csrc/fmk_lz.hip)
+
+
+def message(name, n_codes, stretch=None, invalid_at=None):
+    """The seeded message `name` of n_codes codes (read-only).  `stretch` = (first, end) is the constant stretch of "spliced",
+    `invalid_at` the positions of the 255s of "invalid"; the defaults are those of the 1100-code messages of tests/test_gpu_lz.py."""
+    rng = np.random.default_rng(1800 + sum(map(ord, name)))
+    k = np.arange(n_codes)
+    if name == "binary":
+        m = rng.integers(0, 2, n_codes)
+    elif name == "4-ary":
+        m = rng.integers(0, 4, n_codes)
+    elif name == "16-ary":
+        m = rng.integers(0, 16, n_codes)
+    elif name == "constant":
+        m = np.ones(n_codes)
+    elif name == "period 2":
+        m = k % 2
+    elif name == "period 65":
+        m = k % 65
+    elif name == "k mod 255":
+        m = k % 255
+    elif name == "spliced":                                          # a constant stretch in a binary message
+        first, end = stretch or (TILE - 150, TILE + 150)
+        m = rng.integers(0, 2, n_codes)
+        m[first:end] = 1
+    elif name == "invalid":                                          # a few invalid codes in a 3-ary message
+        m = rng.integers(0, 3, n_codes)
+        m[list(invalid_at or (3, 4 * TILE, n_codes - 1))] = INVALID
+    else:
+        assert name == "over"                                        # codes beyond a binary alphabet that are not 255
+        m = rng.integers(0, 2, n_codes)
+        m[[300, 301]] = [2, 200]
+    m = m.astype(np.uint8)
+    m.setflags(write=False)
+    return m
+
+
+def edge_length(lookback):
+    """the length of the messages at the large lookbacks: four lookbacks, three tiles and an odd rest"""
+    return 4 * lookback + 3 * TILE + 77
+
+
+def edge_stretch(lookback):
+    """the constant stretch of the spliced message at a large lookback: 2 n + 300 codes (more than a tile: it crosses a tile's edge),
+    from a little behind the first valid position"""
+    return lookback + 50, 3 * lookback + 350
+
+
+def edge_invalid_at(lookback):
+    """the 255s of the invalid message at a large lookback: position 3, the first element of the first tile that starts beyond
+    2 n, the last element of the tile after that one, and the last code"""
+    tile = TILE * (2 * lookback // TILE + 1)
+    return 3, tile, tile + 2 * TILE - 1, edge_length(lookback) - 1
+
+
+def edge_message(name, lookback):
+    return message(name, edge_length(lookback), edge_stretch(lookback), edge_invalid_at(lookback))
+
+
+KONTO_NAN = (4096, 64, (3, 8000, 4 * 4096 - 1))       # (window, lookback, the 255s) of the 16384-code message of the NaN windows
+
+
+PLANT_LAGS = (1, 2, 63, 64, 65)
+PLANT_RUNS = (1, 2, 63, 64, 65, 127, 128, 129)
+
+
+def planted_message(lookback, seed):
+    """(codes, plants): random codes 0 .. 250 with one planted repeat per (lag d, run r), plants = [(p, d, r)].  A plant copies
+    codes[i] = codes[i - d] for i = p .. p + r - 1, ascending (r > d: the match runs over p itself), and codes[p - 1] and codes[p + r]
+    are made to differ from the codes d before them: the run at lag d starts at p and holds exactly r matches.  The starts cycle
+    through the lanes 0, 1 and 63 of a wave; every fifth plant sits on the first, the second or the last element of a 256-position
+    tile.  2 n + 8 background codes or more lie between two plants, the first starts beyond 2 n + 256, n + 300 codes follow the last."""
+    n = lookback
+    rng = np.random.default_rng(seed)
+    lags = sorted({d for d in PLANT_LAGS + (n // 2, n - 1, n) if 1 <= d <= n})
+    runs = sorted({r for r in PLANT_RUNS + (n - 1, n, n + 7) if r >= 1})
+    plants, at = [], 2 * n + TILE + 1
+    for k, (d, r) in enumerate((d, r) for d in lags for r in runs):
+        if k % 5 == 4:
+            p = at + (((0, 1, TILE - 1)[k // 5 % 3] - at) % TILE)
+        else:
+            p = at + (((0, 1, 63)[k % 3] - at) % 64)
+        plants.append((p, d, r))
+        at = p + r + 1 + 2 * n + 8 + 1                               # the stop code, the background, the code in front of the next plant
+    codes = rng.integers(0, 251, plants[-1][0] + plants[-1][2] + n + 300)
+
+    def differ(i, d):                                                # codes[i] != codes[i - d], whatever it was
+        if codes[i] == codes[i - d]:
+            codes[i] = (codes[i - d] + 1 + rng.integers(0, 250)) % 251
+
+    for p, d, r in plants:
+        differ(p - 1, d)
+        for i in range(p, p + r):
+            codes[i] = codes[i - d]
+        differ(p + r, d)
+    codes = codes.astype(np.uint8)
+    codes.setflags(write=False)
+    return codes, plants
+
+
+def plant_seed(lookback):
+    return 1900 + lookback

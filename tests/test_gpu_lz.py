@@ -25,35 +25,11 @@ GOLDEN = json.load(open(os.path.join(ROOT, "tests", "golden", "lz.json")))
 
 
 @functools.lru_cache(maxsize=None)
-def message(name):
-    """The seeded messages, shared by the tests below (never written to)."""
-    rng = np.random.default_rng(1800 + sum(map(ord, name)))
-    k = np.arange(N)
-    if name == "binary":
-        m = rng.integers(0, 2, N)
-    elif name == "16-ary":
-        m = rng.integers(0, 16, N)
-    elif name == "constant":
-        m = np.ones(N)
-    elif name == "period 2":
-        m = k % 2
-    elif name == "period 65":
-        m = k % 65
-    elif name == "k mod 255":
-        m = k % 255
-    elif name == "spliced":                                          # a constant stretch of 300 across the edge of tiles 0 and 1
-        m = rng.integers(0, 2, N)
-        m[TILE - 150:TILE + 150] = 1
-    elif name == "invalid":                                          # three invalid codes, one at a tile's first element
-        m = rng.integers(0, 3, N)
-        m[[3, 4 * TILE, N - 1]] = 255
-    else:
-        assert name == "over"                                        # codes beyond a binary alphabet that are not 255
-        m = rng.integers(0, 2, N)
-        m[[300, 301]] = [2, 200]
-    m = m.astype(np.uint8)
-    m.setflags(write=False)
-    return m
+def message(name, n_codes=N, stretch=None, invalid_at=None):
+    """The seeded messages (tests/_lz_ref.py), shared by the tests here and in tests/test_gpu_lz_edges.py (never written to).
+    At the defaults: 1100 codes, "spliced" with a constant stretch of 300 across the edge of tiles 0 and 1, "invalid" with three
+    invalid codes, one at a tile's first element."""
+    return R.message(name, n_codes, stretch, invalid_at)
 
 
 MESSAGES = ("binary", "16-ary", "constant", "period 2", "period 65", "k mod 255", "spliced", "invalid")

@@ -346,6 +346,68 @@ def test_the_transforms_are_built_without_a_device(monkeypatch):
     assert c.output_name == "price_ret1_konto64_16"
 
 
+# ---------------------------------------------------------------------------------------------- the messages of the edge tests
+@pytest.mark.parametrize("lookback", (64, 129, 256, 1023, 1024))
+def test_planted_repeats_have_their_closed_form_on_the_reference(lookback):
+    """tests/test_gpu_lz_edges.py compares the kernel with R.match_lengths on these messages; here the reference itself against what
+    was planted: a run of exactly r matches at lag d from p on gives 1 + min(r, n) at p, and at least 1 + min(r - i, n) i codes on."""
+    n = lookback
+    codes, plants = R.planted_message(n, R.plant_seed(n))
+    assert codes.dtype == np.uint8 and codes.max() <= 250 and len(plants) == len({(d, r) for _, d, r in plants}) >= 45
+    lam = R.match_lengths(codes, n)
+    for p, d, r in plants:
+        assert codes[p - 1] != codes[p - 1 - d] and codes[p + r] != codes[p + r - d] and (codes[p:p + r] == codes[p - d:p + r - d]).all()
+        assert lam[p] == 1 + min(r, n), (p, d, r)
+        assert (lam[p:p + r] >= 1 + np.minimum(r - np.arange(r), n)).all(), (p, d, r)
+    starts = [p for p, _, _ in plants]
+    assert {0, 1, 63} <= {p % 64 for p in starts} and {0, 1, 255} <= {p % 256 for p in starts}
+    assert starts[0] > 2 * n + 256 and len(codes) == starts[-1] + plants[-1][2] + n + 300
+    assert min(b - 1 - (a + r + 1) for (a, _, r), b in zip(plants, starts[1:])) >= 2 * n + 8     # background between two plants
+    # what the random messages do not hold: a run of more than 64 that stops before the cap, at a lag beyond 65
+    assert lookback < 129 or sum(1 for _, d, r in plants if d > 65 and 64 < r < n) >= 6
+    if lookback == 64:
+        msg = tuple(int(c) for c in codes)
+        for p in starts:
+            assert R.match_length(msg, p, n) == lam[p], p
+
+
+@pytest.mark.parametrize("lookback", (127, 128, 129, 255, 256, 257, 1023, 1024))
+def test_the_messages_at_large_lookbacks_cover_what_they_are_for(lookback):
+    n, N = lookback, R.edge_length(lookback)
+    first, end = R.edge_stretch(n)
+    assert end - first == 2 * n + 300 and first // 256 != (end - 1) // 256 and end < N
+    sp = R.match_lengths(R.edge_message("spliced", n), n)
+    assert (sp[first + 1:end - n + 1] == n + 1).all()                                           # the cap, on a stretch
+    assert len(set(sp[end - n:end + 64])) >= 64                                                  # and the tail behind it: every length
+    at = R.edge_invalid_at(n)
+    assert at[0] == 3 and at[1] % 256 == 0 and at[1] > 2 * n and at[2] % 256 == 255 and at[2] // 256 != at[1] // 256 and at[3] == N - 1
+    codes = R.edge_message("invalid", n)
+    assert np.array_equal(np.flatnonzero(codes == 255), at)
+    zero = np.zeros(N, bool)
+    zero[:n], zero[N - n + 1:] = True, True
+    for i in at:
+        zero[max(0, i - n + 1):i + n + 1] = True
+    bad = R.match_lengths(codes, n)
+    assert np.array_equal(bad == 0, zero) and np.count_nonzero(bad) >= 256
+    assert (R.match_lengths(R.edge_message("constant", n), n)[n:N - n + 1] == n + 1).all()
+    ramp = R.match_lengths(R.edge_message("k mod 255", n), n)[n:N - n + 1]                    # a period within the lookback: the cap
+    assert (ramp == (n + 1 if n >= 255 else 1)).all()
+    assert not R.match_lengths(np.full(2400, 255, np.uint8), 1024).any()
+
+
+def test_the_kontoyiannis_nan_message_on_the_reference():
+    window, lookback, at = R.KONTO_NAN
+    codes = R.message("invalid", 4 * window, None, at)
+    assert at[0] == 3 and at[-1] == len(codes) - 1 and window < at[1] < len(codes) - 2 * window
+    want = R.kontoyiannis_entropy(codes, window, lookback)
+    nan = np.zeros(len(codes), bool)
+    nan[:window - 1] = True
+    for i in at:
+        nan[i:i + window] = True
+    assert np.array_equal(np.isnan(want), nan)
+    assert 2 * int(np.isfinite(want[window - 1:]).sum()) >= len(codes) - window + 1               # finite in half of the full windows
+
+
 # ---------------------------------------------------------------------------------------------- the header on the host
 def test_rule_header_on_the_host(tmp_path):
     """tools/lz_check.cpp, built from csrc/fmk_lz_rule.h with the host compiler alone (no HIP), in its quick form: the runs a wave
