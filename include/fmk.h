@@ -821,6 +821,40 @@ int fmk_sequential_bootstrap(fmk_ctx *ctx, const int64_t *event_idx, const int64
  * per launch when draws_per_launch is 0.  Needs no context and no device. */
 int fmk_seqboot_geometry(int64_t *out3);
 
+/* ---- optimal trading rules (Lopez de Prado, Advances in Financial Machine Learning, ch. 13, snippets 13.1 / 13.2; the reference has no
+ * such function: the definition is this project's; csrc/fmk_otr.hip, csrc/fmk_otr_rule.h).  Paths of a discrete
+ * Ornstein-Uhlenbeck process are closed at a profit-taking level, a stop-loss level or a maximum holding period, for every pair
+ * (pt[i], sl[j]) of a mesh; the outputs are the statistics of the closing values.  A result is a function of the arguments alone, bit
+ * for bit, on any device and on the host (tools/otr_check.cpp runs the same rule text).
+ *   Inputs: n_cfg parameter sets (forecast[c], phi[c], sigma[c]), all finite, 0 <= phi <= 1, sigma >= 0; pt[0 .. n_pt) and
+ *     sl[0 .. n_sl), each non-negative, non-decreasing, without NaN (+inf: the barrier is off); max_hp, n_paths, seed; normals: NULL,
+ *     or a HOST array [n_paths][max_hp] of finite float64 that replaces the generator.
+ *   Limits: 1 <= n_pt, n_sl <= 32, 1 <= max_hp <= 4096, 1 <= n_paths <= 2^32, 1 <= n_cfg <= 1024; anything else is FMK_E_ARG.
+ *   Normal variates (Marsaglia's polar method on counter words): path p takes step h = 1 .. max_hp from pair k = (h-1) >> 1, member
+ *     (h-1) & 1.  For attempt a = 0 .. 63: index = ((((p << 12) | k) << 6 | a) << 1) | w (w = 0 for u, 1 for v); word = splitmix64 at
+ *     counter index + 1 from seed (the bootstrap's word); u = (double)(word >> 11) * 2^-52 - 1.0 (exact, in [-1, 1)); s = u*u + v*v (the
+ *     products and the sum rounded separately); the first attempt with s < 1.0 && s != 0.0 is taken: f = sqrt((-2.0 * log(s)) / s)
+ *     with the host's logarithm, the pair is (u*f, v*f).  After 64 rejections the pair is (0.0, 0.0).  The variates depend on
+ *     (seed, p, h) only: all parameter sets of a call see the same random numbers.
+ *   Path: c0 = (1.0 - phi) * forecast, P_0 = 0.0, P_h = (c0 + phi * P_{h-1}) + sigma * z_h, every operation rounded on its own.
+ *   Exit of node (i, j): the smallest h with P_h > pt[i] (profit) or P_h < -sl[j] (stop), strict, else max_hp (time); x = P_h there.  A
+ *     crossing at h = max_hp counts as the barrier's.
+ *   Sums: paths are cut into blocks [b B, (b+1) B), B a constant of the library (fmk_otr_geometry).  Per node and block
+ *     S1_b = (((0 + x_0) + x_1) + ...) in path order, S2_b the same with x*x (the product rounded, then added); the totals are the
+ *     left-to-right sums of the block partials in block order.  mean = S1 / n; var = S2 / n - mean*mean, 0.0 when negative;
+ *     std = sqrt(var); sharpe = mean / std with IEEE semantics (0/0 NaN, x/0 +-inf).
+ *   Outputs, HOST arrays [n_cfg][n_pt][n_sl], each may be NULL: mean, std, sharpe (float64); n_profit, n_stop, n_time (their sum is
+ *     n_paths) and hold, the sum of the exit steps (int64).
+ * A host-pointer entry without a _dev flavour: the inputs are a few hundred bytes and the outputs a few KiB.  The arguments are
+ * checked before a device is touched.  FMK_E_NOMEM when the scratch does not fit: 16 bytes per node and block of one parameter set
+ * (several sets share a launch while their partials stay under 256 MiB), 8 bytes per normal. */
+int fmk_otr_mesh(fmk_ctx *ctx, const double *forecast, const double *phi, const double *sigma, int64_t n_cfg, const double *pt,
+                 int64_t n_pt, const double *sl, int64_t n_sl, int64_t max_hp, int64_t n_paths, uint64_t seed, const double *normals,
+                 double *mean, double *std, double *sharpe, int64_t *n_profit, int64_t *n_stop, int64_t *n_time, int64_t *hold);
+/* The kernel's geometry, for callers that place work at its seams: out4[0] B, the paths of a block of the sums, [1] the paths of a
+ * tile (walked at once, one per lane), [2] the most levels on either side, [3] the largest max_hp.  Needs no context and no device. */
+int fmk_otr_geometry(int64_t *out4);
+
 /* ---- causal FIR filter on a float64 series of n elements -> float64 array of n elements (csrc/fmk_fir.hip), and with the weights
  * of feature/core/fracdiff.py the fixed-width window fractional differentiation "FFD" (Lopez de Prado, Advances in Financial
  * Machine Learning, ch. 5; the reference has no such function: the definition is this project's).
