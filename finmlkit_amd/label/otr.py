@@ -101,7 +101,7 @@ def _levels(name, v):
     a = np.ascontiguousarray(np.atleast_1d(np.asarray(v, dtype=np.float64)))
     if a.ndim != 1 or not 1 <= a.size <= MAX_LEVELS:
         raise ValueError(f"optimal_trading_rule: {name} must hold between 1 and 32 levels.")
-    if np.isnan(a).any() or (a < 0.0).any() or (np.diff(a) < 0.0).any():
+    if np.isnan(a).any() or (a < 0.0).any() or (a[1:] < a[:-1]).any():           # not np.diff: inf - inf warns
         raise ValueError(f"optimal_trading_rule: the {name} levels must be non-negative and non-decreasing, without NaN.")
     return a
 

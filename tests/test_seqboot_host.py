@@ -1,7 +1,7 @@
 """CPU-only checks of the sequential bootstrap: the definition in tests/_seqboot_ref.py in its two forms against
 each other and on the book's example, the host program of csrc/fmk_seqboot_rule.h against it, the refusals of the Python layer, and
 the property the feature exists for, on the reference alone.  The inputs are recorded here as functions; tests/test_gpu_seqboot.py
-imports them."""
+and tests/test_gpu_seqboot_edges.py import them."""
 import functools
 import os
 import re
@@ -78,6 +78,24 @@ def recorded_cases():
     out.append((ev, tc, n, 8, 2, 0, np.array([0, (1 << 64) - 1] * 8, np.uint64)))
     out.append((np.array([0, 7, (1 << 32) - 9], np.int64), np.array([(1 << 32) - 1, 7, (1 << 32) - 1], np.int64), 1 << 32, 12, 1, 5, None))
     return out
+
+
+# ---------------------------------------------------------------------------------------------- the inputs of tests/test_gpu_seqboot_edges.py
+SB_BATCH = 8                       # csrc/fmk_seqboot.hip SB_BATCH: the loads a thread keeps in flight; sb_draws walks its runs in such groups
+BATCH_M = (8191, 8192, 8193, 16384, 16385)          # events: 8, 8, 9, 16, 17 per thread
+BATCH_J = (7168, 8191, 16383, 16384)                # intervals: 8 per thread (with a spare row place, and to the last place), 16, 17
+BATCH_LAST_M = (8199, 16388)                        # whole runs of 9 and 17 events: the last event closes the second and the third group
+BATCH_EXTRA = 40
+
+
+def runs_per_thread(ev, tc, threads):
+    """-> (ept, ipt): the events and the intervals of a thread's run, as the library sizes them"""
+    return -(-len(ev) // threads), len(R.compress(ev, tc)[0]) // threads + 1
+
+
+def batch_passes(n):
+    """-> (full groups of SB_BATCH, remainder) of a run of n elements"""
+    return divmod(n, SB_BATCH)
 
 
 # ---------------------------------------------------------------------------------------------- the definition
@@ -219,3 +237,31 @@ def test_header_declares_and_library_exports_the_entry_points():
     g = bootstrap.geometry()                                  # needs no device
     assert g["threads"] == 1024 and g["draws_per_launch"] >= 1
     assert 12 * g["lds_intervals"] + 8 <= 64 * 1024           # c (4 B) and P (8 B) per interval, one more P, in static LDS
+
+
+# ---------------------------------------------------------------------------------------------- what the batched-loop cases hold
+def test_batch_cases_go_round_the_batched_loops_twice_with_and_without_a_remainder():
+    from finmlkit_amd.label import bootstrap
+    g = bootstrap.geometry()
+    T = g["threads"]
+    by_m = {m: runs_per_thread(*random_spans(m, m)[:2], T) for m in BATCH_M + BATCH_LAST_M}
+    by_j = {J: runs_per_thread(*spans_with_intervals(J, extra=BATCH_EXTRA)[:2], T) for J in BATCH_J}
+    print("m -> (ept, ipt)", by_m, "J -> (ept, ipt)", by_j)
+    ept = {v[0] for v in by_m.values()}
+    ipt = {v[1] for v in list(by_m.values()) + list(by_j.values())}
+    assert [by_m[m][0] for m in BATCH_M] == [8, 8, 9, 16, 17] and {8, 9, 16, 17} <= ept
+    assert [by_j[J][1] for J in BATCH_J] == [8, 8, 16, 17] and 8 in ipt and max(ipt) >= 16
+    assert all(ip > g["lds_intervals"] // T + 1 for _, ip in list(by_m.values()) + list(by_j.values()))       # all the scratch flavour
+    for runs in (ept, ipt):                                              # steps 2 and 3 walk ept, step 1 walks ipt
+        passes = {batch_passes(n) for n in runs}
+        assert (1, 0) in passes                                          # one full group, an empty remainder
+        assert any(full >= 2 and rest == 0 for full, rest in passes)     # twice round, an empty remainder
+        assert any(full >= 2 and rest > 0 for full, rest in passes)      # twice round and a remainder
+    # J = 7168 leaves whole threads without intervals and the end of the last interval a place in row 0; J = 8191 fills every place
+    assert by_j[7168][1] * T - 7168 == T and by_j[8191][1] * T - 8191 == 1
+    for m in BATCH_M + BATCH_LAST_M:
+        assert len(set(zip(*[a.tolist() for a in random_spans(m, m)[:2]]))) < m        # duplicates among the events
+    # the last event: which thread owns it, and in which group of its run it lies
+    last = {m: divmod(m - 1, by_m[m][0]) for m in BATCH_M + BATCH_LAST_M}
+    assert [last[m][1] // SB_BATCH for m in BATCH_LAST_M] == [1, 2] and all(last[m][1] == by_m[m][0] - 1 for m in BATCH_LAST_M)
+    assert last[8193] == (910, 2) and last[16385] == (963, 13)           # a short last run, in the first and in the second group
