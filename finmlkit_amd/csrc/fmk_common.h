@@ -103,6 +103,13 @@ struct fmk_mail {
         int64_t last[4];                   // host copy only: outputs, slabs per tile span, slab elements, tiles of the last call
     } brk;
     struct Micro { int bad; } micro;       // fmk_micro.hip (k_micro_lanes): a bar's close indices outside the tape (the call fails)
+    struct Bet {                           // fmk_bet.hip: each of them fails the call
+        long long bad, bad_signal;         // k_bet_mark / k_bud_mark: spans outside the tape, signals that are NaN or outside [-1, 1]
+        long long bad_idx;                 // k_bet_gather: indices outside the tape
+        int max_c;                         // k_bet_apply: the largest concurrency above 32767 (0: none)
+        int max2[2];                       // k_bud_scan: the largest long and short concurrency
+        int pad;
+    } bet;
 };
 static_assert(sizeof(fmk_mail::fp_median) == 2 * sizeof(int), "k_bar_footprints adds to saw_long + 1");
 static_assert(alignof(fmk_mail) == 8, "the 64-bit atomics of the kernels need 8-byte fields");
@@ -468,6 +475,18 @@ static inline int fmk_rule_kontoyiannis(fmk_ctx *ctx, int64_t window, int64_t lo
         return fmk_set_error(ctx, FMK_E_ARG, "kontoyiannis_entropy: lookback must be between 1 and 1024.");
     if (window < 2 * lookback) return fmk_set_error(ctx, FMK_E_ARG, "kontoyiannis_entropy: window must be at least 2 * lookback.");
     if (window > 4096) return fmk_set_error(ctx, FMK_E_ARG, "kontoyiannis_entropy: window must be at most 4096.");
+    return FMK_OK;
+}
+
+// bet sizing (fmk_bet.hip): what both flavours refuse from their scalars alone (the budget call passes step 0); the limits and the
+// step rule are fmk_bet_rule.h's
+#include "fmk_bet_rule.h"
+static inline int fmk_rule_bet(fmk_ctx *ctx, const char *what, int64_t n_events, int64_t n, double step)
+{
+    if (n_events < 1 || n_events > FMK_BET_MAX_EVENTS)
+        return fmk_set_error(ctx, FMK_E_ARG, "%s: n_events must be between 1 and 2^31 - 1.", what);
+    if (n < 1 || n > FMK_BET_MAX_AXIS) return fmk_set_error(ctx, FMK_E_ARG, "%s: n must be between 1 and 2^32.", what);
+    if (!fmk_bet_step_ok(step)) return fmk_set_error(ctx, FMK_E_ARG, "%s: step must be 0 (no discretisation) or in (0, 1].", what);
     return FMK_OK;
 }
 

@@ -642,6 +642,62 @@ int fmk_label_weights(fmk_ctx *ctx, const double *close_, const int16_t *concurr
     return FMK_OK;
 }
 
+int fmk_bet_size_path(fmk_ctx *ctx, const int64_t *event_idx, const int64_t *touch_idx, const double *signal, int64_t n_events,
+                      int64_t n, double step, double *out_value, int16_t *out_count)
+{
+    FMK_TRY(fmk_rule_bet(ctx, "bet_size_path", n_events, n, step));
+    DevBag bag(ctx);
+    int64_t *d_ev, *d_touch;
+    double *d_sig, *d_v;
+    int16_t *d_c = nullptr;
+    FMK_TRY(bag.up(event_idx, n_events, &d_ev));
+    FMK_TRY(bag.up(touch_idx, n_events, &d_touch));
+    FMK_TRY(bag.up(signal, n_events, &d_sig));
+    FMK_TRY(bag.out(n, &d_v));
+    if (out_count) FMK_TRY(bag.out(n, &d_c));
+    FMK_TRY(fmk_bet_size_path_dev(ctx, d_ev, d_touch, d_sig, n_events, n, step, d_v, d_c));
+    FMK_TRY(down(ctx, out_value, (const double *)d_v, n));
+    FMK_TRY(down(ctx, out_count, (const int16_t *)d_c, n));
+    return FMK_OK;
+}
+
+int fmk_bet_size_at(fmk_ctx *ctx, const int64_t *event_idx, const int64_t *touch_idx, const double *signal, int64_t n_events,
+                    int64_t n, double step, const int64_t *idx, int64_t n_idx, double *out)
+{
+    FMK_TRY(fmk_rule_bet(ctx, "bet_size_at", n_events, n, step));
+    if (n_idx < 0) return fmk_set_error(ctx, FMK_E_ARG, "negative dimensions are not allowed");
+    DevBag bag(ctx);
+    int64_t *d_ev, *d_touch, *d_idx;
+    double *d_sig, *d_o;
+    FMK_TRY(bag.up(event_idx, n_events, &d_ev));
+    FMK_TRY(bag.up(touch_idx, n_events, &d_touch));
+    FMK_TRY(bag.up(signal, n_events, &d_sig));
+    FMK_TRY(bag.up(idx, n_idx, &d_idx));
+    FMK_TRY(bag.out(n_idx, &d_o));
+    FMK_TRY(fmk_bet_size_at_dev(ctx, d_ev, d_touch, d_sig, n_events, n, step, d_idx, n_idx, d_o));
+    FMK_TRY(down(ctx, out, (const double *)d_o, n_idx));
+    return FMK_OK;
+}
+
+int fmk_bet_size_budget(fmk_ctx *ctx, const int64_t *event_idx, const int64_t *touch_idx, const int8_t *side, int64_t n_events,
+                        int64_t n, double *out_m, int64_t *out_max2)
+{
+    FMK_TRY(fmk_rule_bet(ctx, "bet_size_budget", n_events, n, 0.0));
+    DevBag bag(ctx);
+    int64_t *d_ev, *d_touch, *d_max;
+    int8_t *d_sd;
+    double *d_m;
+    FMK_TRY(bag.up(event_idx, n_events, &d_ev));
+    FMK_TRY(bag.up(touch_idx, n_events, &d_touch));
+    FMK_TRY(bag.up(side, n_events, &d_sd));
+    FMK_TRY(bag.out(n, &d_m));
+    FMK_TRY(bag.out(2, &d_max));
+    FMK_TRY(fmk_bet_size_budget_dev(ctx, d_ev, d_touch, d_sd, n_events, n, d_m, d_max));
+    FMK_TRY(down(ctx, out_m, (const double *)d_m, n));
+    FMK_TRY(down(ctx, out_max2, (const int64_t *)d_max, 2));
+    return FMK_OK;
+}
+
 int fmk_cusum_filter(fmk_ctx *ctx, const double *x, int64_t n, const double *thr, int64_t n_thr, int64_t *out, int64_t capacity,
                      int64_t *n_out)
 {

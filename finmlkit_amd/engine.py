@@ -752,6 +752,55 @@ class DeviceTrades:
                       c_i64(n_runs), C.c_uint64(seed), None, c_i64(dpl), draws.p, None if q is None else q.p)
         return (draws, q) if return_uniqueness else draws
 
+    def _bet_events(self, what: str, event_idx: DeviceArray, touch_idx: DeviceArray, per_event: DeviceArray, dtype, name: str):
+        if touch_idx.n != event_idx.n or per_event.n != event_idx.n:
+            raise ValueError(f"{what}: event_idxs, touch_idxs and {name} must have the same length.")
+        if event_idx.dtype != np.int64 or touch_idx.dtype != np.int64:
+            raise TypeError(f"{what}: the event and touch indices must be int64")
+        if per_event.dtype != dtype:
+            raise TypeError(f"{what}: {name} must be {np.dtype(dtype)}, not {per_event.dtype}")
+        if event_idx.n < 1:
+            raise ValueError(f"{what}: n_events must be between 1 and 2^31 - 1.")
+
+    def bet_size_path(self, event_idx: DeviceArray, touch_idx: DeviceArray, signal: DeviceArray, step: float = 0.0,
+                      return_count: bool = False):
+        """bet_size_path (label/betsize.py) on resident spans, as `triple_barrier` and `trend_scanning` return
+        them, and a resident float64 signal per event -> the float64 position per tick of this tape: the average of the signals of
+        the events open on event_idx <= t < touch_idx, discretised when step > 0; with return_count also the int16 number of open
+        events.  ValueError for what the library counts on the device: a span outside the tape, a signal that is NaN or outside
+        [-1, 1], more than 32767 events open on one tick."""
+        from .label.betsize import check_step
+        self._bet_events("bet_size_path", event_idx, touch_idx, signal, np.float64, "signal")
+        step = check_step("bet_size_path", step)
+        value = DeviceArray(self.ctx, self.n, np.float64)
+        count = DeviceArray(self.ctx, self.n, np.int16) if return_count else None
+        self.ctx.call("fmk_bet_size_path_dev", event_idx.p, touch_idx.p, signal.p, c_i64(event_idx.n), c_i64(self.n), c_f64(step),
+                      value.p, None if count is None else count.p)
+        return (value, count) if return_count else value
+
+    def bet_size_at(self, event_idx: DeviceArray, touch_idx: DeviceArray, signal: DeviceArray, at_idx: Optional[DeviceArray] = None,
+                    step: float = 0.0) -> DeviceArray:
+        """The path of `bet_size_path` at the ticks of an int64 DeviceArray (None: each event's own tick); the path is a temporary
+        of the call.  ValueError also for an index outside the tape."""
+        from .label.betsize import check_step
+        self._bet_events("bet_size_at", event_idx, touch_idx, signal, np.float64, "signal")
+        step = check_step("bet_size_at", step)
+        at = event_idx if at_idx is None else at_idx
+        if at.dtype != np.int64:
+            raise TypeError("bet_size_at: the indices must be int64")
+        out = DeviceArray(self.ctx, at.n, np.float64)
+        self.ctx.call("fmk_bet_size_at_dev", event_idx.p, touch_idx.p, signal.p, c_i64(event_idx.n), c_i64(self.n), c_f64(step),
+                      at.p, c_i64(at.n), out.p)
+        return out
+
+    def bet_size_budget(self, event_idx: DeviceArray, touch_idx: DeviceArray, side: DeviceArray):
+        """bet_size_budget (label/betsize.py) on resident spans and a resident int8 side per event -> (m float64 per tick of this
+        tape, max2): max2 is a device int64 pair, the largest number of concurrent long and short bets."""
+        self._bet_events("bet_size_budget", event_idx, touch_idx, side, np.int8, "side")
+        m, max2 = DeviceArray(self.ctx, self.n, np.float64), DeviceArray(self.ctx, 2, np.int64)
+        self.ctx.call("fmk_bet_size_budget_dev", event_idx.p, touch_idx.p, side.p, c_i64(event_idx.n), c_i64(self.n), m.p, max2.p)
+        return m, max2
+
 
 def to_host(d: Dict[str, DeviceArray]) -> Dict[str, np.ndarray]:
     return {k: v.to_host() for k, v in d.items()}

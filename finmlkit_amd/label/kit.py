@@ -11,6 +11,7 @@ import pandas as pd
 
 from .. import _ffi
 from ..bar.data_model import TradesData
+from .betsize import bet_size_at, signal_from_probability
 from .bootstrap import sequential_bootstrap
 from .tbm import check_arguments
 from .weights import (average_uniqueness, class_balance_weights, normalize_attribution, return_attribution, time_decay)
@@ -251,3 +252,25 @@ class SampleWeights:
         base = combined / mean
         out["weights"] = class_balance_weights(labels=labels.values, base_w=base)[3] if labels is not None else base
         return out
+
+
+class BetSizing:
+    """From a classifier's probabilities to bet sizes (AFML chapter 10; label/betsize.py)."""
+
+    @staticmethod
+    def from_probabilities(labels: pd.DataFrame, prob, pred=None, n_classes: int = 2, step: float = 0.0) -> pd.DataFrame:
+        """`labels`: a frame with `event_idx` / `touch_idx` columns, the one `compute_labels` returns; prob: the probability of the
+        predicted class per row, pred: the predicted class (-1 / 1; default 1, as for meta labels).  -> a frame on the same index:
+        `signal` (`signal_from_probability`, times the frame's `side` column when it has one) and `bet_size`, the average of the
+        signals of the bets open at each event's own tick (`bet_size_at`), discretised when step > 0."""
+        if not isinstance(labels, pd.DataFrame):
+            raise ValueError("Events must be a pandas DataFrame.")
+        if "event_idx" not in labels.columns or "touch_idx" not in labels.columns:
+            raise ValueError("Events DataFrame must contain 'event_idx' and 'touch_idx' columns.")
+        prob = np.asarray(prob, dtype=np.float64)
+        if prob.ndim != 1 or len(prob) != len(labels):
+            raise ValueError("from_probabilities: prob must have one value per row of the frame.")
+        side = labels["side"].values if "side" in labels.columns else None
+        signal = signal_from_probability(prob, None if pred is None else np.asarray(pred), side, n_classes)
+        bet = bet_size_at(labels.event_idx.values, labels.touch_idx.values, signal, step=step)
+        return pd.DataFrame({"signal": signal, "bet_size": bet}, index=labels.index)

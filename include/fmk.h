@@ -855,6 +855,48 @@ int fmk_otr_mesh(fmk_ctx *ctx, const double *forecast, const double *phi, const 
  * tile (walked at once, one per lane), [2] the most levels on either side, [3] the largest max_hp.  Needs no context and no device. */
 int fmk_otr_geometry(int64_t *out4);
 
+/* ---- bet sizing (Lopez de Prado, Advances in Financial Machine Learning, ch. 10, snippets 10.1 - 10.3 and section 10.2; the
+ * reference has no such function: the definition is this project's; csrc/fmk_bet.hip, csrc/fmk_bet_rule.h).
+ * From the signals of the events to the position per tick of the tape: the average of the signals of the bets still open.
+ *   Spans: event i is open on the ticks event_idx[i] <= t < touch_idx[i] -- the bet is closed AT the touch (the book's
+ *     index <= loc < t1), which is not the closed range fmk_label_concurrency counts.  touch_idx[i] == event_idx[i] (a skipped
+ *     label) is never open.  Events in any order, duplicates included.  1 <= n_events <= 2^31 - 1, 1 <= n <= 2^32.
+ *   Signal: float64 in [-1, 1], counted in units of 2^-30: q_i = rint(signal[i] * 2^30), an exact product with one rounding, ties to
+ *     even.
+ *   Value: c[t] the number of open events at tick t, S[t] the sum of their q_i (an integer).  value[t] = fl(S[t] / c[t]) * 2^-30
+ *     where c[t] > 0 -- one correctly rounded division, the scaling is exact -- and +0.0 where c[t] == 0; -0.0 never appears here.
+ *     out_count (int16, may be NULL) receives c[t].
+ *   Discretisation: step == 0: none; 0 < step <= 1: value = min(1, max(-1, rint(value / step) * step)), each operation rounded
+ *     on its own (NumPy's bits).
+ * The sums are integer sums made with integer atomics, so a result is a function of the arguments alone, bit for bit, run to run.
+ * FMK_E_ARG, before a device is touched: n_events or n outside the bounds, a step that is neither 0 nor in (0, 1].  FMK_E_ARG, counted
+ * on the device (the message holds the count; the outputs are then undefined): an event outside 0 <= event_idx <= touch_idx < n, a
+ * signal that is NaN or outside [-1, 1], a concurrency above 32767 on any tick (the message holds the largest).  The sum and the
+ * count are carried in an int64 and an int32 of their own, which cannot wrap below 2^31 events: the last refusal is certain for every
+ * n_events.  Scratch: 12 bytes per tick (rounded up to a tile), freed in the stream's order; the call waits once, for the mailbox. */
+int fmk_bet_size_path_dev(fmk_ctx *ctx, const int64_t *d_event_idx, const int64_t *d_touch_idx, const double *d_signal,
+                          int64_t n_events, int64_t n, double step, double *d_out_value, int16_t *d_out_count);
+int fmk_bet_size_path(fmk_ctx *ctx, const int64_t *event_idx, const int64_t *touch_idx, const double *signal, int64_t n_events,
+                      int64_t n, double step, double *out_value, int16_t *out_count);
+/* out[k] = value[idx[k]] of the path above, k = 0 .. n_idx - 1: the path (8 more bytes per tick) is a temporary of the call.  n_idx ==
+ * 0 is a valid call that still checks the events.  FMK_E_ARG as above, and for an index outside [0, n) (counted on the device). */
+int fmk_bet_size_at_dev(fmk_ctx *ctx, const int64_t *d_event_idx, const int64_t *d_touch_idx, const double *d_signal,
+                        int64_t n_events, int64_t n, double step, const int64_t *d_idx, int64_t n_idx, double *d_out);
+int fmk_bet_size_at(fmk_ctx *ctx, const int64_t *event_idx, const int64_t *touch_idx, const double *signal, int64_t n_events,
+                    int64_t n, double step, const int64_t *idx, int64_t n_idx, double *out);
+/* The budget approach (section 10.2).  side: int8 per event; cl[t] / cs[t] = the open events (spans as above) with side > 0 /
+ * side < 0, side 0 counts nowhere; Ml = max_t cl[t], Ms = max_t cs[t];
+ *   out_m[t] = (Ml ? fl(cl[t] / Ml) : 0) - (Ms ? fl(cs[t] / Ms) : 0),   out_max2 (int64[2], may be NULL) = {Ml, Ms}.
+ * FMK_E_ARG: the bounds of n_events and n, an event outside the tape, Ml or Ms above 32767.  Scratch: 8 bytes per tick. */
+int fmk_bet_size_budget_dev(fmk_ctx *ctx, const int64_t *d_event_idx, const int64_t *d_touch_idx, const int8_t *d_side,
+                            int64_t n_events, int64_t n, double *d_out_m, int64_t *d_out_max2);
+int fmk_bet_size_budget(fmk_ctx *ctx, const int64_t *event_idx, const int64_t *touch_idx, const int8_t *side, int64_t n_events,
+                        int64_t n, double *out_m, int64_t *out_max2);
+/* The kernels' geometry, for callers that place work at its seams: out3[0] the ticks of a tile (one workgroup), [1] the ticks of a
+ * row (one workgroup scan; a thread owns 4 consecutive ticks of it), [2] the tiles of one trip of the aggregate scan.  Needs no
+ * context and no device. */
+int fmk_bet_geometry(int64_t *out3);
+
 /* ---- causal FIR filter on a float64 series of n elements -> float64 array of n elements (csrc/fmk_fir.hip), and with the weights
  * of feature/core/fracdiff.py the fixed-width window fractional differentiation "FFD" (Lopez de Prado, Advances in Financial
  * Machine Learning, ch. 5; the reference has no such function: the definition is this project's).
